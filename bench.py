@@ -12,17 +12,25 @@ reference's default), K = 9 bins, H = 8, B = 5, Adam lr = 0.01, fixed number of 
 trained as ONE batched launch sequence (grid.y = clique).  A "step" is ONE full-batch training iteration of
 all 8 cliques (forward + analytic backward + gradient reduction + Adam).  With N > 1 every rank trains its
 own 8 cliques (weak scaling, no data-path collective: independent cliques never exchange data).
-With N > 1 a second, UNTIMED-for-`value` regime runs behind the headline and is reported as `exchange`: one incremental
+With N > 1 and `--full` a second, UNTIMED-for-`value` regime runs behind the headline and is reported as `exchange`: one incremental
 update of a branching factor graph through `slam.ParallelNFiSAM` -- a binary "meeting tree" of 2^ceil(log2 N) robots, whose
 Bayes tree has one leaf arm per rank and ceil-log2 levels of joins that cross ranks -- i.e. the path north_star describes
 ("RCCL over xGMI carrying separator samples between parent/child cliques"): cross-rank tree edges, bytes, this rank's
 point-to-point and all-gather wall clock, and the update's wall clock on every rank.
 
-Launch: `python bench.py --gpus N --steps K --warmup W`.  Under torchrun (WORLD_SIZE set) this process is one
-rank; without it and N > 1 the script starts N child ranks itself BEFORE touching the GPU and relays rank 0's
-line.
+Launch: `python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]`.  Under torchrun (WORLD_SIZE set)
+this process is one rank; without it and N > 1 the script starts N child ranks itself BEFORE touching the GPU and relays
+rank 0's line.
 
-Prints ONE JSON line on rank 0 (driver contract), including
+A plain run does only what the headline needs: set-up, W warm-up steps, ONE timed run of exactly K steps (the K-step plan,
+bracketed by barrier + synchronize, MAX over ranks; a plan of up to PRIME_MAX_STEPS steps first runs untimed for PRIME_S
+seconds), and the line.  `--dump-outputs DIR` then writes what that run computed in
+its last step -- each clique's trained parameters in the reference's order and the loss of its last iteration -- as
+DIR/<name>.npy (float32); the inputs are seeded, so two builds can be compared output for output.
+
+Prints ONE JSON line on rank 0 (driver contract).  `--full` adds everything that takes runs of its own: the headline as the
+MEDIAN of R replays of the K-step plan (R from K alone) with three more replays carrying HIP events, the `exchange` (N > 1)
+and `replicas` regimes, the config[0] incremental-update wall clock, and
   roofline     : dominant kernel (the gradient kernel of the C3 batch) algorithmic FLOP / its average launch
                  duration, measured live with HIP events, against the fp32 peak of gfx950
                  (157.3 TFLOP/s = f32 MFMA peak = f32 packed-VALU peak); the binding resource is VALU issue.
@@ -53,6 +61,8 @@ sys.path.insert(0, ROOT)
 FP32_PEAK_TFLOPS = 157.3     # /opt/skills/guides/MI355X_MICROARCH.md: f32 MFMA == f32 vector peak
 K, H, B = 9, 8, 5.0
 LR = 0.01
+PRIME_MAX_STEPS = 16384      # a plain run's plan of up to this many steps (< 0.2 s a run) first runs untimed, back to back,
+PRIME_S = 0.05               # for at least this many seconds (at least once): the first runs of a fresh plan are slower
 
 
 def c2_clique(n, seed):
@@ -205,25 +215,36 @@ class Workload:
         return self.nh.TrainBatch(self.xs, [p.clone() for p in self.kp0], K, self.H, B, self.L, lr=LR, max_iters=iters,
                                   average_window=iters, loss_delta_tol=0.0, early_stop=True)
 
-    def time_iterations(self, iters, warmup, barrier, reduce_max=None):
-        """`iters` training iterations of the prepared plan, timed R times (R from `iters` alone, so every rank agrees):
-        each replay restarts from the initial parameters (re-initialised in place, untimed), starts behind a
-        barrier + synchronize, ends at the rank's own synchronize (the closing barrier follows, outside the clock: with
-        RCCL it is a collective of tens of microseconds that would be charged to a 0.3 ms region of an exchange-free job)
-        and is reduced with MAX over ranks; the MEDIAN replay is reported, so that one
-        slow graph launch does not decide a 0.4 ms measurement.  -> (median seconds, median GPU ms, first loss, final loss)"""
+    def time_iterations(self, iters, warmup, barrier, reduce_max=None, full=True, keep_outputs=False):
+        """`iters` training iterations of the prepared plan, after a warm-up plan of `warmup` iterations.  Plain run
+        (full=False): ONE timed run -- exactly `iters` timed steps -- that starts behind a barrier + synchronize and ends at
+        the rank's own synchronize (the closing barrier follows, outside the clock: with RCCL it is a collective of tens of
+        microseconds that would be charged to a 0.3 ms region of an exchange-free job), reduced with MAX over ranks.
+        full=True: the same timed R times (R from `iters` alone, so every rank agrees), each replay restarting from the initial
+        parameters (re-initialised in place, untimed); the MEDIAN replay is reported, so that one slow graph launch does not
+        decide a 0.4 ms measurement, and three more replays carry two HIP events (GPU time of the region).
+        keep_outputs: `self.outputs` = what the last run computed (each clique's parameters in the reference's order, the loss of
+        its last iteration), float32 host arrays.
+        -> (median seconds, median GPU ms or None, first loss, final loss)"""
         torch = self.torch
         tbw = self.batch(max(warmup, 1))
         tbw.run(use_graph=True)
         tbw.close()
         tb = self.batch(iters)
         tb.prepare(use_graph=True)               # one-time graph capture, outside the timed region
-        reps = int(min(200, max(5, math.ceil(0.06 / (iters * 25e-6)))))      # >= ~60 ms of timed work
+        reps = int(min(200, max(5, math.ceil(0.06 / (iters * 25e-6))))) if full else 1     # full: >= ~60 ms of timed work
+        prime_end = time.perf_counter() + PRIME_S
+        while not full and iters <= PRIME_MAX_STEPS:     # untimed, back to back: the first runs of a fresh plan are slower
+            tb.run(use_graph=True)
+            torch.cuda.synchronize()
+            tb.reset(self.kp0)
+            if time.perf_counter() >= prime_end:
+                break
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         dts, gms = [], []
-        ev_reps = 3                              # extra replays that carry the two HIP events (GPU time of the region): the events'
+        ev_reps = 3 if full else 0               # extra replays that carry the two HIP events (GPU time of the region): the events'
         for r in range(reps + ev_reps):          # own stream packets and host calls stay out of the wall-clock replays
-            with_events = r >= reps or os.environ.get("BENCH_EVENTS_IN_REPLAY") == "1"      # (=1: as up to round 5, every replay carries them: A/B)
+            with_events = r >= reps or (full and os.environ.get("BENCH_EVENTS_IN_REPLAY") == "1")      # (=1: as up to round 5, every replay carries them: A/B)
             if r > 0:
                 tb.reset(self.kp0)
             barrier()
@@ -244,13 +265,17 @@ class Workload:
         il = [t.cpu().numpy() for t in tb.iter_loss]
         for v in il:
             assert np.all(np.isfinite(v)) and (iters == 1 or v[iters - 1] < v[0]), (v[0], v[iters - 1])   # --steps 1: one loss value
+        if keep_outputs:
+            self.outputs = {"params_clique%d" % c: self.nh.unpack(p, int(x.shape[1]), K, self.H, self.L).cpu().numpy().astype(np.float32)
+                            for c, (x, p) in enumerate(zip(self.xs, tb.kparams))}
+            self.outputs["last_step_loss"] = np.array([v[iters - 1] for v in il], dtype=np.float32)
         # which form the plan ran in: chunk-persistent launches (a chunk's iterations in ONE launch per chain) report the XCDs
         # their (clique, dim) groups sat on; 0 = one launch per iteration
         self.persistent = tb.xcd_span() > 0
         self.chunk_iters = max(c for c in range(1, min(iters, 128) + 1) if iters % c == 0)    # nsf_kernels.hip: chunk_length()
         tb.close()
         self.replays = reps
-        return (float(np.median(dts)), float(np.median(gms)), float(np.mean([v[0] for v in il])),
+        return (float(np.median(dts)), float(np.median(gms)) if gms else None, float(np.mean([v[0] for v in il])),
                 float(np.mean([v[iters - 1] for v in il])))
 
     def time_persistent_kernel(self, iters, reps=7):
@@ -299,8 +324,13 @@ class Workload:
         tbk.close()
         return us, chains
 
-    def record(self, iters, warmup, barrier, reduce_max=None):
-        dt, gpu_ms, l0, l1 = self.time_iterations(iters, warmup, barrier, reduce_max)
+    def record(self, iters, warmup, barrier, reduce_max=None, full=True, keep_outputs=False):
+        dt, gpu_ms, l0, l1 = self.time_iterations(iters, warmup, barrier, reduce_max, full, keep_outputs)
+        if not full:                             # plain run: the timed region only, no kernel timing of its own
+            return dict(cliques=len(self.xs), D=[int(x.shape[1]) for x in self.xs] if len(self.xs) <= 8 else int(self.xs[0].shape[1]),
+                        particles_per_clique=int(self.xs[0].shape[0]), layers=self.L, hidden_dim=self.H, iterations=iters,
+                        replays=self.replays, us_per_iteration=1e6 * dt / iters, samples_per_s=self.n_samples * iters / dt,
+                        first_loss=l0, final_loss=l1), dt
         kus, chains = self.time_gradient_kernel()
         ach_plain = self.flop_per_launch / (kus * 1e-6) / 1e12
         gpu_us_it = 1e3 * gpu_ms / iters
@@ -588,6 +618,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline: median of replays + HIP-event replays, roofline, regimes, replicas, "
+                         "exchange (N > 1), incremental-update wall clock, CPU baseline (the --no-* options below apply to it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed run computed in its last step as DIR/<name>.npy (float32; rank 0's cliques)")
     ap.add_argument("--regime-steps", type=int, default=200, help="iterations timed per secondary regime")
     ap.add_argument("--no-regimes", action="store_true", help="headline workload only (rocprofv3 runs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -657,10 +692,14 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    head, dt = wl.record(args.steps, args.warmup, barrier, reduce_max)
+    head, dt = wl.record(args.steps, args.warmup, barrier, reduce_max, full=args.full, keep_outputs=bool(args.dump_outputs) and rank == 0)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in wl.outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
 
     regimes = {}
-    if rank == 0 and world == 1 and not args.no_regimes:
+    if args.full and rank == 0 and world == 1 and not args.no_regimes:
         for name in ("C2_single_clique_n4096_D6_L4", "plaza_clique_n2000_D15", "single_clique_n1000_D15", "batch64_n2000_D15", "plaza_clique_n2000_D15_H16",
                      "batch64_n2000_D15_H16", "C2_single_clique_n4096_D6_L4_H16", "C2_single_clique_n4096_D6_L4_H04"):
             prob, L = regime_problem(name, seed0=7)
@@ -668,7 +707,7 @@ def main():
 
     # ---- every N: what N GPUs do for the chain-shaped configs (Plaza1, Manhattan): independent runs per GPU ("replicas only") ----
     replicas_block = None
-    if not args.no_replicas and not args.no_update_bench:
+    if args.full and not args.no_replicas and not args.no_update_bench:
         try:
             per = replicas_regime(world, rank, use_dist)
             good = [r for r in per if "error" not in r]
@@ -690,13 +729,14 @@ def main():
     # ---- N > 1 (or the forced process group of a 1-GPU box): the path that DOES exchange -- ParallelNFiSAM on a branching tree ----
     exchange = None
     hard_exit = False
-    if use_dist and not args.no_exchange:
+    run_exchange = args.full and use_dist and not args.no_exchange
+    box = {}
+    if run_exchange:
         # The regime has NEVER run with more than one RCCL rank (no multi-GPU node was available to this build: DESIGN.md 7); a
         # mismatched point-to-point pair would be a hang, and a hang here would take the headline line -- already measured -- with
         # it.  So it runs in a thread under a watchdog (BENCH_EXCHANGE_TIMEOUT seconds, default 240): if it does not come back,
         # `exchange` says so, the line is printed, and the rank leaves with os._exit (no barrier, no teardown: they would hang too).
         import threading
-        box = {}
 
         def _run_exchange():
             try:
@@ -712,7 +752,7 @@ def main():
             box["error"] = "the exchange regime did not return within its watchdog's time on rank %d" % rank
         elif "error" in box:
             hard_exit = True              # (the other ranks may sit in a collective this rank never entered: do not join their barrier)
-    if "per_rank" in (box if use_dist and not args.no_exchange else {}):
+    if "per_rank" in box:
         try:
             per_rank = box["per_rank"]
             r0 = per_rank[0]
@@ -738,19 +778,18 @@ def main():
                         "Not part of `value`: the headline stays the exchange-free weak-scaling line."}
         except Exception as e:   # noqa: BLE001  (must never break the contract line)
             exchange = {"error": repr(e)[:300]}
-    elif use_dist and not args.no_exchange:
+    elif run_exchange:
         exchange = {"error": box.get("error", "no result")}
 
     if rank == 0:
         total = world * wl.n_samples * args.steps
-        ach = head["achieved_tflops"]
         out = {
             "metric": "flow-training samples/sec/GPU + wall-clock per incremental update",
             "value": total / dt,
             "unit": "samples/s (n x training iterations / s, whole job)",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * dt / args.steps,
-            "timing": "median of %d replays of the %d-step plan (each bracketed by barrier + synchronize, MAX over ranks)" % (wl.replays, args.steps),
+            "timing": ("median of %d replays" % wl.replays if args.full else "one run") + " of the %d-step plan (bracketed by barrier + synchronize, MAX over ranks)" % args.steps,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": "C3 (BASELINE config[2]): 8 independent cliques of the range-only SLAM family per GPU, "
@@ -759,86 +798,91 @@ def main():
                        "cliques_per_gpu": len(problem), "particles": 2000, "D": head["D"], "layers": 1, "K": K, "H": H,
                        "hipgraph": True, "parallelism": "independent cliques per GPU (no collective)"},
             "per_gpu_value": wl.n_samples * args.steps / dt,
-            "gpu_ms_per_step_events": head["gpu_us_per_iteration_events"] / 1e3,
             "final_loss": head["final_loss"], "first_loss": head["first_loss"],
-            "roofline": {"bound": "valu_issue", "achieved": ach, "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": ach / FP32_PEAK_TFLOPS, "traffic": None,
-                         "kernel": "nsf_train1_kernel<9,8,true>" if head["chunk_persistent"] else "nsf_train1_kernel<9,8>",
-                         "kernel_us": head["training_launch_us"], "flop_per_launch": head["training_launch_flop"],
-                         "iterations_per_launch": head["iterations_per_launch"],
-                         "launches_per_training_iteration": head["launches_per_training_iteration"],
-                         "achieved_in_training": head["flop_per_launch"] / (head["gpu_us_per_iteration_events"] * 1e-6) / 1e12,
-                         "one_launch_per_iteration": head["one_launch_per_iteration"],
-                         "note": "fp32 INSTRUCTION-ISSUE-bound kernel (SURVEY.md §8d: ~600 flop/B, HBM does not bind), priced "
-                                 "against the fp32 peak (157.3 TFLOP/s = f32 MFMA = packed f32 VALU).  `kernel` is the kernel the "
-                                 "TIMED REGION ran.  Chunk-persistent form (nsf_train1_kernel<9,8,true>, DESIGN.md §3.1e/f): one "
-                                 "launch (over all (clique, dim) groups) runs `iterations_per_launch` training iterations (gradient + the "
-                                 "previous iteration's Adam update; the blocks of a (clique, dim) group exchange their gradient "
-                                 "copies as tagged words, no kernel boundary); `flop_per_launch` = 333 MFLOP x iterations per launch, "
-                                 "`kernel_us` = the duration of that launch between "
-                                 "two HIP timing events recorded on its stream, measured right behind the timed region in a plan of "
-                                 "the same shape whose chunk end is a graph of its own (rocprofv3's per-launch average for the same "
-                                 "command: profiles/; `achieved_in_training` divides by the timed region's own GPU time per "
-                                 "iteration, closing Adam and bookkeeping kernels included).  One launch per iteration "
-                                 "(nsf_train1_kernel<9,8>): `kernel_us` times the gradient kernel as ONE launch over all groups, "
-                                 "200 back to back in a graph (`one_launch_per_iteration` holds that figure in either case).  Per "
-                                 "(dim, 64-particle tile) unit a wave issues ~560 VALU instructions (~450 of them the spline, 64 "
-                                 "transcendentals), 164 v_mfma_f32_4x4x1 (the conditioner mat-vecs, particle on the lane), 48-64 "
-                                 "v_mfma_f32_16x16x4 (the weight-gradient GEMMs) and ~220 LDS instructions; f32 MFMA and VALU issue of "
-                                 "a SIMD do not overlap on gfx950 (profiles/history/r02_mfma_valu_issue_microbench.txt).  C3 is 2496 "
-                                 "(dim, tile) units on 1024 SIMDs: per iteration and wave ~12 k cycles of arithmetic and ~15 k of "
-                                 "staging (the group's 8 gradient copies -> Adam -> panel), epilogue (block sum, copy out) and "
-                                 "barriers at three waves per SIMD (profiles/r04_phase_cycles_persistent.txt) -- a latency-plus-issue "
-                                 "regime; the 64-clique batch (`regimes.batch64_n2000_D15`) is the throughput regime at ~95 % of what "
-                                 "its instruction mix allows (DESIGN.md §3.1c).  Algorithmic HBM bytes per iteration: 608 KB (x, "
-                                 "read once per CHUNK by the persistent form: the tile stays in LDS) + 112 KB (parameters); "
-                                 "`traffic` = HBM-side bytes per launch from separate rocprofv3 --pmc passes of an earlier run of "
-                                 "this workload (lower bound of the gfx950 FETCH_SIZE range, see `traffic_profiled`), not measured "
-                                 "in this run."},
-            "regimes": regimes,
-            "replicas": replicas_block,
-            "exchange": exchange,
-            # (round 6: nobody should have to dig for it -- the rank still leaves with exit code 0 so that the driver keeps the line)
-            "exchange_failed": (None if exchange is None else ("error" in exchange)),
+            "full": bool(args.full),
         }
-        import glob
-        tjs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_train_kernel_traffic.json")))
-        if tjs:   # HBM bytes per launch from separate rocprofv3 --pmc passes of an EARLIER run of this workload (latest round)
-            try:
-                t = json.load(open(tjs[-1]))
-                out["roofline"]["traffic_profiled"] = dict(t, source="profiles/" + os.path.basename(tjs[-1]))
-                if t.get("kernel") == out["roofline"]["kernel"]:
-                    per_it = t.get("hbm_side_bytes_per_iteration_lower", t.get("hbm_side_bytes_per_launch_lower"))
-                    out["roofline"]["traffic"] = per_it * head["iterations_per_launch"]
-                    out["roofline"]["traffic_provenance"] = ("rocprofv3 --pmc passes of scripts/collect_profiles.sh (%s, collected %s): lower bound of the "
-                                                             "HBM-side bytes per ITERATION of %s (separate FETCH_SIZE / WRITE_SIZE passes) x the %d "
-                                                             "iterations of a launch of this run; a counter figure of that collection, not of this run"
-                                                             % (os.path.basename(tjs[-1]), t.get("profiled_at", "in an earlier round"), t.get("kernel"),
-                                                                head["iterations_per_launch"]))
-                    out["roofline"]["traffic_profiled_at"] = t.get("profiled_at")
-            except Exception:   # noqa: BLE001
-                pass
-        ujs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_issue_utilisation.json")))
-        uj = ujs[-1] if ujs else ""
-        if os.path.exists(uj):   # VALU issue / MFMA busy fractions from the same EARLIER profiled run (not measured here)
-            try:
-                u = json.load(open(uj))
-                out["roofline"]["issue_profiled"] = {k: {f: u[k][f] for f in ("valu_issue_frac", "mfma_busy_frac", "issue_frac")}
-                                                     for k in ("C3", "batch64")}
-                out["roofline"]["issue_profiled"]["source"] = "profiles/" + os.path.basename(uj)
-            except Exception:   # noqa: BLE001
-                pass
-        if args.no_update_bench or world > 1:       # end-to-end update timing and CPU baseline: N = 1 only
-            out["wall_clock_per_incremental_update"] = None
-        else:
-            try:
-                out["wall_clock_per_incremental_update"] = incremental_update_wallclock()
-            except Exception as e:   # noqa: BLE001  (must never break the contract line)
-                out["wall_clock_per_incremental_update"] = {"error": str(e)[:200]}
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(problem)
-        else:
-            out["cpu_baseline"] = None
+        if args.full:
+            ach = head["achieved_tflops"]
+            out.update({
+                "gpu_ms_per_step_events": head["gpu_us_per_iteration_events"] / 1e3,
+                "roofline": {"bound": "valu_issue", "achieved": ach, "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                             "frac": ach / FP32_PEAK_TFLOPS, "traffic": None,
+                             "kernel": "nsf_train1_kernel<9,8,true>" if head["chunk_persistent"] else "nsf_train1_kernel<9,8>",
+                             "kernel_us": head["training_launch_us"], "flop_per_launch": head["training_launch_flop"],
+                             "iterations_per_launch": head["iterations_per_launch"],
+                             "launches_per_training_iteration": head["launches_per_training_iteration"],
+                             "achieved_in_training": head["flop_per_launch"] / (head["gpu_us_per_iteration_events"] * 1e-6) / 1e12,
+                             "one_launch_per_iteration": head["one_launch_per_iteration"],
+                             "note": "fp32 INSTRUCTION-ISSUE-bound kernel (SURVEY.md §8d: ~600 flop/B, HBM does not bind), priced "
+                                     "against the fp32 peak (157.3 TFLOP/s = f32 MFMA = packed f32 VALU).  `kernel` is the kernel the "
+                                     "TIMED REGION ran.  Chunk-persistent form (nsf_train1_kernel<9,8,true>, DESIGN.md §3.1e/f): one "
+                                     "launch (over all (clique, dim) groups) runs `iterations_per_launch` training iterations (gradient + the "
+                                     "previous iteration's Adam update; the blocks of a (clique, dim) group exchange their gradient "
+                                     "copies as tagged words, no kernel boundary); `flop_per_launch` = 333 MFLOP x iterations per launch, "
+                                     "`kernel_us` = the duration of that launch between "
+                                     "two HIP timing events recorded on its stream, measured right behind the timed region in a plan of "
+                                     "the same shape whose chunk end is a graph of its own (rocprofv3's per-launch average for the same "
+                                     "command: profiles/; `achieved_in_training` divides by the timed region's own GPU time per "
+                                     "iteration, closing Adam and bookkeeping kernels included).  One launch per iteration "
+                                     "(nsf_train1_kernel<9,8>): `kernel_us` times the gradient kernel as ONE launch over all groups, "
+                                     "200 back to back in a graph (`one_launch_per_iteration` holds that figure in either case).  Per "
+                                     "(dim, 64-particle tile) unit a wave issues ~560 VALU instructions (~450 of them the spline, 64 "
+                                     "transcendentals), 164 v_mfma_f32_4x4x1 (the conditioner mat-vecs, particle on the lane), 48-64 "
+                                     "v_mfma_f32_16x16x4 (the weight-gradient GEMMs) and ~220 LDS instructions; f32 MFMA and VALU issue of "
+                                     "a SIMD do not overlap on gfx950 (profiles/history/r02_mfma_valu_issue_microbench.txt).  C3 is 2496 "
+                                     "(dim, tile) units on 1024 SIMDs: per iteration and wave ~12 k cycles of arithmetic and ~15 k of "
+                                     "staging (the group's 8 gradient copies -> Adam -> panel), epilogue (block sum, copy out) and "
+                                     "barriers at three waves per SIMD (profiles/r04_phase_cycles_persistent.txt) -- a latency-plus-issue "
+                                     "regime; the 64-clique batch (`regimes.batch64_n2000_D15`) is the throughput regime at ~95 % of what "
+                                     "its instruction mix allows (DESIGN.md §3.1c).  Algorithmic HBM bytes per iteration: 608 KB (x, "
+                                     "read once per CHUNK by the persistent form: the tile stays in LDS) + 112 KB (parameters); "
+                                     "`traffic` = HBM-side bytes per launch from separate rocprofv3 --pmc passes of an earlier run of "
+                                     "this workload (lower bound of the gfx950 FETCH_SIZE range, see `traffic_profiled`), not measured "
+                                     "in this run."},
+                "regimes": regimes,
+                "replicas": replicas_block,
+                "exchange": exchange,
+                # (round 6: nobody should have to dig for it -- the rank still leaves with exit code 0 so that the driver keeps the line)
+                "exchange_failed": (None if exchange is None else ("error" in exchange)),
+            })
+            import glob
+            tjs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_train_kernel_traffic.json")))
+            if tjs:   # HBM bytes per launch from separate rocprofv3 --pmc passes of an EARLIER run of this workload (latest round)
+                try:
+                    t = json.load(open(tjs[-1]))
+                    out["roofline"]["traffic_profiled"] = dict(t, source="profiles/" + os.path.basename(tjs[-1]))
+                    if t.get("kernel") == out["roofline"]["kernel"]:
+                        per_it = t.get("hbm_side_bytes_per_iteration_lower", t.get("hbm_side_bytes_per_launch_lower"))
+                        out["roofline"]["traffic"] = per_it * head["iterations_per_launch"]
+                        out["roofline"]["traffic_provenance"] = ("rocprofv3 --pmc passes of scripts/collect_profiles.sh (%s, collected %s): lower bound of the "
+                                                                 "HBM-side bytes per ITERATION of %s (separate FETCH_SIZE / WRITE_SIZE passes) x the %d "
+                                                                 "iterations of a launch of this run; a counter figure of that collection, not of this run"
+                                                                 % (os.path.basename(tjs[-1]), t.get("profiled_at", "in an earlier round"), t.get("kernel"),
+                                                                    head["iterations_per_launch"]))
+                        out["roofline"]["traffic_profiled_at"] = t.get("profiled_at")
+                except Exception:   # noqa: BLE001
+                    pass
+            ujs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_issue_utilisation.json")))
+            uj = ujs[-1] if ujs else ""
+            if os.path.exists(uj):   # VALU issue / MFMA busy fractions from the same EARLIER profiled run (not measured here)
+                try:
+                    u = json.load(open(uj))
+                    out["roofline"]["issue_profiled"] = {k: {f: u[k][f] for f in ("valu_issue_frac", "mfma_busy_frac", "issue_frac")}
+                                                         for k in ("C3", "batch64")}
+                    out["roofline"]["issue_profiled"]["source"] = "profiles/" + os.path.basename(uj)
+                except Exception:   # noqa: BLE001
+                    pass
+            if args.no_update_bench or world > 1:       # end-to-end update timing and CPU baseline: N = 1 only
+                out["wall_clock_per_incremental_update"] = None
+            else:
+                try:
+                    out["wall_clock_per_incremental_update"] = incremental_update_wallclock()
+                except Exception as e:   # noqa: BLE001  (must never break the contract line)
+                    out["wall_clock_per_incremental_update"] = {"error": str(e)[:200]}
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(problem)
+            else:
+                out["cpu_baseline"] = None
         print(json.dumps(out))
         sys.stdout.flush()
     if hard_exit:                      # (the exchange regime hangs in a collective: so would the barrier and the teardown)

@@ -3,9 +3,10 @@
 # combined with tracing) of the bench.py headline workload (C3) and of the 64-clique throughput batch.
 # usage: scripts/collect_profiles.sh <out dir under gpurun_out>
 out=$GRAFT_REPO_ROOT/$1
+repo="$(cd "$(dirname "$0")/.." && pwd)"
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-B="python3 $GRAFT_REPO_ROOT/bench.py --steps 500 --warmup 50 --no-cpu-baseline --no-update-bench"
+B="python3 $repo/bench.py --steps 500 --warmup 50 --full --no-cpu-baseline --no-update-bench"
 # counters and per-kernel durations are per LAUNCH: the profiled runs issue every iteration as ONE launch (a plan would
 # split big batches into two concurrent launches over disjoint (clique, dim) groups, nfisam_nsf_train_chains); the
 # `*_chains_*` trace keeps the default so that the concurrent launches show up as they run in training

@@ -6,7 +6,7 @@ for rep in 1 2; do
 for cfg in "NFISAM_FUSED_CLOSE=0" "NFISAM_FUSED_CLOSE=1"; do
   for K in 20 500; do
   echo -n "$cfg | " >> gpurun_out/fused_close.txt
-  env $cfg python bench.py --steps $K --warmup 5 --no-regimes --no-cpu-baseline --no-update-bench --no-replicas 2>/dev/null | python -c "
+  env $cfg python bench.py --steps $K --warmup 5 --full --no-regimes --no-cpu-baseline --no-update-bench --no-replicas 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); r=d['roofline']
 print('K=%3d  %.3f us per step  value %.4e  persistent launch %.1f us frac %.4f' % (d['steps'], 1e3*d['ms_per_step'], d['value'], r['kernel_us'], r['frac']))" >> gpurun_out/fused_close.txt

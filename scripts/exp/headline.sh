@@ -2,7 +2,7 @@
 mkdir -p gpurun_out; rm -f gpurun_out/headline.txt
 for rep in 1 2; do
 for K in 500 20; do
-  python bench.py --steps $K --warmup 5 --no-regimes --no-cpu-baseline --no-update-bench 2>/dev/null | python -c "
+  python bench.py --steps $K --warmup 5 --full --no-regimes --no-cpu-baseline --no-update-bench 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); r=d['roofline']
 print('K=%3d  %.3f us per step  value %.4e  persistent launch %.1f us (%s iterations per launch) frac %.4f' % (d['steps'], 1e3*d['ms_per_step'], d['value'], r['kernel_us'], r.get('iterations_per_launch'), r['frac']))" >> gpurun_out/headline.txt

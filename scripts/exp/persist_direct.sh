@@ -5,7 +5,7 @@ NFISAM_PERSIST_DIRECT=1 python -m pytest tests/test_hip_parity.py -x -q -m gpu -
 for rep in 1 2 3; do
 for cfg in "NFISAM_PERSIST_DIRECT=0" "NFISAM_PERSIST_DIRECT=1"; do
   echo -n "$cfg | " >> gpurun_out/persist_direct.txt
-  env $cfg python bench.py --gpus 1 --steps 20 --warmup 5 --no-regimes --no-cpu-baseline --no-update-bench --no-replicas 2>/dev/null | python -c "
+  env $cfg python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-regimes --no-cpu-baseline --no-update-bench --no-replicas 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); r=d['roofline']
 print('K=%3d  %.3f us per step  value %.4e  persistent launch %.1f us' % (d['steps'], 1e3*d['ms_per_step'], d['value'], r['kernel_us']))" >> gpurun_out/persist_direct.txt

@@ -2,8 +2,8 @@
 # the round's last binary: the two bench lines + scripts/collect_profiles.sh (kernel traces, --pmc passes, derived JSONs) again
 out=gpurun_out/r06b
 mkdir -p $out
-python bench.py 2>/dev/null | tail -1 > $out/bench_line.json
-python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $out/bench_line_driver_style_20_steps.json
+python bench.py --full 2>/dev/null | tail -1 > $out/bench_line.json
+python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | tail -1 > $out/bench_line_driver_style_20_steps.json
 bash scripts/collect_profiles.sh $out > $out/collect.log 2>&1
 head -4 $out/c3_trace_kernel_stats.csv | cut -c1-220
 python - <<'PY'

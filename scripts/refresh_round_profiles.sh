@@ -2,7 +2,7 @@
 # Everything profiles/rNN_* is made from, in one gpurun call:  scripts/refresh_round_profiles.sh gpurun_out/<dir>
 out=$1
 mkdir -p $out
-python bench.py 2>/dev/null | tail -1 > $out/bench_line.json
+python bench.py --full 2>/dev/null | tail -1 > $out/bench_line.json
 bash scripts/collect_profiles.sh $out > $out/collect.log 2>&1
 python scripts/run_plaza1.py 100000 $out/plaza1_end_to_end.json > $out/plaza1.log 2>&1
 DATASET=Plaza1ADA0.4EFG python scripts/run_plaza1.py 100000 $out/plaza1_ada04_end_to_end.json > $out/plaza1_ada04.log 2>&1

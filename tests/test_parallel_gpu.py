@@ -149,7 +149,7 @@ def test_bench_two_ranks_prints_the_contract_line():
     The LAST stdout line is the driver's JSON line: whole-job value = 2 x per-rank value, n_gpus = 2, weak scaling."""
     env = dict(os.environ, BENCH_DIST_BACKEND="gloo")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full"],
                        env=env, capture_output=True, text=True, timeout=550)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.strip().split("\n") if l.strip()]
@@ -207,7 +207,7 @@ def test_bench_under_the_launcher_over_rccl_prints_only_the_contract_line():
         env.pop(k, None)
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
                         "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1",
-                        "--steps", "20", "--warmup", "5", "--no-regimes", "--no-update-bench", "--no-cpu-baseline"],
+                        "--steps", "20", "--warmup", "5", "--full", "--no-regimes", "--no-update-bench", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=550)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.split("\n") if l.strip()]
@@ -224,7 +224,7 @@ def test_bench_under_the_launcher_over_rccl_prints_only_the_contract_line():
     # a 0.36 ms region of an exchange-free job would have read 10-25 % of fake scaling loss at N > 1).
     for k in ("BENCH_FORCE_DIST",):
         env.pop(k, None)
-    q = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-regimes",
+    q = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-regimes",
                         "--no-update-bench", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=300)
     assert q.returncode == 0, q.stderr[-2000:]
     alone = json.loads([l for l in q.stdout.split("\n") if l.strip()][-1])
@@ -243,7 +243,7 @@ def test_bench_line_survives_an_exchange_regime_that_does_not_come_back():
         env.pop(k, None)
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
                         "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1",
-                        "--steps", "20", "--warmup", "5", "--no-regimes", "--no-update-bench", "--no-cpu-baseline"],
+                        "--steps", "20", "--warmup", "5", "--full", "--no-regimes", "--no-update-bench", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=550)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.split("\n") if l.strip()]
