@@ -25,6 +25,11 @@ __device__ __forceinline__ void bookkeep_body(const BookArgs& a) {
     float* ring = a.ring;
     float* iter_loss = a.iter_loss;
     nfisam_train_state* st = a.st;
+    // The reads go through global-address-space pointers: a wait for a generic (flat) load also waits for every other flat
+    // load in flight, so the state words could not be consumed while the ring's rows were still arriving.
+    typedef const __attribute__((address_space(1))) float* gf;
+    const gf gring = (gf)ring;
+    typedef __attribute__((address_space(1))) int* gi;
     const int n = a.n, D = a.D;
     const int lane = threadIdx.x & 63;
     const bool worker = threadIdx.x < 256;                           // (block-size independent: see the header)
@@ -33,27 +38,37 @@ __device__ __forceinline__ void bookkeep_body(const BookArgs& a) {
     constexpr int PER_WAVE = LOSS_RING / 4;
     float part[PER_WAVE];
     static_assert(LOSS_SLOTS == 128, "a lane takes slots l and l + 64 of a row");
+    // Everything the body reads from memory is requested up front, instead of one dependent round trip at a time behind the
+    // barriers: the state words first, the host mirror's chunk number (a round trip to host memory; only this block writes it),
+    // the ring's rows, the counters, then -- once the step is known -- the older part of the window mean (the first element of
+    // this thread's share).  The values are those the body read before, consumed in the same order: the same sums.
+    // (the state words as vector loads: a scalar load could meet a stale scalar-cache line where the window-spanning launch calls
+    //  this body again for the next window, and the state was rewritten by vector stores in between)
+    auto state_word = [&](const int& f) { return __hip_atomic_load((gi)&f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    const int s0 = state_word(st->step), stop0 = state_word(st->stop), have_avg = state_word(st->have_avg);
+    const float loss_avg = __int_as_float(state_word(*(const int*)&st->loss_avg));
+    const int err0 = state_word(st->domain_err);
+    const int slower_stop = state_word(st->reserved[2]);             // hold-out validation: the scheduled end (nsf_validate_kernel), 0: none
+    const int span_prev = state_word(st->reserved[1]);               // (nobody else writes it while this block runs)
+    // (loads with no condition around them: a value loaded under a branch is waited for where the branch ends)
+    const int seq_pre = __hip_atomic_load((gi)(a.mirror != nullptr ? &a.mirror->reserved[0] : &st->reserved[0]), __ATOMIC_RELAXED,
+                                          __HIP_MEMORY_SCOPE_SYSTEM);      // (no mirror: a harmless read, unused)
+    // (the loads are unconditional -- a thread that is no worker reads wave 0's rows and drops them -- so that all 2 x PER_WAVE of
+    //  them are in flight at once: a load under `worker ? ... : 0` became a branch per row with its own wait for the data, i.e.
+    //  PER_WAVE dependent round trips, which made this block the closing kernel's critical path)
 #pragma unroll
-    for (int k = 0; k < PER_WAVE; ++k)                                                       // ring row w + 4k
-        part[k] = worker ? ring[(w + 4 * k) * LOSS_SLOTS + lane] + ring[(w + 4 * k) * LOSS_SLOTS + 64 + lane] : 0.0f;   // (launches of up to 128 blocks use the lower half only: x + 0)
-    // the group-barrier counters of the chunk-persistent training kernel (one per dim; nsf_unit.hip: bits 0-22 arrivals,
-    // 23-30 the XCC ids the group's blocks ran on, 31 the group's abort flag): looked at, then zeroed for the next chunk
-    int stalled = 0, xcd_span = 0;
-    if (threadIdx.x < FUSED_COUNTERS) {                              // (= the block's first wave)
-        unsigned* ctr = (unsigned*)(ring + (size_t)LOSS_RING * LOSS_SLOTS) + threadIdx.x;
-        const bool close_word = a.zero_counters == 2 && (threadIdx.x == CLOSE_WORD_STEP || threadIdx.x == CLOSE_WORD_STOP);
-        const unsigned cv = close_word ? 0u : *ctr;
-        if (a.zero_counters && !close_word) *ctr = 0u;
-        stalled = __any((int)(cv >> 31));
-        int span = __popc((cv >> 23) & 0xffu);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) { const int o = __shfl_xor(span, off, 64); span = o > span ? o : span; }
-        xcd_span = span;
+    for (int k = 0; k < PER_WAVE; ++k) {                                                     // ring row w + 4k
+        const float lo = gring[(w + 4 * k) * LOSS_SLOTS + lane], hi = gring[(w + 4 * k) * LOSS_SLOTS + 64 + lane];
+        part[k] = worker ? lo + hi : 0.0f;                                                   // (launches of up to 128 blocks use the lower half only: x + 0)
     }
-    const int s0 = st->step, stop0 = st->stop, have_avg = st->have_avg;
-    const float loss_avg = st->loss_avg;
-    int new_step = s0, new_stop = stop0, new_have = have_avg, new_err = st->domain_err;
-    const int slower_stop = st->reserved[2];                         // hold-out validation: the scheduled end (nsf_validate_kernel), 0: none
+    unsigned* ctr = (unsigned*)(ring + (size_t)LOSS_RING * LOSS_SLOTS) + (threadIdx.x & (FUSED_COUNTERS - 1));
+    const unsigned cv_raw = *(const __attribute__((address_space(1))) unsigned*)ctr;
+    const int cnt_pre = (a.chunk < a.cfg.max_iters - s0) ? a.chunk : (a.cfg.max_iters - s0);
+    const int wnd_pre = a.cfg.average_window, j_pre = s0 + cnt_pre - wnd_pre + (int)threadIdx.x;
+    const bool have_pre = worker && wnd_pre > 0 && cnt_pre > 0 && ((s0 + cnt_pre) % wnd_pre) == 0 && j_pre >= 0 && j_pre < s0;
+    const float old_pre = ((gf)iter_loss)[have_pre ? j_pre : 0];     // (iter_loss[0] always exists: no branch, see above)
+    __builtin_amdgcn_sched_barrier(0);                               // (all of the above in flight before the ring's rows are summed)
+    int new_step = s0, new_stop = stop0, new_have = have_avg, new_err = err0;
     float new_avg = loss_avg;
     __shared__ float s_loss[LOSS_RING];
     __shared__ float s_wsum[4];
@@ -96,7 +111,7 @@ __device__ __forceinline__ void bookkeep_body(const BookArgs& a) {
             if (wnd > 0 && (t_end % wnd) == 0) {   // window mean over iter_loss[t_end - wnd, t_end): this chunk's part from LDS
                 float sm = 0.0f;
                 for (int j = t_end - wnd + (int)threadIdx.x; j < t_end && worker; j += NTW)
-                    sm += (j >= s0) ? s_loss[j - s0] : iter_loss[j];
+                    sm += (j >= s0) ? s_loss[j - s0] : ((have_pre && j == j_pre) ? old_pre : iter_loss[j]);
                 sm = wave_sum(sm);
                 if (lane == 0 && worker) s_wsum[w] = sm;
                 __syncthreads();
@@ -113,21 +128,35 @@ __device__ __forceinline__ void bookkeep_body(const BookArgs& a) {
         // (reference NFiSAM.py:453-456: the loop breaks in front of iteration i when i + 1 >= slower_stop_iter)
         if (slower_stop != 0 && new_step + 1 >= slower_stop) new_stop = 1;
     }
+    // the group-barrier counters of the chunk-persistent training kernel (one per dim; nsf_unit.hip: bits 0-22 arrivals,
+    // 23-30 the XCC ids the group's blocks ran on, 31 the group's abort flag): looked at (read above), then zeroed for the next chunk
+    int stalled = 0, xcd_span = 0;
+    if (threadIdx.x < FUSED_COUNTERS) {                              // (= the block's first wave)
+        const bool close_word = a.zero_counters == 2 && (threadIdx.x == CLOSE_WORD_STEP || threadIdx.x == CLOSE_WORD_STOP);
+        const unsigned cv = close_word ? 0u : cv_raw;
+        if (a.zero_counters && !close_word) *ctr = 0u;
+        stalled = __any((int)(cv >> 31));
+        int span = __popc((cv >> 23) & 0xffu);
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) { const int o = __shfl_xor(span, off, 64); span = o > span ? o : span; }
+        xcd_span = span;
+    }
     if (threadIdx.x == 0) {
         if (stalled) {                                               // a group barrier of the chunk timed out: the run is over, loudly
             new_err |= NFISAM_STATE_STALLED; new_stop = 1;
             st->domain_err = new_err; st->stop = new_stop;
         }
-        if (xcd_span > st->reserved[1]) st->reserved[1] = xcd_span;   // most XCDs a (clique, dim) group of a persistent chunk spanned
+        const int span_new = xcd_span > span_prev ? xcd_span : span_prev;
+        if (xcd_span > span_prev) st->reserved[1] = xcd_span;       // most XCDs a (clique, dim) group of a persistent chunk spanned
         if (active) {
             st->loss_avg = new_avg; st->have_avg = new_have; st->domain_err = new_err; st->stop = new_stop; st->step = new_step;
         }
         if (a.mirror != nullptr) {
             nfisam_train_state* m = a.mirror;
-            const int seq = __hip_atomic_load(&m->reserved[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) + 1;
+            const int seq = seq_pre + 1;
             m->step = new_step; m->stop = new_stop; m->have_avg = new_have; m->loss_avg = new_avg; m->domain_err = new_err;
-            m->reserved[1] = st->reserved[1];
-            m->reserved[2] = st->reserved[2];
+            m->reserved[1] = span_new;
+            m->reserved[2] = slower_stop;
             __hip_atomic_store(&m->reserved[0], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }

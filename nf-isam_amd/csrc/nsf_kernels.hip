@@ -50,7 +50,8 @@ struct AdamArgs {
 #define NSF_BOOKKEEP_BLOCK(a, clique, zc)                                                                            \
     do {                                                                                                             \
         const bool batched_ = (a).cliques != nullptr;                                                                \
-        const nfisam_clique* cp_ = batched_ ? ((a).cliques + (clique)) : nullptr;                                    \
+        const __attribute__((address_space(1))) nfisam_clique* cp_ =      /* (global loads: see nsf_bookkeep.h) */   \
+            batched_ ? ((const __attribute__((address_space(1))) nfisam_clique*)(a).cliques + (clique)) : nullptr;      \
         float* G_ = batched_ ? cp_->kgrad : (a).single.kgrad;                                                        \
         const int D_ = batched_ ? cp_->D : (a).single.D;                                                             \
         const int PoP_ = pop_of((a).K);                                                                              \

@@ -101,6 +101,7 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 #if defined(NSF_STAMPS) && NSF_UNIT == 0   // stamps exist in the K = 9, H = 8 unit only
 __device__ unsigned long long g_stamps[64 * 32];
 __device__ unsigned long long g_blk[4096 * 2];
+__device__ unsigned long long g_stamps_it[64 * 32];   // NSF_STAMPS == 3, chunk-persistent: the sums after iteration 0 (words 0-15) and after K - 2 (16-31)
 __device__ __forceinline__ unsigned long long g_stamps_t0(int) { return 0ull; }
 #if NSF_STAMPS == 3      // pinned: per-phase cycle sums in LDS (nsf_train1_kernel only); PSTAMP ties the phase's results to the stamp
 #define STAMP_DECL unsigned long long sprev_ = 0ull;
@@ -153,6 +154,9 @@ extern "C" int nfisam_debug_write_stamps(const unsigned long long* in) {
     return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), in, sizeof(unsigned long long) * 64 * 32);
 }
 #if NSF_STAMPS == 3
+extern "C" int nfisam_debug_read_stamps_it(unsigned long long* out) {
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps_it), sizeof(unsigned long long) * 64 * 32);
+}
 extern "C" int nfisam_debug_read_stg(unsigned long long* out, int zero) {
     if (zero) { unsigned long long z[32] = {0ull}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_stg), z, sizeof(z)); }
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stg), sizeof(unsigned long long) * 32);
@@ -2074,6 +2078,12 @@ nsf_train1_kernel(const nfisam_clique* h_cliques, const uint32_t* h_panel_map, u
     if constexpr (!PERSIST) {
         break;
     } else {
+#if defined(NSF_STAMPS) && NSF_STAMPS == 3 && NSF_UNIT == 0
+        // the first iteration (prologue, tile, the chunk's first staging and rendez-vous, the units' first pass) and the last one
+        // apart from the steady ones: snapshots of the running sums after iteration 0 and after iteration K - 2
+        if ((it == 0 || it == AF(persist_iters) - 2) && STAMP_SEL && lane0 < 16 && w < 4)
+            g_stamps_it[STAMP_SLOT * 32 + (it == 0 ? 0 : 16) + lane0] = (unsigned long long)((unsigned*)smem)[PANEL_BASE - 64 + w * 16 + lane0];
+#endif
         if (++it >= AF(persist_iters)) break;                 // (no barrier: the next staging waits for the copies' tags)
     }
   }

@@ -66,3 +66,16 @@ if hasattr(lib, "nfisam_debug_read_stg"):
 for w in (4, 5, 4 * (D // 2), 4 * (D - 1)):
     if w < 64:
         print("  slot %2d (dim %2d wave %d): " % (w, w // 4, w % 4) + " ".join("%s=%d" % (names[i], st[w][i]) for i in range(1, 10)))
+# chunk-persistent: iteration 0 (prologue, tile, the chunk's first staging and rendez-vous, the units' first pass on cold code) and
+# the last iteration apart from the steady ones (snapshots of the running sums after iteration 0 and after iteration K - 2)
+if per > 1 and hasattr(lib, "nfisam_debug_read_stamps_it"):
+    sb = (C.c_ulonglong * (64 * 32))()
+    assert lib.nfisam_debug_read_stamps_it(sb) == 0
+    si = np.array(sb[:]).reshape(64, 32).astype(np.int64)
+    tot = np.array(buf[:]).reshape(64, 32)[:, 16:32].astype(np.int64)
+    first, upto = si[rows, 0:16].mean(0), si[rows, 16:32].mean(0)
+    steady, last = (upto - first) / (per - 2), tot[rows].mean(0) - upto
+    print("  iteration 0 / steady (mean of 1 .. %d) / last, cycles per phase (mean over the stamped waves):" % (per - 2))
+    for i in range(1, 13):
+        print("  %-14s %8.0f %8.0f %8.0f" % (names[i], first[i], steady[i], last[i]))
+    print("  %-14s %8.0f %8.0f %8.0f" % ("total", first[1:13].sum(), steady[1:13].sum(), last[1:13].sum()))
