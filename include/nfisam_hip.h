@@ -148,6 +148,30 @@ int nfisam_nsf_posterior_walk(const nfisam_post_clique* table, int n_cliques, co
                               int max_D, int K, int H, float B, int L, int n, const float* Zt, float* St,
                               nfisam_stream_t stream);
 
+/* The joint log-density of the tree's posterior at n given points, not in the reference (whose per-sample
+ * separator_forward / log_pdf is scrambled for n > 1): the walk run FORWARD.  For every clique c of
+ * `table` (the walk's table, cols and obs, same meaning), with D = n_obs + n_sep + n_frontal:
+ *   u = [true observations | separator columns | frontal columns] of the point, normalised as
+ *       NormalizingFlowModelWithSeparator.normalize_samples (src/slam/NFiSAM.py:96-106: angle columns wrap(u - mean) / std
+ *       with wrap to [-pi, pi), others (u - mean) / std);
+ *   z = the L-layer forward of u (NSF_AR.forward, src/flows/flows.py:65-93; the first D of D_model dims, as
+ *       NormalizingFlowModelWithSeparator.separator_forward evaluates a marginal, src/slam/NFiSAM.py:157-173);
+ *   term_c = sum over the frontal columns d of [ -z_d^2/2 - log(2 pi)/2 + sum_l log|dz^l_d / dz^(l-1)_d| - log std_d ]
+ *          = log q_c(frontal | separator, observations) in the variables' own units (metres, radians).
+ * log_q[p] = sum of term_c over the cliques in table order.  Observation and separator columns only condition.  The density
+ * is periodic in every angle; on the circle it is normalised up to the mass the flow puts beyond +-pi/std.
+ *   St[total_dim][n]: the points, COLUMN-major as the walk writes them; log_q[n];
+ *   per_clique[n_cliques][n] (nullable): term_c of every point -- without it the library takes a scratch buffer of that
+ *     size from the stream-ordered allocator for the call;
+ *   latent[total_dim][n] (nullable): z_d of every frontal column, at the row the walk reads that column's latent draw from
+ *     (walk order: sum_{c' < c} n_frontal(c') + j); other rows are not written.
+ * Two launches (one block per (clique, 64-point tile), then the per-point sum in table order); no float atomics: two calls
+ * give the same bits.  The column indices in `cols` must lie in [0, total_dim) (the binding checks them; the device
+ * table is not read on the host).  NFISAM_ERR_ARG: unsupported (K, H), NULL table / cols / St / log_q, a bad count. */
+int nfisam_nsf_posterior_log_density(const nfisam_post_clique* table, int n_cliques, const int32_t* cols, const float* obs,
+                                     int max_D, int K, int H, float B, int L, int n, const float* St, float* log_q,
+                                     float* per_clique, float* latent, nfisam_stream_t stream);
+
 /* Training-batch normalisation on the device (NFiSAM.normalize_training_samples, src/slam/NFiSAM.py:515-548):
  * per column c of x[n,D]: Euclidean -> mean / population std; circular[c] != 0 -> mean = direction of the mean
  * resultant (scipy.stats.circmean(., high=pi, low=-pi)), deviations wrapped to [-pi, pi), std of the wrapped

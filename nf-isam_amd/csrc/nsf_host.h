@@ -109,6 +109,9 @@ struct NsfUnitOps {
                    float* logdet, hipStream_t s);
     int (*walk)(const nfisam_post_clique* table, int n_cliques, const int32_t* cols, const float* obs, int max_D, float B,
                 int L, int n, const float* Zt, float* St, hipStream_t s);
+    // posterior log-density, first pass: per[c][p] = clique c's term at point p (latent nullable)
+    int (*density)(const nfisam_post_clique* table, int n_cliques, const int32_t* cols, const float* obs, int max_D, float B,
+                   int L, int n, const float* St, float* per, float* latent, hipStream_t s);
     int (*train)(const TrainArgs& a, int n_cliques, int max_n, int max_D, hipStream_t s);   // gradient kernel of an iteration
     int (*prepare)(int max_D);      // device-resident tables of the training kernels (idempotent; call once outside stream capture)
     // nsf_train3_kernel (two dims per wave): LDS bytes of a launch (0: the launch does not fit that kernel) and the

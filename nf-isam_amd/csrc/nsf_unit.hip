@@ -13,6 +13,7 @@
 //                               nsf_train_kernel (one lane per particle; big launches, hidden_dim != 8, A/B)
 //   inverse    one wave per 64 particles, dims sequential (true data dependence, flows.py:115-137)
 //   walk       whole Bayes tree root -> leaves in one launch
+//   density    whole Bayes tree at given points: one block per (clique, particle tile), no chain
 #include <stddef.h>
 #include <type_traits>
 #include <vector>
@@ -3404,6 +3405,96 @@ __global__ void __launch_bounds__(64) nsf_posterior_walk2_kernel(WalkArgs a) {
     }
 }
 
+// =============================================================================================
+// posterior log-density of a whole Bayes tree at given points: the walk run FORWARD
+// (reference: the per-clique forward src/flows/flows.py:65-93 behind NormalizingFlowModelWithSeparator.separator_forward,
+// src/slam/NFiSAM.py:157-173).  Given the whole point, every clique's term depends on known columns only, so there is
+// no chain: block = (clique, tile of 64 points), W = 4 or 1 waves (unit_density).  The waves gather the clique's
+// [obs | separator | frontal] row from the column-major sample matrix (one coalesced run per column) and normalise it into LDS; then wave w evaluates
+// the columns w, w + W, ... of each layer (layers before the last: all D columns, the next layer conditions on them;
+// the last layer: the frontal columns only) and sums the frontal columns' terms; the W partial sums are added in
+// wave order and written to per[c][p].  nsf_density_sum_kernel adds per[.][p] in table order (no float atomics).
+// =============================================================================================
+constexpr int DENS_WAVES = 4;                 // most waves per block (W = blockDim.x / 64)
+
+template <int K, int H>
+__global__ void __launch_bounds__(64 * DENS_WAVES) nsf_posterior_density_kernel(
+        const nfisam_post_clique* __restrict__ table, const int32_t* __restrict__ cols, const float* __restrict__ obs,
+        float B, int L, int n, int tiles, int dmax, const float* __restrict__ St, float* __restrict__ per,
+        float* __restrict__ latent) {
+    using LY = Layout<K, H>;
+    constexpr int PoP = LY::PoP;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int c = blockIdx.x / tiles, p0 = (blockIdx.x - c * tiles) * TILE;
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int W = blockDim.x >> 6;
+    const nfisam_post_clique q = table[c];
+    const int n_obs = q.n_obs, n_sep = q.n_sep, Ds = n_obs + n_sep, D = Ds + q.n_frontal;
+    float* xa = smem;                                   // [dmax][TILE] layer input
+    float* xb = xa + (size_t)dmax * TILE;               // [dmax][TILE] layer output (L > 1)
+    float* part = xb + (L > 1 ? (size_t)dmax * TILE : 0);   // [DENS_WAVES][TILE] partial sums
+    int* zoff_s = (int*)(part + DENS_WAVES * TILE);     // latent row of the clique's first frontal column
+    if (latent != nullptr && w == 0) {                  // = frontal columns of the cliques in front of it (walk order)
+        int s = 0;
+        for (int k = lane; k < c; k += 64) s += table[k].n_frontal;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+        if (lane == 0) *zoff_s = s;
+    }
+    // the row: true observations (the same for every point), separator and frontal columns; normalised as
+    // NormalizingFlowModelWithSeparator.normalize_samples (src/slam/NFiSAM.py:96-106)
+    for (int e = threadIdx.x; e < D * TILE; e += (int)blockDim.x) {
+        const int k = e / TILE, p = e - k * TILE;
+        const int gp = p0 + p;
+        float v = 0.0f;
+        if (k < n_obs) v = obs[q.obs_off + k];
+        else if (gp < n) {
+            const int col = (k < Ds) ? cols[q.sep_off + (k - n_obs)] : cols[q.front_off + (k - Ds)];
+            v = St[(size_t)col * n + gp];
+        }
+        const float d = v - q.mean[k];
+        xa[k * TILE + p] = (q.circular[k] ? wrap_pi(d) : d) / q.std[k];
+    }
+    __syncthreads();
+    cfloat* kp = (cfloat*)q.kparams;
+    const int Pk = LY::count(q.D_model);
+    const int gp = p0 + lane;
+    float* xin = xa;
+    float* xout = xb;
+    float acc = 0.0f;
+    for (int l = 0; l < L; ++l) {
+        cfloat* lp = kp + (size_t)l * Pk;
+        const bool last = (l == L - 1);
+        for (int i = (last ? Ds : 0) + w; i < D; i += W) {
+            float h1[H], h2[H], th[PoP];
+            load_theta<K, H, cfloat*>(lp, i, xin, TILE, lane, h1, h2, th);
+            Spline<K> S;
+            float zz, lad;
+            spline_eval<K, PoP, false>(xin[i * TILE + lane], th, B, S, zz, lad);
+            if (i >= Ds) acc += lad;
+            if (!last) {
+                xout[i * TILE + lane] = zz;
+            } else {
+                // standard-normal prior of the latent column and the normalisation's Jacobian 1 / std
+                acc += -0.5f * zz * zz - 0.9189385332046727f - logf(q.std[i]);
+                if (latent != nullptr && gp < n) latent[(size_t)(*zoff_s + (i - Ds)) * n + gp] = zz;
+            }
+        }
+        if (!last) {
+            __syncthreads();
+            float* t = xin; xin = xout; xout = t;
+        }
+    }
+    part[w * TILE + lane] = acc;
+    __syncthreads();
+    if (w == 0 && gp < n) {
+        float s = part[lane];
+        for (int v = 1; v < W; ++v) s += part[v * TILE + lane];
+        per[(size_t)c * n + gp] = s;
+    }
+}
+
 
 // =============================================================================================
 // launchers of one (K, H) pair
@@ -3461,6 +3552,28 @@ static int unit_walk(const nfisam_post_clique* table, int n_cliques, const int32
     if (rc) return rc;
     hipLaunchKernelGGL((nsf_posterior_walk_kernel<KK, HH>), dim3((n + TILE - 1) / TILE), dim3(64), lds, s, table, n_cliques, cols,
                        obs, B, L, n, max_D, Zt, St);
+    HIP_TRY(hipGetLastError());
+    return NFISAM_OK;
+}
+
+template <int KK, int HH>
+static int unit_density(const nfisam_post_clique* table, int n_cliques, const int32_t* cols, const float* obs, int max_D,
+                        float B, int L, int n, const float* St, float* per, float* latent, hipStream_t s) {
+    // one (clique, tile) block; LDS = the layer input (and output when L > 1) rows of the widest clique + the partial sums
+    const size_t lds = ((size_t)max_D * TILE * (L > 1 ? 2 : 1) + (size_t)DENS_WAVES * TILE + 4) * sizeof(float);
+    int rc = set_lds(nsf_posterior_density_kernel<KK, HH>, lds);
+    if (rc) return rc;
+    const int tiles = (n + TILE - 1) / TILE;
+    const long blocks = (long)tiles * (long)n_cliques;
+    if (blocks > 0x7fffffffL) return NFISAM_ERR_ARG;
+    // Four waves share a block's (clique, tile) while the launch is small: the frontal columns run side by side, which is what
+    // a latency-bound launch wants; once the launch is large the waves without a column of their own (a clique has ~3 frontal
+    // columns) only hold CU slots, and one wave per block takes the columns in turn.  Final Plaza1 tree, 777 cliques, whole
+    // call (A/B of two builds): n = 500 (6.2 k blocks) 242 us with 4 waves, 261 with 1; n = 10 000 (122 k blocks) 1028 us
+    // with 4, 877 with 1 (profiles/r07_posterior_density_trace.txt)
+    const int W = (blocks <= 16384) ? DENS_WAVES : 1;
+    hipLaunchKernelGGL((nsf_posterior_density_kernel<KK, HH>), dim3((unsigned)blocks), dim3(64 * W), lds, s, table, cols,
+                       obs, B, L, n, tiles, max_D, St, per, latent);
     HIP_TRY(hipGetLastError());
     return NFISAM_OK;
 }
@@ -3947,7 +4060,7 @@ static int unit_train(const TrainArgs& a_in, int n_cliques, int max_n, int max_D
 
 // ---- the unit's table -------------------------------------------------------------------------------------------
 #define NSF_OPS_ENTRY(k, h) \
-    {k, h, unit_forward<k, h>, unit_inverse<k, h>, unit_walk<k, h>, unit_train<k, h>, unit_prepare<k, h>, pair_kernel_lds<k, h>, unit_pair_map<k, h>, unit_persist_places<k, h>},
+    {k, h, unit_forward<k, h>, unit_inverse<k, h>, unit_walk<k, h>, unit_density<k, h>, unit_train<k, h>, unit_prepare<k, h>, pair_kernel_lds<k, h>, unit_pair_map<k, h>, unit_persist_places<k, h>},
 static const NsfUnitOps g_unit_ops[] = {NSF_FOR_EACH_KH(NSF_OPS_ENTRY)};
 
 #define NSF_UNIT_FN_(u) nsf_unit_ops_u##u

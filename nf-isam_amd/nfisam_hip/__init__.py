@@ -27,6 +27,7 @@ EXPORTS = [
     "nfisam_nsf_train_plan_begin", "nfisam_nsf_train_plan_enqueue", "nfisam_nsf_train_plan_peek", "nfisam_nsf_train_plan_stream",
     "nfisam_nsf_train_plan_end", "nfisam_nsf_train_plan_xcd_span", "nfisam_nsf_train_plan_kernel_ms", "nfisam_nsf_train_plan_create_validated", "nfisam_nsf_train_plan_feed", "nfisam_nsf_train_plan_enqueued", "nfisam_nsf_train_plan_refill",
     "nfisam_normalize_columns", "nfisam_simulate_clique", "nfisam_nsf_train_plan_launch_async",
+    "nfisam_nsf_posterior_log_density",
 ]
 
 
@@ -683,3 +684,58 @@ def posterior_walk_raw(table: np.ndarray, cols: np.ndarray, obs: np.ndarray, tot
                                            int(max_D), int(K), int(H), C.c_float(B), int(L), int(n), _ptr(Zt), _ptr(St),
                                            _stream()), "nfisam_nsf_posterior_walk")
     return St.t().contiguous()
+
+
+def posterior_log_density(table: np.ndarray, cols: np.ndarray, obs: np.ndarray, S, max_D, K, H, B, L, device,
+                          per_clique=False, latent=False):
+    """Joint log-density of the tree's posterior at the n rows of S (nfisam_nsf_posterior_log_density): the clique table
+    of `posterior_walk_raw` (numpy POST_DTYPE, parents first), S [n, total_dim] as the walk returns it (tensor or numpy).
+    Launched on the current stream.  -> log_q [n] (device tensor); with per_clique or latent: (log_q, per [n_cliques, n] or
+    None, latent [total_dim, n] or None) -- `latent` holds z of every frontal column at the row of Zt the walk reads that
+    column's draw from (rows of no frontal column are zero)."""
+    if not isinstance(table, np.ndarray) or table.dtype != POST_DTYPE or table.ndim != 1:
+        raise ValueError("table must be a 1-D numpy array of POST_DTYPE")
+    if not (torch.is_tensor(S) or isinstance(S, np.ndarray)) or S.ndim != 2:
+        raise ValueError("S must be a [n, total_dim] tensor or array")
+    n, total_dim = int(S.shape[0]), int(S.shape[1])
+    cols = np.asarray(cols, dtype=np.int32).reshape(-1)
+    obs = np.asarray(obs, dtype=np.float32).reshape(-1)
+    if not supported(K, H):
+        raise ValueError("num_knots=%r, hidden_dim=%r: no kernels for this (K, H)" % (K, H))
+    if int(L) < 1 or not float(B) > 0 or int(max_D) < 1:
+        raise ValueError("L >= 1, B > 0 and max_D >= 1 are required")
+    nc = int(table.shape[0])
+    if nc:
+        n_obs, n_sep, n_fr = (table[f].astype(np.int64) for f in ("n_obs", "n_sep", "n_frontal"))
+        Dm = table["D_model"].astype(np.int64)
+        if (min(n_obs.min(), n_sep.min(), n_fr.min()) < 0 or np.any(n_obs + n_sep + n_fr > Dm) or Dm.max() > int(max_D)
+                or Dm.min() < 1):
+            raise ValueError("a clique's columns exceed its model dimension, or a model dimension exceeds max_D")
+        if (np.any(table["obs_off"] < 0) or np.any(table["sep_off"] < 0) or np.any(table["front_off"] < 0)
+                or np.any(table["obs_off"] + n_obs > obs.size) or np.any(table["sep_off"] + n_sep > cols.size)
+                or np.any(table["front_off"] + n_fr > cols.size)):
+            raise ValueError("a clique's offsets run past `obs` / `cols`")
+        if cols.size and not 0 <= int(cols.min()) <= int(cols.max()) < total_dim:
+            raise ValueError("a column index is out of range of the %d columns of S" % total_dim)
+        if latent and int(n_fr.sum()) > total_dim:
+            raise ValueError("the cliques' frontal columns exceed the %d latent rows" % total_dim)
+    if torch.is_tensor(S):
+        St = S.to(device=device, dtype=torch.float32).t().contiguous()
+    else:
+        St = torch.from_numpy(np.ascontiguousarray(S.T, dtype=np.float32)).to(device)
+    log_q = torch.empty(n, dtype=torch.float32, device=device)
+    # the per-clique terms are the first pass's output; they come from torch's allocator even when the caller does not want
+    # them (the C entry would otherwise take a scratch buffer from HIP's own stream-ordered pool)
+    per = torch.empty(nc, n, dtype=torch.float32, device=device)
+    lat = torch.zeros(total_dim, n, dtype=torch.float32, device=device) if latent else None
+    if nc == 0 or n == 0:
+        log_q.zero_()                                       # the empty tree / no points: nothing to launch
+    else:
+        tbl, cols_t, obs_t = upload(table.view(np.uint8).reshape(-1), cols if cols.size else np.zeros(1, dtype=np.int32),
+                                    obs if obs.size else np.zeros(1, dtype=np.float32), device=device)
+        _check(lib().nfisam_nsf_posterior_log_density(C.c_void_p(tbl.data_ptr()), nc, _ptr(cols_t), _ptr(obs_t), int(max_D),
+                                                      int(K), int(H), C.c_float(B), int(L), n, _ptr(St), _ptr(log_q), _ptr(per),
+                                                      _ptr(lat), _stream()), "nfisam_nsf_posterior_log_density")
+    if per_clique or latent:
+        return log_q, (per if per_clique else None), lat
+    return log_q

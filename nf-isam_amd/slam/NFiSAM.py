@@ -735,6 +735,19 @@ class NFiSAM(FactorGraphSolver):
         slam.ReplicaNFiSAM)."""
         start = time.time()
         num_samples = self._args.posterior_sample_num
+        t = self._posterior_table()
+        K, H, B, L = t["cfg"]
+        S = _nh.posterior_walk_raw(t["table"], t["cols"], t["obs"], t["total_dim"], num_samples, t["max_D"],
+                                   K, H, B, L, t["device"])
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream())
+        return dict(S=S, pcol=t["pcol"], order=list(self._elimination_ordering), start=start,
+                    stream=torch.cuda.current_stream(), keep=t["models"], done=done)
+
+    def _posterior_table(self):
+        """The clique table of the current physical tree (root first, parents before children) that the tree walk and the
+        log-density evaluation share: dict(cliques, table (numpy POST_DTYPE), cols, obs, cfg (K, H, B, L), device, max_D,
+        pcol (variable -> first column of the sample matrix), total_dim, models (to keep alive while a launch reads them))."""
         order = self._elimination_ordering
         # every variable owns a permanent column range of the sample matrix (assigned when first seen), so a
         # clique's column indices never change and are cached on its model together with the device pointers
@@ -782,12 +795,61 @@ class NFiSAM(FactorGraphSolver):
         table["obs_off"] = np.cumsum(n_obs) - n_obs
         table["sep_off"] = np.cumsum(n_col) - n_col
         table["front_off"] = table["sep_off"] + n_sep
-        K, H, B, L = cfg
-        S = _nh.posterior_walk_raw(table, np.concatenate(cols), np.concatenate(obs), total_dim, num_samples, max_D,
-                                   K, H, B, L, device)
-        done = torch.cuda.Event()
-        done.record(torch.cuda.current_stream())
-        return dict(S=S, pcol=pcol, order=list(order), start=start, stream=torch.cuda.current_stream(), keep=models, done=done)
+        return dict(cliques=cliques, table=table, cols=np.concatenate(cols), obs=np.concatenate(obs), cfg=cfg, device=device,
+                    max_D=max_D, pcol=pcol, total_dim=total_dim, models=models)
+
+    def posterior_log_pdf(self, samples, per_clique: bool = False):
+        """log q(X) of the tree's posterior at n points, not in the reference: the sum over the cliques of the physical Bayes
+        tree of log q_c(frontal | separator, true observations), each the clique's trained flow evaluated forward on the
+        device (all cliques in one launch plus a per-point sum: nfisam_nsf_posterior_log_density).
+
+        samples: mapping variable -> [n, dim] values (numpy or torch; the dict or LazyPosterior that `sample_posterior`
+        returns is valid input); it must hold every variable of the current tree, extra keys are ignored.
+        -> np.ndarray[n] float32; with per_clique=True: (total [n], terms [n, n_cliques], cliques in table order).
+
+        The density is in the variables' own units (metres, radians) and periodic in every angle.  On the circle it is
+        normalised up to the mass each clique's flow puts beyond +-pi / std of its heading columns -- negligible for the
+        heading spreads SLAM produces (std << pi).  Stream-ordered on the current stream behind the fits and the walk.
+        Raises RuntimeError when there is no tree (or no trained model) yet, ValueError for a missing variable or ragged n,
+        before anything is launched."""
+        tree = self._physical_bayes_tree
+        if tree is None or tree.root is None:
+            raise RuntimeError("posterior_log_pdf: no Bayes tree yet (run an incremental update first)")
+        for clique in tree.clique_ordering():
+            if clique not in self._clique_density_model:
+                raise RuntimeError("posterior_log_pdf: clique %s has no trained model yet" % clique)
+        n = None
+        values = {}
+        for v in self._elimination_ordering:
+            if v not in samples:
+                raise ValueError("posterior_log_pdf: samples lack variable %s" % v.name)
+            a = samples[v]
+            if a.ndim == 1 and v.dim == 1:
+                a = a.reshape(-1, 1)
+            if a.ndim != 2 or a.shape[1] != v.dim:
+                raise ValueError("posterior_log_pdf: samples of %s must be [n, %d], got %s" % (v.name, v.dim, tuple(a.shape)))
+            if n is None:
+                n = int(a.shape[0])
+            elif int(a.shape[0]) != n:
+                raise ValueError("posterior_log_pdf: ragged samples: %s has %d rows, the others %d" % (v.name, a.shape[0], n))
+            values[v] = a
+        t = self._posterior_table()
+        K, H, B, L = t["cfg"]
+        pcol, device = t["pcol"], t["device"]
+        if values and all(torch.is_tensor(a) for a in values.values()):
+            S = torch.zeros(n, t["total_dim"], dtype=torch.float32, device=device)
+            for v, a in values.items():
+                S[:, pcol[v]:pcol[v] + v.dim] = a.to(device=device, dtype=torch.float32)
+        else:
+            S = np.zeros((n or 0, t["total_dim"]), dtype=np.float32)
+            for v, a in values.items():
+                S[:, pcol[v]:pcol[v] + v.dim] = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        out = _nh.posterior_log_density(t["table"], t["cols"], t["obs"], S, t["max_D"], K, H, B, L, device,
+                                        per_clique=per_clique)
+        if per_clique:
+            log_q, per, _ = out
+            return log_q.cpu().numpy(), per.t().cpu().numpy(), list(t["cliques"])
+        return out.cpu().numpy()
 
     def posterior_collect(self, handle, timer: List = None, copy_stream=None):
         """Second half: wait for the walk, one D2H copy, per-variable views of the sample matrix (in the elimination ordering

@@ -1,0 +1,305 @@
+"""The posterior's log-density on the GPU (nfisam_nsf_posterior_log_density, nfisam_hip.posterior_log_density,
+NFiSAM.posterior_log_pdf): parity with the float64 oracle on synthetic trees, the round trip with the tree walk, the
+normalisation of solved posteriors, an exact Gaussian posterior, and the pipeline's invariants.
+
+Reference values come from the oracle only (oracle/nsf_torch.py): a clique's term is log q(first D columns) - log q(first
+n_obs + n_sep columns) - sum of the frontal columns' log std, which is exact for an autoregressive flow with a factorised
+prior (the first D' dims of a D-dim flow ARE its D'-dim marginal flow)."""
+import json
+import math
+import os
+import random
+
+import numpy as np
+import pytest
+import torch
+
+import nfisam_hip as nh
+from oracle import nsf_torch as O
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+B = 5.0
+
+
+def dev(a):
+    return torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32).to(DEV)
+
+
+def _tree(L, K, H, rng):
+    """Three cliques over a 9-column sample matrix (columns permuted against the walk order): root {c4..c8}; a child with
+    two observation columns and separator c7 c8; a leaf with one observation column and five separator columns; one model
+    is wider than the columns it uses (ragged).  Columns 2 and 6 are angles in every model that sees them."""
+    total = 9
+    angle = np.zeros(total, dtype=bool)
+    angle[[2, 6]] = True
+    specs = [dict(n_obs=0, sep=[], front=[4, 5, 6, 7, 8]),
+             dict(n_obs=2, sep=[7, 8], front=[1, 2, 3]),
+             dict(n_obs=1, sep=[1, 2, 3, 4, 5], front=[0])]
+    entries, host = [], []
+    for j, sp in enumerate(specs):
+        used = sp["sep"] + sp["front"]
+        D = sp["n_obs"] + len(used) + (1 if j == 1 else 0)
+        gen = torch.Generator().manual_seed(int(rng.randint(1000)))
+        blob = torch.cat([O.init_blob(D, K, H, gen) for _ in range(L)])
+        blob = (blob + 0.25 * torch.randn(blob.shape, generator=gen)).numpy().astype(np.float32)
+        mean = (rng.randn(D) * 2).astype(np.float32)
+        std = (0.5 + rng.rand(D)).astype(np.float32)
+        circ = np.zeros(D, dtype=bool)
+        for k, col in enumerate(used):
+            circ[sp["n_obs"] + k] = angle[col]
+        std[circ] = (0.25 + 0.25 * rng.rand(int(circ.sum()))).astype(np.float32)      # headings: std << pi
+        mean[circ] = rng.uniform(-np.pi, np.pi, int(circ.sum())).astype(np.float32)
+        obs = rng.randn(sp["n_obs"])
+        entries.append(dict(kparams=nh.pack(dev(blob), D, K, H, L), mean=dev(mean), std=dev(std),
+                            circular=torch.from_numpy(circ.astype(np.uint8)).to(DEV), D_model=D, obs=obs,
+                            sep_cols=sp["sep"], front_cols=sp["front"]))
+        host.append((blob, mean, std, circ, D, obs))
+    return total, angle, specs, entries, host
+
+
+def _table(entries):
+    """The clique table of `entries` as posterior_walk_raw / posterior_log_density take it."""
+    rows, cols, obs, max_D = [], [], [], 1
+    for e in entries:
+        r = np.zeros(1, dtype=nh.POST_DTYPE)
+        r["kparams"], r["mean"], r["std"], r["circular"] = (e["kparams"].data_ptr(), e["mean"].data_ptr(), e["std"].data_ptr(),
+                                                           e["circular"].data_ptr())
+        r["D_model"], r["n_obs"], r["n_sep"], r["n_frontal"] = e["D_model"], len(e["obs"]), len(e["sep_cols"]), len(e["front_cols"])
+        r["obs_off"], r["sep_off"], r["front_off"] = len(obs), len(cols), len(cols) + len(e["sep_cols"])
+        obs.extend(float(v) for v in e["obs"])
+        cols.extend(int(v) for v in e["sep_cols"] + e["front_cols"])
+        rows.append(r)
+        max_D = max(max_D, e["D_model"])
+    return np.concatenate(rows), np.array(cols, dtype=np.int32), np.array(obs, dtype=np.float32), max_D
+
+
+def _oracle_terms(specs, host, X, K, H, L):
+    """float64 per-clique terms [n_cliques, n] at the points X [n, total]."""
+    terms = []
+    for sp, (blob, mean, std, circ, D, obs) in zip(specs, host):
+        Ds, F = sp["n_obs"] + len(sp["sep"]), len(sp["front"])
+        u = np.concatenate([np.tile(obs, (X.shape[0], 1)), X[:, sp["sep"] + sp["front"]]], 1).astype(np.float32)
+        un = torch.from_numpy(O.normalize_samples(u, mean, std, circ, 0).astype(np.float64))
+        P = O.param_count(D, K, H)
+
+        def lp(d):
+            if d == 0:
+                return torch.zeros(un.shape[0], dtype=torch.float64)
+            Pd = O.param_count(d, K, H)
+            b = torch.from_numpy(np.concatenate([blob[l * P:l * P + Pd] for l in range(L)]).astype(np.float64))
+            return O.log_prob(un[:, :d], b, K, H, B, L)
+        t = lp(Ds + F) - lp(Ds) - np.log(std[Ds:Ds + F].astype(np.float64)).sum()
+        terms.append(t.numpy())
+    return np.stack(terms)
+
+
+def _bars(got, ref):
+    err = np.abs(got.astype(np.float64) - ref) / (1.0 + np.abs(ref))
+    assert np.quantile(err, 0.98) < 2e-4 and err.max() < 5e-3, (np.quantile(err, 0.98), err.max())
+
+
+LH = [(1, 4), (1, 8), (1, 16), (2, 8), (2, 16)]
+
+
+@pytest.mark.parametrize("K", [5, 9, 12])
+@pytest.mark.parametrize("L,H", LH)
+def test_log_density_matches_the_float64_oracle(L, H, K):
+    """Total and per-clique terms against the oracle at walk samples, at points beyond the spline's tail bound (identity
+    tails) and at the walk samples with every angle shifted by +-2 pi (periodic: the same values within 1e-4)."""
+    rng = np.random.RandomState(100 * L + H + K)
+    total, angle, specs, entries, host = _tree(L, K, H, rng)
+    table, cols, obs, max_D = _table(entries)
+    n = 300
+    Zt = torch.from_numpy(rng.randn(total, n).astype(np.float32)).to(DEV)
+    S = nh.posterior_walk_raw(table, cols, obs, total, n, max_D, K, H, B, L, DEV, Zt=Zt)
+    X = S.cpu().numpy()
+    far = X[:64].copy()                                   # beyond the tail bound: several columns at > B std from the mean
+    for r in range(far.shape[0]):
+        for col in rng.choice(total, 3, replace=False):
+            if not angle[col]:
+                far[r, col] += (1 if r % 2 else -1) * (8.0 + 4.0 * rng.rand())
+    pts = np.concatenate([X, far]).astype(np.float32)
+    lq, per, _ = nh.posterior_log_density(table, cols, obs, dev(pts), max_D, K, H, B, L, DEV, per_clique=True)
+    ref = _oracle_terms(specs, host, pts.astype(np.float64), K, H, L)
+    _bars(per.cpu().numpy(), ref)
+    _bars(lq.cpu().numpy(), ref.sum(0))
+    assert torch.equal(lq, nh.posterior_log_density(table, cols, obs, dev(pts), max_D, K, H, B, L, DEV))   # same bits
+    for shift in (2 * np.pi, -2 * np.pi):
+        sh = pts.copy()
+        sh[:, angle] += np.float32(shift)
+        lq2 = nh.posterior_log_density(table, cols, obs, dev(sh), max_D, K, H, B, L, DEV).cpu().numpy()
+        d = np.abs(lq2 - lq.cpu().numpy()) / (1.0 + np.abs(lq.cpu().numpy()))
+        # the shifted angle |x| + 2 pi is itself rounded to fp32 (ulp ~1e-6 rad): with two layers of random, steep splines a few
+        # points amplify that past 1e-4 (measured worst 4.5e-4), so the bulk is held to 1e-4 and every point to the parity bars
+        # against the float64 oracle at the UNSHIFTED point
+        assert np.quantile(d, 0.98) < 1e-4, np.quantile(d, 0.98)
+        _bars(lq2, ref.sum(0))
+
+
+@pytest.mark.parametrize("L,H", LH)
+def test_latent_round_trip_with_the_walk(L, H):
+    """Walk with given draws Zt, evaluate its output with latent=True: the latent of every frontal column is Zt (the bars of
+    the walk's own parity test)."""
+    K = 9
+    rng = np.random.RandomState(7 + L + H)
+    total, angle, specs, entries, host = _tree(L, K, H, rng)
+    table, cols, obs, max_D = _table(entries)
+    n = 300
+    Zt_np = rng.randn(total, n).astype(np.float32)
+    S = nh.posterior_walk_raw(table, cols, obs, total, n, max_D, K, H, B, L, DEV, Zt=dev(Zt_np))
+    lq, per, lat = nh.posterior_log_density(table, cols, obs, S, max_D, K, H, B, L, DEV, latent=True)
+    assert per is None and lat.shape == (total, n)
+    err = np.abs(lat.cpu().numpy() - Zt_np)
+    assert np.quantile(err, 0.99) < 2e-4 * L and err.max() < 5e-3 * L, (np.quantile(err, 0.99), err.max())
+    assert np.all(np.isfinite(lq.cpu().numpy()))
+
+
+def _solve(steps, **kw):
+    from slam.NFiSAM import NFiSAM, NFiSAMArgs
+    args = dict(num_knots=9, hidden_dim=8, flow_iterations=2000, local_sample_num=2000, learning_rate=0.015,
+                average_window=50, loss_delta_tol=1e-2, posterior_sample_num=2000, cuda_training=True)
+    args.update(kw)
+    s = NFiSAM(NFiSAMArgs(**args))
+    for vs, fs in steps:
+        for v in vs: s.add_node(v)
+        for f in fs: s.add_factor(f)
+        s.update_physical_and_working_graphs()
+        s.incremental_inference()
+    return s
+
+
+def test_se2_pose_posterior_integrates_to_one():
+    """One SE(2) pose with a Gaussian prior (heading sigma 0.25): exp(log q) summed over a 64^3 grid covering +-6 sigma in x
+    and y and [-pi, pi) in heading (one call) is 1 within 0.02."""
+    from factors.Factors import UnarySE2ApproximateGaussianPriorFactor
+    from slam.Variables import SE2Variable
+    random.seed(0); np.random.seed(0); torch.manual_seed(0)
+    X0 = SE2Variable("X0")
+    s = _solve([([X0], [UnarySE2ApproximateGaussianPriorFactor(X0, np.array([2.0, -1.0, 3.0]),
+                                                               np.diag([0.5, 0.4, 0.25]) ** 2)])])
+    smp = np.asarray(s.sample_posterior()[X0], dtype=np.float64)
+    m, sd = smp[:, :2].mean(0), smp[:, :2].std(0)
+    g = 64
+    xs = [m[k] - 6 * sd[k] + (np.arange(g) + 0.5) * 12 * sd[k] / g for k in range(2)]
+    th = -np.pi + (np.arange(g) + 0.5) * 2 * np.pi / g
+    grid = np.stack(np.meshgrid(xs[0], xs[1], th, indexing="ij"), -1).reshape(-1, 3).astype(np.float32)
+    lq = s.posterior_log_pdf({X0: grid})
+    assert lq.shape == (g ** 3,) and lq.dtype == np.float32 and np.all(np.isfinite(lq))
+    mass = np.exp(lq.astype(np.float64)).sum() * (12 * sd[0] / g) * (12 * sd[1] / g) * (2 * np.pi / g)
+    assert abs(mass - 1.0) < 0.02, mass
+
+
+def test_two_clique_r2_posterior_integrates_to_one():
+    """Two R2 variables with priors of their own (two cliques, 4 dimensions): importance sampling with a Gaussian proposal
+    twice as wide as the posterior samples, 2^20 points, estimates the mass as 1 within 0.03."""
+    from factors.Factors import UnaryR2GaussianPriorFactor
+    from slam.Variables import R2Variable
+    random.seed(1); np.random.seed(1); torch.manual_seed(1)
+    A, Bv = R2Variable("A"), R2Variable("B")
+    s = _solve([([A, Bv], [UnaryR2GaussianPriorFactor(A, np.array([1.0, 2.0]), np.array([[1.0, 0.3], [0.3, 0.5]])),
+                           UnaryR2GaussianPriorFactor(Bv, np.array([-3.0, 0.5]), np.diag([2.0, 0.7]) ** 2)])])
+    assert len(s.physical_bayes_tree.clique_ordering()) == 2
+    smp = s.sample_posterior()
+    X = np.hstack([np.asarray(smp[A], dtype=np.float64), np.asarray(smp[Bv], dtype=np.float64)])
+    mu, cov = X.mean(0), 4.0 * np.cov(X.T)                # twice the spread
+    Lc = np.linalg.cholesky(cov)
+    rng = np.random.RandomState(2)
+    N = 1 << 20
+    P = mu + rng.randn(N, 4) @ Lc.T
+    logp = (-0.5 * (np.linalg.solve(Lc, (P - mu).T) ** 2).sum(0) - 0.5 * 4 * math.log(2 * math.pi)
+            - np.log(np.diag(Lc)).sum())
+    lq = s.posterior_log_pdf({A: P[:, :2].astype(np.float32), Bv: P[:, 2:].astype(np.float32)})
+    mass = np.exp(lq.astype(np.float64) - logp).mean()
+    assert abs(mass - 1.0) < 0.03, mass
+
+
+EXACT_BAR = 0.4
+
+
+def test_linear_gaussian_chain_matches_the_exact_posterior():
+    """A prior and three R2 odometry factors (sigma 5), solved incrementally; the exact posterior from the information form.
+    On 5000 posterior samples of each of seeds 0, 1, 2: |mean(log q - log p_exact)| <= EXACT_BAR and the Pearson
+    correlation of log q and log p_exact >= 0.95.
+    Measured (MI355X): mean(log q - log p_exact) = 0.125 / 0.119 / 0.126 (the KL of the trained flows to the exact posterior,
+    >= 0 as it must be), correlation 0.964 / 0.970 / 0.971, smallest |log std| of a frontal column 1.58 / 1.57 / 1.60.
+    Bar basis: about three times the worst seed's mean (0.126 -> 0.4), and below the smallest |log std| (1.57): dropping
+    the normalisation's Jacobian 1 / std of any one frontal column moves the mean by more than the bar."""
+    from factors.Factors import R2RelativeGaussianLikelihoodFactor, UnaryR2GaussianPriorFactor
+    from slam.Variables import R2Variable
+    out = []
+    for seed in (0, 1, 2):
+        random.seed(seed); np.random.seed(seed); torch.manual_seed(seed)
+        V = [R2Variable("X%d" % i) for i in range(4)]
+        cov = np.eye(2) * 25.0
+        odo = [np.array([6.0, 2.0]), np.array([5.0, -4.0]), np.array([-2.0, 7.0])]
+        steps = [([V[0]], [UnaryR2GaussianPriorFactor(V[0], np.array([1.0, -2.0]), cov)])]
+        steps += [([V[i + 1]], [R2RelativeGaussianLikelihoodFactor(V[i], V[i + 1], odo[i], cov)]) for i in range(3)]
+        s = _solve(steps, posterior_sample_num=5000)
+        # information form: x = (X0, X1, X2, X3), prior on X0, X_{i+1} - X_i = odo_i
+        Hm = np.zeros((8, 8)); bv = np.zeros(8)
+        Wi = np.linalg.inv(cov)
+        Hm[0:2, 0:2] += Wi; bv[0:2] += Wi @ np.array([1.0, -2.0])
+        for i in range(3):
+            a, b = slice(2 * i, 2 * i + 2), slice(2 * i + 2, 2 * i + 4)
+            Hm[a, a] += Wi; Hm[b, b] += Wi; Hm[a, b] -= Wi; Hm[b, a] -= Wi
+            bv[b] += Wi @ odo[i]; bv[a] -= Wi @ odo[i]
+        mean = np.linalg.solve(Hm, bv)
+        smp = s.sample_posterior()
+        X = np.hstack([np.asarray(smp[v], dtype=np.float64) for v in V])
+        d = X - mean
+        logp = -0.5 * np.einsum("ni,ij,nj->n", d, Hm, d) - 4 * math.log(2 * math.pi) + 0.5 * np.linalg.slogdet(Hm)[1]
+        lq = s.posterior_log_pdf(smp).astype(np.float64)
+        min_log_std = np.inf                              # over the frontal columns of every clique's normalisation
+        for c in s.physical_bayes_tree.clique_ordering():
+            std = torch.as_tensor(s._clique_density_model[c].samples_std).double().cpu().numpy()
+            Ds = len(np.ravel(s._clique_true_obs[c])) + c.separator_dim
+            min_log_std = min(min_log_std, float(np.abs(np.log(std[Ds:Ds + c.frontal_dim])).min()))
+        out.append((float(np.mean(lq - logp)), float(np.corrcoef(lq, logp)[0, 1]), min_log_std))
+    print("mean(log q - log p), corr, min |log std| per seed:", out)
+    for bias, corr, mls in out:
+        assert mls >= 1.0 and EXACT_BAR < mls
+        assert abs(bias) <= EXACT_BAR and corr >= 0.95, out
+
+
+def test_pipeline_invariants_and_async_lazy_equality(tmp_path):
+    """The small range problem (BASELINE config[0]) through all six updates: after each, log q of the update's posterior
+    samples is finite, equals the sum of its per-clique terms and is the same bits on a repeated call; a solver with
+    async_fits=True, lazy_posterior=True and the same seeds gives the same bits."""
+    from slam.NFiSAM import NFiSAM, NFiSAMArgs
+    from slam.RunBatch import graph_file_parser, group_nodes_factors_incrementally
+    fx = np.load(os.path.join(GOLDEN, "pipeline_small_range.npz"), allow_pickle=False)
+    kwargs = json.loads(str(fx["arguments"]))
+    kwargs["cuda_training"] = True
+    path = tmp_path / "factor_graph.fg"
+    path.write_text(str(np.load(os.path.join(GOLDEN, "small_range_case1.npz"))["factor_graph_fg"]))
+
+    def solve(**extra):
+        random.seed(5); np.random.seed(5); torch.manual_seed(5)
+        nodes, truth, factors = graph_file_parser(str(path), "fg", prior_cov_scale=0.1)
+        steps = group_nodes_factors_incrementally(nodes, factors, incremental_step=int(fx["incremental_step"]))
+        assert len(steps) == 6
+        solver = NFiSAM(NFiSAMArgs(**extra, **kwargs))
+        vals = []
+        for vs, fs in steps:
+            for v in vs: solver.add_node(v)
+            for f in fs: solver.add_factor(f)
+            solver.update_physical_and_working_graphs()
+            smp = solver.incremental_inference()
+            lq = solver.posterior_log_pdf(smp)
+            tot, terms, cliques = solver.posterior_log_pdf(smp, per_clique=True)
+            n = len(smp[solver.elimination_ordering[0]])
+            assert lq.shape == (n,) and lq.dtype == np.float32 and np.all(np.isfinite(lq))
+            assert terms.shape == (n, len(cliques)) == (n, len(solver.physical_bayes_tree.clique_ordering()))
+            assert np.array_equal(tot, lq) and np.array_equal(solver.posterior_log_pdf(smp), lq)
+            ssum = terms.astype(np.float64).sum(1)
+            assert np.all(np.abs(lq - ssum) <= 1e-5 * np.maximum(1.0, np.abs(terms).sum(1))), np.abs(lq - ssum).max()
+            vals.append(lq)
+        return vals
+
+    ref = solve()
+    got = solve(async_fits=True, lazy_posterior=True)
+    for a, b in zip(got, ref):
+        np.testing.assert_array_equal(a, b)
