@@ -217,6 +217,49 @@ typedef struct nfisam_sim_op {
 int nfisam_simulate_clique(const nfisam_sim_op* ops, int n_ops, int n, int D_out, int D_total, uint64_t seed,
                            float* x_out, nfisam_stream_t stream);
 
+/* ---- the factor graph's joint log-density ------------------------------------------------------------------
+ * log p(X, Z) = sum over the factors f of log p_f(x_f) at n points, the reference's JointFactor.log_pdf
+ * (src/sampler/sampler_utils.py:85-98) over its factors' `log_pdf` (src/factors/Factors.py).  One record per factor; a, b,
+ * cand[] are FIRST ROWS of the variables in St (an SE(2) variable takes 3 consecutive rows x y theta, an R2 variable 2; range
+ * codes read the first two rows of either kind).  p[] by code -- Gaussians carry the upper triangle of the precision matrix
+ * (row-major: 6 entries for 3x3, 3 for 2x2) and their log normaliser -(d log 2 pi + log det Sigma) / 2:              */
+#define NFISAM_FAC_PRIOR_SE2      1 /* N(Log(p[0:3]^-1 * a); 0, Sigma) + log|det dLog|; p[3:9] precision, p[9] log norm
+                                       (UnarySE2ApproximateGaussianPriorFactor, Factors.py:823-827; Log and its Jacobian
+                                       det = th^2 / (4 sin^2(th/2)), 1 for |th| < 1e-5: geometry/TwoDimension.py:405-441)  */
+#define NFISAM_FAC_REL_SE2        2 /* the same of p[0:3]^-1 * (a^-1 * b)  (SE2RelativeGaussianLikelihoodFactor, :1443-1448)   */
+#define NFISAM_FAC_RANGE          3 /* N(|a_xy - b_xy| - p[0]; 0, 1 / p[1]), p[2] log norm  (SE2R2RangeGaussianLikelihoodFactor
+                                       :2724-2730, R2RangeGaussianLikelihoodFactor :2195-2201)                          */
+#define NFISAM_FAC_RANGE_MIX      4 /* log sum_{j<k} exp(range term of (a, cand[j]) with p[3j] measurement, p[3j+1] 1 / sigma^2,
+                                       p[3j+2] log norm + log weight), by log-sum-exp  (BinaryFactorMixture, :3126-3133:
+                                       AmbiguousDataAssociationFactor; BinaryFactorWithNullHypo = k 2, one landmark twice
+                                       with two sigmas)                                                                 */
+#define NFISAM_FAC_PRIOR_R2       5 /* N(a - p[0:2]; 0, Sigma); p[2:5] precision, p[5] log norm  (UnaryR2GaussianPriorFactor, :373)  */
+#define NFISAM_FAC_PRIOR_R2_RANGE 6 /* N(|a - p[0:2]| - p[2]; 0, 1 / p[3]), p[4] log norm  (UnaryR2RangeGaussianPriorFactor, :2226:
+                                       the range term :2195-2201 with one end at the centre)                            */
+#define NFISAM_FAC_REL_R2         7 /* N(b - a - p[0:2]; 0, Sigma); p[2:5] precision, p[5] log norm
+                                       (R2RelativeGaussianLikelihoodFactor, :1070-1074)                                 */
+typedef struct nfisam_factor_term {
+    int32_t code;
+    int32_t a, b;          /* first rows of the factor's variables (b unused by unary factors and mixtures) */
+    int32_t k;             /* mixture components, 1..4 (RANGE_MIX only) */
+    int32_t cand[4];       /* first rows of the candidate landmarks */
+    double p[16];
+} nfisam_factor_term;
+
+/* log_p[p] = sum_f term_f(point p), float64, for the n points of St[total_dim][n] -- the COLUMN-major float32 sample matrix
+ * the tree walk writes and nfisam_nsf_posterior_log_density reads.  Float32 points in, float64 arithmetic, float64 out: the
+ * value of the float64 formula at the float32 point (heading wraps are theta_to_pipi, utils/Functions.py:20-21).
+ *   terms[n_terms]: DEVICE array;  per_factor[n_terms][n] (nullable): every term -- without it the library takes a scratch
+ *   buffer of that size from the stream-ordered allocator for the call.
+ * Two launches: one wave per (64-point tile, run of 8 factors) writes the terms, then one thread per point adds them
+ * strictly in table order: log_p[p] == ((term_0 + term_1) + term_2) + ... in float64, independent of n and of the tile.  No
+ * float atomics: two calls give the same bits.
+ * NFISAM_ERR_ARG: NULL terms / St / log_p, a negative count, total_dim < 1, more than 524280 factors.  The library does not
+ * read the device table on the host: a record with an unknown code, k outside 1..4 or a row outside [0, total_dim) yields NaN
+ * for its term (nothing is read out of bounds); the Python binding refuses such tables before upload.               */
+int nfisam_factor_graph_log_density(const nfisam_factor_term* terms, int n_terms, const float* St, int total_dim, int n,
+                                    double* log_p, double* per_factor, nfisam_stream_t stream);
+
 /* ---- training -------------------------------------------------------------------------- */
 /* Vector-Jacobian product of the L-layer flow (what torch autograd computes for
  * `loss.backward()` in slam/NFiSAM.py:474): kgrad[L*kparam_count] += d<gz,z>/dtheta + d<gl,logdet>/dtheta,

@@ -14,14 +14,28 @@ dispatch (`PriorFactor`, `BinaryFactor`, ...), `.fg` text (de)serialisation, and
 The reference draws noise with TransportMaps' `GaussianDistribution.rvs` and then loops over
 samples building `SE2Pose` objects; here the noise comes from numpy's global RNG (seeded by the
 example scripts exactly like the reference's) and the pose algebra is vectorised
-(geometry.TwoDimension).  Density evaluation (`log_pdf`, gradients) of these factors is only used
-by the nested-sampling baselines (out of scope) and is not provided.
+(geometry.TwoDimension).
+
+Density evaluation: every class has `log_pdf(x)` / `pdf(x)` (x: [n, sum of the variables' dims], columns in
+`factor.vars` order, float64 throughout), vectorised over n with no `SE2Pose` objects:
+    SE(2) prior / relative pose   N(Log(dT); 0, Sigma) + log|det dLog|, det = th^2 / (4 sin^2(th/2)), 1 for |th| < 1e-5
+                                  (reference :823-827, :1443-1448; geometry/TwoDimension.py:405-441)
+    range factors                 N(|a_xy - b_xy| - d; 0, sigma^2)              (reference :2724-2730, :2195-2201)
+    mixtures                      log sum_k w_k p_k                            (reference :3126-3133)
+    R2 Gaussian prior / relative  the multivariate normal of x - mu / of var2 - var1 - observation (reference :373, :1070-1074)
+    R2 range prior                N(|x - center| - mu; 0, sigma^2): the density of what `sample` draws.  The reference's only
+                                  body for it (:2301-2303, `evaluate_loglike`) subtracts mu inside the norm and is no range
+                                  density; the range likelihood with one end pinned at the centre is what is restated.
+One deliberate difference: the reference's mixture takes `np.log` of a sum of `exp`s, which is -inf far from every
+component; here mixtures use log-sum-exp and stay finite (equal wherever the reference is finite).  The log map uses the
+half-angle form (th/2) cot(th/2), which does not cancel for small th.  `density_record()` returns the factor's row of the
+device table of `nfisam_factor_graph_log_density` (include/nfisam_hip.h); gradients are not provided.
 """
 from typing import Iterable, List, Union
 
 import numpy as np
 
-from geometry.TwoDimension import SE2Pose, se2_compose, se2_exp, se2_inverse
+from geometry.TwoDimension import SE2Pose, se2_compose, se2_exp, se2_inverse, wrap_pi
 from slam.Variables import R1Variable, R2Variable, SE2Variable, Variable, VariableType
 
 
@@ -111,6 +125,46 @@ def _gaussian_noise(cov_chol: np.ndarray, n: int) -> np.ndarray:
     return np.random.standard_normal((n, cov_chol.shape[0])) @ cov_chol.T
 
 
+# ---- densities (float64, vectorised over the rows of x) -------------------------------------------------
+_LOG_2PI = float(np.log(2.0 * np.pi))
+
+
+def _gaussian_log_norm(covariance: np.ndarray) -> float:
+    covariance = np.atleast_2d(np.asarray(covariance, dtype=np.float64))
+    return float(-0.5 * (covariance.shape[0] * _LOG_2PI + np.linalg.slogdet(covariance)[1]))
+
+
+def _quad_form(d: np.ndarray, precision: np.ndarray) -> np.ndarray:
+    return np.einsum("ni,ij,nj->n", d, precision, d)
+
+
+def _sym_upper(precision: np.ndarray) -> List[float]:
+    """Upper triangle (row-major) of the symmetrised precision: the device adds each off-diagonal entry twice."""
+    ps = 0.5 * (precision + precision.T)
+    return [float(ps[r, c]) for r in range(ps.shape[0]) for c in range(r, ps.shape[0])]
+
+
+def _se2_tangent_log_pdf(tx, ty, w, precision, log_norm) -> np.ndarray:
+    """log N(Log(dT); 0, Sigma) + log|det dLog/d(x, y, theta)| for dT = (tx, ty, w), w in [-pi, pi)
+    (reference geometry/TwoDimension.py:405-418 log_map, :437-441 det_grad_x_logmap)."""
+    small = np.abs(w) < 1e-10
+    half = 0.5 * np.where(small, 1.0, w)
+    a = np.where(small, 1.0, half * np.cos(half) / np.sin(half))
+    b = np.where(small, 0.0, half)
+    v = np.stack([a * tx + b * ty, -b * tx + a * ty, w], axis=1)
+    flat = np.abs(w) < 1e-5
+    h = 0.5 * np.where(flat, 1.0, w)
+    log_det = np.where(flat, 0.0, 2.0 * np.log(np.abs(h / np.sin(h))))
+    return log_norm - 0.5 * _quad_form(v, precision) + log_det
+
+
+def _as_points(x, width: int) -> np.ndarray:
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] != width:
+        raise ValueError("x must be [n, %d], got %s" % (width, tuple(x.shape)))
+    return x
+
+
 def _mat3(tok, start):
     return np.array([[float(tok[start + 3 * r + c]) for c in range(3)] for r in range(3)])
 
@@ -128,6 +182,8 @@ class UnarySE2ApproximateGaussianPriorFactor(ExplicitPriorFactor, UnaryFactor):
         self._prior_pose = prior_pose
         self._covariance = np.array(covariance, dtype=np.float64)
         self._chol = np.linalg.cholesky(self._covariance)
+        self._precision = np.linalg.inv(self._covariance)
+        self._log_norm = _gaussian_log_norm(self._covariance)
         self._correlated_R_t = correlated_R_t
 
     @property
@@ -159,6 +215,23 @@ class UnarySE2ApproximateGaussianPriorFactor(ExplicitPriorFactor, UnaryFactor):
         out[:, :2] = self._prior_pose.array[:2] + noise[:, :2]
         out[:, 2] = (self._prior_pose.theta + theta + np.pi) % (2 * np.pi) - np.pi
         return out
+
+    def log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """Density in (x, y, theta) of the pose: the tangent Gaussian of prior^-1 * T times the Jacobian of Log
+        (reference :823-827)."""
+        x = _as_points(x, 3)
+        px, py, pth = self._prior_pose.array
+        c, s = np.cos(pth), np.sin(pth)
+        dx, dy = x[:, 0] - px, x[:, 1] - py
+        w = wrap_pi(wrap_pi(-pth) + wrap_pi(x[:, 2]))
+        return _se2_tangent_log_pdf(c * dx + s * dy, -s * dx + c * dy, w, self._precision, self._log_norm)
+
+    def pdf(self, x: np.ndarray) -> np.ndarray:
+        return np.exp(self.log_pdf(x))
+
+    def density_record(self) -> dict:
+        return dict(code="PRIOR_SE2", a=self.var, b=None, cand=[],
+                    p=[float(t) for t in self._prior_pose.array] + _sym_upper(self._precision) + [self._log_norm])
 
     @classmethod
     def construct_from_text(cls, line: str, variables):
@@ -199,6 +272,8 @@ class SE2RelativeGaussianLikelihoodFactor(LikelihoodFactor, BinaryFactor, OdomFa
         self._observation = observation
         self._covariance = np.array(covariance, dtype=np.float64)
         self._chol = np.linalg.cholesky(self._covariance)
+        self._precision = np.linalg.inv(self._covariance)
+        self._log_norm = _gaussian_log_norm(self._covariance)
         self._correlated_Rt = correlated_R_t
         self._observation_var = SE2Variable(name="O" + str(var1.name) + str(var2.name),
                                             variable_type=VariableType.Measurement)
@@ -245,6 +320,25 @@ class SE2RelativeGaussianLikelihoodFactor(LikelihoodFactor, BinaryFactor, OdomFa
         if var1.shape != var2.shape or var1.shape[1] != 3:
             raise ValueError("Dimensionality of variable 1 or variable 2 is wrong")
         return self._noisy_relative(se2_compose(se2_inverse(var1), var2), var1.shape[0])
+
+    def log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """Density of x = [T_i | T_j]: the tangent Gaussian of observation^-1 * (T_i^-1 * T_j) times the Jacobian of Log
+        (reference :1443-1448)."""
+        x = _as_points(x, 6)
+        ox, oy, oth = self.observation
+        ci, si = np.cos(x[:, 2]), np.sin(x[:, 2])
+        dx, dy = x[:, 3] - x[:, 0], x[:, 4] - x[:, 1]
+        rx, ry = ci * dx + si * dy - ox, -si * dx + ci * dy - oy
+        co, so = np.cos(oth), np.sin(oth)
+        w = wrap_pi(wrap_pi(-oth) + wrap_pi(wrap_pi(-wrap_pi(x[:, 2])) + wrap_pi(x[:, 5])))
+        return _se2_tangent_log_pdf(co * rx + so * ry, -so * rx + co * ry, w, self._precision, self._log_norm)
+
+    def pdf(self, x: np.ndarray) -> np.ndarray:
+        return np.exp(self.log_pdf(x))
+
+    def density_record(self) -> dict:
+        return dict(code="REL_SE2", a=self.var1, b=self.var2, cand=[],
+                    p=[float(t) for t in self.observation] + _sym_upper(self._precision) + [self._log_norm])
 
     @classmethod
     def construct_from_text(cls, line: str, variables):
@@ -324,6 +418,19 @@ class SE2R2RangeGaussianLikelihoodFactor(LikelihoodFactor, BinaryFactor):
         t2 = x[:, d1:][:, self.var2.t_dim_indices]
         r = np.sqrt(((t2 - t1) ** 2).sum(1))
         return np.exp(-0.5 * ((r - self._observation[0]) / self._sigma) ** 2) / (np.sqrt(2 * np.pi) * self._sigma)
+
+    def log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """log N(|t_1 - t_2| - observation; 0, sigma^2) at x = [var1 | var2] (reference :2724-2730, :2195-2201)."""
+        x = _as_points(x, self.var1.dim + self.var2.dim)
+        d1 = self.var1.dim
+        t1 = x[:, :d1][:, self.var1.t_dim_indices]
+        t2 = x[:, d1:][:, self.var2.t_dim_indices]
+        delta = np.sqrt(((t1 - t2) ** 2).sum(1)) - self._observation[0]
+        return _gaussian_log_norm(self._sigma ** 2) - 0.5 * delta * delta * (1.0 / self._sigma ** 2)
+
+    def density_record(self) -> dict:
+        return dict(code="RANGE", a=self.var1, b=self.var2, cand=[],
+                    p=[float(self._observation[0]), 1.0 / self._sigma ** 2, _gaussian_log_norm(self._sigma ** 2)])
 
     def sample(self, var1=None, var2=None) -> np.ndarray:
         if var1 is None:
@@ -405,6 +512,28 @@ class BinaryFactorMixture(LikelihoodFactor):
 
     def pdf(self, x: np.ndarray) -> np.ndarray:
         return sum(c.pdf(x[:, self.comp2idx[c]]) * w for c, w in zip(self.components, self.weights))
+
+    def log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """log sum_k w_k p_k(x) by log-sum-exp: finite far from every component, where the reference's log of a sum of
+        exps (:3126-3133) is -inf; equal to it wherever that is finite."""
+        x = _as_points(x, self.dim)
+        terms = np.stack([c.log_pdf(x[:, self.comp2idx[c]]) + np.log(w) for c, w in zip(self.components, self.weights)])
+        top = terms.max(0)
+        return top + np.log(np.exp(terms - top).sum(0))
+
+    def density_record(self) -> dict:
+        """A k-way range mixture: candidates may repeat (the null hypothesis: one landmark, two sigmas)."""
+        if len(self.components) > 4:
+            raise NotImplementedError("%s with %d components: the device table holds at most 4"
+                                      % (self.__class__.__name__, len(self.components)))
+        p = []
+        for c, w in zip(self.components, self.weights):
+            if not isinstance(c, SE2R2RangeGaussianLikelihoodFactor) or c.var1 != self.observer_var:
+                raise NotImplementedError("%s over %s components has no device code (range components only)"
+                                          % (self.__class__.__name__, c.__class__.__name__))
+            r = c.density_record()["p"]
+            p += [r[0], r[1], r[2] + float(np.log(w))]
+        return dict(code="RANGE_MIX", a=self.observer_var, b=None, cand=[c.var2 for c in self.components], p=p)
 
     def posterior_weights(self, var2x) -> np.ndarray:
         """Re-weight the association hypotheses with posterior samples (reference :3158-3181)."""
@@ -527,6 +656,19 @@ class UnaryR2GaussianPriorFactor(ExplicitPriorFactor, UnaryFactor):
     def sample(self, num_samples: int, **kwargs) -> np.ndarray:
         return self._mu + _gaussian_noise(self._chol, num_samples)
 
+    def log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """log N(x; mu, covariance) (reference :373: the distribution's own log_pdf)."""
+        d = _as_points(x, 2) - self._mu
+        return _gaussian_log_norm(self._covariance) - 0.5 * _quad_form(d, np.linalg.inv(self._covariance))
+
+    def pdf(self, x: np.ndarray) -> np.ndarray:
+        return np.exp(self.log_pdf(x))
+
+    def density_record(self) -> dict:
+        return dict(code="PRIOR_R2", a=self.var, b=None, cand=[],
+                    p=[float(self._mu[0]), float(self._mu[1])] + _sym_upper(np.linalg.inv(self._covariance)) +
+                      [_gaussian_log_norm(self._covariance)])
+
     @classmethod
     def construct_from_text(cls, line: str, variables):
         tok = line.strip().split()
@@ -577,6 +719,21 @@ class UnaryR2RangeGaussianPriorFactor(ExplicitPriorFactor, UnaryFactor):
         r = self._mu + self._sigma * np.random.standard_normal(num_samples)
         phi = np.random.uniform(-np.pi, np.pi, num_samples)
         return self._center + np.stack([r * np.cos(phi), r * np.sin(phi)], 1)
+
+    def log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """log N(|x - center| - mu; 0, sigma^2): the range likelihood (reference :2195-2201) with one end at the centre,
+        i.e. the density of the radius `sample` draws (see the module docstring on the reference's own body)."""
+        x = _as_points(x, 2)
+        delta = np.sqrt(((x - self._center) ** 2).sum(1)) - self._mu
+        return _gaussian_log_norm(self._sigma ** 2) - 0.5 * delta * delta * (1.0 / self._sigma ** 2)
+
+    def pdf(self, x: np.ndarray) -> np.ndarray:
+        return np.exp(self.log_pdf(x))
+
+    def density_record(self) -> dict:
+        return dict(code="PRIOR_R2_RANGE", a=self.var, b=None, cand=[],
+                    p=[float(self._center[0]), float(self._center[1]), self._mu, 1.0 / self._sigma ** 2,
+                       _gaussian_log_norm(self._sigma ** 2)])
 
     @classmethod
     def construct_from_text(cls, line: str, variables):
@@ -646,6 +803,20 @@ class R2RelativeGaussianLikelihoodFactor(LikelihoodFactor, BinaryFactor, OdomFac
         if var1.shape != var2.shape or var1.shape[1] != 2:
             raise ValueError("Dimensionality of variable 1 or variable 2 is wrong")
         return var2 - var1 + _gaussian_noise(self._chol, var1.shape[0])
+
+    def log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """log N(var2 - var1 - observation; 0, covariance) at x = [var1 | var2] (reference :1070-1074)."""
+        x = _as_points(x, 4)
+        d = x[:, 2:] - x[:, :2] - self._observation
+        return _gaussian_log_norm(self._covariance) - 0.5 * _quad_form(d, np.linalg.inv(self._covariance))
+
+    def pdf(self, x: np.ndarray) -> np.ndarray:
+        return np.exp(self.log_pdf(x))
+
+    def density_record(self) -> dict:
+        return dict(code="REL_R2", a=self.var1, b=self.var2, cand=[],
+                    p=[float(self._observation[0]), float(self._observation[1])] +
+                      _sym_upper(np.linalg.inv(self._covariance)) + [_gaussian_log_norm(self._covariance)])
 
     @classmethod
     def construct_from_text(cls, line: str, variables):

@@ -27,7 +27,7 @@ EXPORTS = [
     "nfisam_nsf_train_plan_begin", "nfisam_nsf_train_plan_enqueue", "nfisam_nsf_train_plan_peek", "nfisam_nsf_train_plan_stream",
     "nfisam_nsf_train_plan_end", "nfisam_nsf_train_plan_xcd_span", "nfisam_nsf_train_plan_kernel_ms", "nfisam_nsf_train_plan_create_validated", "nfisam_nsf_train_plan_feed", "nfisam_nsf_train_plan_enqueued", "nfisam_nsf_train_plan_refill",
     "nfisam_normalize_columns", "nfisam_simulate_clique", "nfisam_nsf_train_plan_launch_async",
-    "nfisam_nsf_posterior_log_density",
+    "nfisam_nsf_posterior_log_density", "nfisam_factor_graph_log_density",
 ]
 
 
@@ -63,7 +63,13 @@ class PostClique(C.Structure):
                 ("obs_off", C.c_int32), ("sep_off", C.c_int32), ("front_off", C.c_int32), ("reserved", C.c_int32)]
 
 
+class FactorTerm(C.Structure):
+    _fields_ = [("code", C.c_int32), ("a", C.c_int32), ("b", C.c_int32), ("k", C.c_int32), ("cand", C.c_int32 * 4),
+                ("p", C.c_double * 16)]
+
+
 assert C.sizeof(TrainState) == 32 and C.sizeof(AdamCfg) == 32 and C.sizeof(Clique) == 64 and C.sizeof(PostClique) == 64
+assert C.sizeof(FactorTerm) == 160
 
 _lib = None
 
@@ -739,3 +745,99 @@ def posterior_log_density(table: np.ndarray, cols: np.ndarray, obs: np.ndarray, 
     if per_clique or latent:
         return log_q, (per if per_clique else None), lat
     return log_q
+
+
+# ---- the factor graph's joint log-density (nfisam_factor_graph_log_density) ------------------------------------------------------
+FACTOR_DTYPE = np.dtype([("code", np.int32), ("a", np.int32), ("b", np.int32), ("k", np.int32), ("cand", np.int32, (4,)),
+                         ("p", np.float64, (16,))])
+assert FACTOR_DTYPE.itemsize == C.sizeof(FactorTerm)
+# NFISAM_FAC_* of include/nfisam_hip.h; _FAC_ROWS: code -> (rows of St read at `a`, rows read at `b` or 0)
+FAC_CODES = {"PRIOR_SE2": 1, "REL_SE2": 2, "RANGE": 3, "RANGE_MIX": 4, "PRIOR_R2": 5, "PRIOR_R2_RANGE": 6, "REL_R2": 7}
+_FAC_ROWS = {1: (3, 0), 2: (3, 3), 3: (2, 2), 4: (2, 0), 5: (2, 0), 6: (2, 0), 7: (2, 2)}
+
+
+def pack_factor_terms(factors, row_of) -> np.ndarray:
+    """The device table of `factors` (numpy FACTOR_DTYPE, one record per factor, in order): every factor's
+    `density_record()` with its variables replaced by their first rows `row_of[variable]` of the sample matrix.
+    NotImplementedError names the class of a factor without a device code."""
+    t = np.zeros(len(factors), dtype=FACTOR_DTYPE)
+    for i, f in enumerate(factors):
+        rec = getattr(f, "density_record", None)
+        if rec is None:
+            raise NotImplementedError("factor class %s has no device code for the joint log-density" % f.__class__.__name__)
+        r = rec()
+        cand = [row_of[v] for v in r["cand"]]
+        if len(cand) > 4 or len(r["p"]) > 16:
+            raise NotImplementedError("%s: %d components, the device table holds at most 4" % (f.__class__.__name__, len(cand)))
+        t["code"][i] = FAC_CODES[r["code"]]
+        t["a"][i] = row_of[r["a"]]
+        t["b"][i] = row_of[r["b"]] if r["b"] is not None else 0
+        t["k"][i] = len(cand)
+        t["cand"][i, :len(cand)] = cand
+        t["p"][i, :len(r["p"])] = r["p"]
+    return t
+
+
+def check_factor_terms(terms: np.ndarray, total_dim: int) -> None:
+    """ValueError for a table the kernel must not see: an unknown code, k outside 1..4, a row outside [0, total_dim)."""
+    if not isinstance(terms, np.ndarray) or terms.dtype != FACTOR_DTYPE or terms.ndim != 1:
+        raise ValueError("terms must be a 1-D numpy array of FACTOR_DTYPE")
+    if terms.size == 0:
+        return
+    code = terms["code"]
+    known = np.isin(code, list(_FAC_ROWS))
+    if not np.all(known):
+        raise ValueError("unknown factor code %d" % int(code[~known][0]))
+    mix = code == FAC_CODES["RANGE_MIX"]
+    if np.any((terms["k"][mix] < 1) | (terms["k"][mix] > 4)):
+        raise ValueError("a mixture must have 1..4 components")
+    rows_a = np.array([_FAC_ROWS[int(c)][0] for c in code])
+    rows_b = np.array([_FAC_ROWS[int(c)][1] for c in code])
+    a, b = terms["a"].astype(np.int64), terms["b"].astype(np.int64)
+    bad = (a < 0) | (a + rows_a > total_dim) | ((rows_b > 0) & ((b < 0) | (b + rows_b > total_dim)))
+    used = np.arange(4)[None, :] < terms["k"][:, None]
+    cand = terms["cand"].astype(np.int64)
+    bad |= mix & np.any(used & ((cand < 0) | (cand + 2 > total_dim)), axis=1)
+    if np.any(bad):
+        raise ValueError("factor %d: a variable row is out of range of the %d columns of S" % (int(np.argmax(bad)), total_dim))
+
+
+def factor_graph_log_density(terms: np.ndarray, S, device, per_factor=False, terms_dev=None):
+    """log p(X, Z) = the sum of the factors' log densities at the n rows of S (nfisam_factor_graph_log_density): `terms` the
+    numpy FACTOR_DTYPE table (`pack_factor_terms`), S [n, total_dim] in the walk's column layout (tensor or numpy; float32
+    points, the arithmetic is float64).  Launched on the current stream.  `terms_dev`: an uploaded copy of `terms` to reuse
+    (uint8 device tensor, kept by callers that score every update).
+    -> log_p [n] float64 device tensor; with per_factor: (log_p, per [n_terms, n] float64)."""
+    if not (torch.is_tensor(S) or isinstance(S, np.ndarray)) or S.ndim != 2:
+        raise ValueError("S must be a [n, total_dim] tensor or array")
+    check_factor_terms(terms, int(S.shape[1]))
+    if torch.is_tensor(S):
+        St = S.to(device=device, dtype=torch.float32).t().contiguous()
+    else:
+        St = torch.from_numpy(np.ascontiguousarray(S.T, dtype=np.float32)).to(device)
+    return factor_graph_log_density_t(terms, St, device, per_factor=per_factor, terms_dev=terms_dev, checked=True)
+
+
+def factor_graph_log_density_t(terms: np.ndarray, St, device, per_factor=False, terms_dev=None, checked=False):
+    """`factor_graph_log_density` on the COLUMN-major matrix St [total_dim, n] (contiguous float32 device tensor): what the
+    tree walk wrote, scored in place."""
+    if not torch.is_tensor(St) or St.ndim != 2 or St.dtype != torch.float32 or not St.is_contiguous():
+        raise ValueError("St must be a contiguous float32 [total_dim, n] tensor")
+    total_dim, n = int(St.shape[0]), int(St.shape[1])
+    if not checked:
+        check_factor_terms(terms, total_dim)
+    nt = int(terms.shape[0])
+    log_p = torch.empty(n, dtype=torch.float64, device=device)
+    # the per-factor terms are the first pass's output; they come from torch's allocator even when the caller does not want
+    # them (the C entry would otherwise take a scratch buffer from HIP's own stream-ordered pool)
+    per = torch.empty(nt, n, dtype=torch.float64, device=device)
+    if nt == 0 or n == 0:
+        log_p.zero_()                                       # the empty graph / no points: nothing to launch
+    else:
+        if terms_dev is None:
+            terms_dev, = upload(terms.view(np.uint8).reshape(-1), device=device)
+        _check(lib().nfisam_factor_graph_log_density(C.c_void_p(terms_dev.data_ptr()), nt, _ptr(St), total_dim, n, _ptr(log_p),
+                                                     _ptr(per), _stream()), "nfisam_factor_graph_log_density")
+    if per_factor:
+        return log_p, per
+    return log_p

@@ -729,12 +729,13 @@ class NFiSAM(FactorGraphSolver):
             return LazyPosterior(handle, host, done)
         return self.posterior_collect(self.posterior_launch(), timer)
 
-    def posterior_launch(self):
+    def posterior_launch(self, num_samples: int = None):
         """First half of `sample_posterior`: assemble the clique table and enqueue the walk on the current stream.
         -> handle for `posterior_collect` (several solvers can have their walks in flight on different streams:
-        slam.ReplicaNFiSAM)."""
+        slam.ReplicaNFiSAM).  `num_samples`: rows to draw (default: the arguments' posterior_sample_num)."""
         start = time.time()
-        num_samples = self._args.posterior_sample_num
+        if num_samples is None:
+            num_samples = self._args.posterior_sample_num
         t = self._posterior_table()
         K, H, B, L = t["cfg"]
         S = _nh.posterior_walk_raw(t["table"], t["cols"], t["obs"], t["total_dim"], num_samples, t["max_D"],
@@ -744,20 +745,23 @@ class NFiSAM(FactorGraphSolver):
         return dict(S=S, pcol=t["pcol"], order=list(self._elimination_ordering), start=start,
                     stream=torch.cuda.current_stream(), keep=t["models"], done=done)
 
-    def _posterior_table(self):
-        """The clique table of the current physical tree (root first, parents before children) that the tree walk and the
-        log-density evaluation share: dict(cliques, table (numpy POST_DTYPE), cols, obs, cfg (K, H, B, L), device, max_D,
-        pcol (variable -> first column of the sample matrix), total_dim, models (to keep alive while a launch reads them))."""
-        order = self._elimination_ordering
-        # every variable owns a permanent column range of the sample matrix (assigned when first seen), so a
-        # clique's column indices never change and are cached on its model together with the device pointers
+    def _post_columns(self):
+        """(variable -> first column of the sample matrix, number of columns).  Every variable owns a permanent column range
+        (assigned when first seen), so a clique's column indices and a factor's rows never change and are cached."""
         pcol = self.__dict__.setdefault("_post_col", {})
         total_dim = self.__dict__.get("_post_total", 0)
-        for v in order:
+        for v in self._elimination_ordering:
             if v not in pcol:
                 pcol[v] = total_dim
                 total_dim += v.dim
         self._post_total = total_dim
+        return pcol, total_dim
+
+    def _posterior_table(self):
+        """The clique table of the current physical tree (root first, parents before children) that the tree walk and the
+        log-density evaluation share: dict(cliques, table (numpy POST_DTYPE), cols, obs, cfg (K, H, B, L), device, max_D,
+        pcol (variable -> first column of the sample matrix), total_dim, models (to keep alive while a launch reads them))."""
+        pcol, total_dim = self._post_columns()
         cliques, stack = [], [self._physical_bayes_tree.root]
         while stack:
             c = stack.pop()
@@ -798,6 +802,40 @@ class NFiSAM(FactorGraphSolver):
         return dict(cliques=cliques, table=table, cols=np.concatenate(cols), obs=np.concatenate(obs), cfg=cfg, device=device,
                     max_D=max_D, pcol=pcol, total_dim=total_dim, models=models)
 
+    def _check_points(self, samples, what: str):
+        """Validation shared by the density evaluations: `samples` maps every variable of the elimination ordering to
+        [n, dim] values (numpy or torch, extra keys ignored).  -> ({variable: array}, n); ValueError names what is wrong."""
+        n = None
+        values = {}
+        for v in self._elimination_ordering:
+            if v not in samples:
+                raise ValueError("%s: samples lack variable %s" % (what, v.name))
+            a = samples[v]
+            if a.ndim == 1 and v.dim == 1:
+                a = a.reshape(-1, 1)
+            if a.ndim != 2 or a.shape[1] != v.dim:
+                raise ValueError("%s: samples of %s must be [n, %d], got %s" % (what, v.name, v.dim, tuple(a.shape)))
+            if n is None:
+                n = int(a.shape[0])
+            elif int(a.shape[0]) != n:
+                raise ValueError("%s: ragged samples: %s has %d rows, the others %d" % (what, v.name, a.shape[0], n))
+            values[v] = a
+        return values, n
+
+    @staticmethod
+    def _points_matrix(values, n, pcol, total_dim, device):
+        """The float32 point matrix [n, total_dim] in the walk's permanent column layout: a device tensor when every value is
+        a tensor, a numpy array otherwise."""
+        if values and all(torch.is_tensor(a) for a in values.values()):
+            S = torch.zeros(n, total_dim, dtype=torch.float32, device=device)
+            for v, a in values.items():
+                S[:, pcol[v]:pcol[v] + v.dim] = a.to(device=device, dtype=torch.float32)
+        else:
+            S = np.zeros((n or 0, total_dim), dtype=np.float32)
+            for v, a in values.items():
+                S[:, pcol[v]:pcol[v] + v.dim] = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        return S
+
     def posterior_log_pdf(self, samples, per_clique: bool = False):
         """log q(X) of the tree's posterior at n points, not in the reference: the sum over the cliques of the physical Bayes
         tree of log q_c(frontal | separator, true observations), each the clique's trained flow evaluated forward on the
@@ -818,38 +856,118 @@ class NFiSAM(FactorGraphSolver):
         for clique in tree.clique_ordering():
             if clique not in self._clique_density_model:
                 raise RuntimeError("posterior_log_pdf: clique %s has no trained model yet" % clique)
-        n = None
-        values = {}
-        for v in self._elimination_ordering:
-            if v not in samples:
-                raise ValueError("posterior_log_pdf: samples lack variable %s" % v.name)
-            a = samples[v]
-            if a.ndim == 1 and v.dim == 1:
-                a = a.reshape(-1, 1)
-            if a.ndim != 2 or a.shape[1] != v.dim:
-                raise ValueError("posterior_log_pdf: samples of %s must be [n, %d], got %s" % (v.name, v.dim, tuple(a.shape)))
-            if n is None:
-                n = int(a.shape[0])
-            elif int(a.shape[0]) != n:
-                raise ValueError("posterior_log_pdf: ragged samples: %s has %d rows, the others %d" % (v.name, a.shape[0], n))
-            values[v] = a
+        values, n = self._check_points(samples, "posterior_log_pdf")
         t = self._posterior_table()
         K, H, B, L = t["cfg"]
-        pcol, device = t["pcol"], t["device"]
-        if values and all(torch.is_tensor(a) for a in values.values()):
-            S = torch.zeros(n, t["total_dim"], dtype=torch.float32, device=device)
-            for v, a in values.items():
-                S[:, pcol[v]:pcol[v] + v.dim] = a.to(device=device, dtype=torch.float32)
-        else:
-            S = np.zeros((n or 0, t["total_dim"]), dtype=np.float32)
-            for v, a in values.items():
-                S[:, pcol[v]:pcol[v] + v.dim] = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        device = t["device"]
+        S = self._points_matrix(values, n, t["pcol"], t["total_dim"], device)
         out = _nh.posterior_log_density(t["table"], t["cols"], t["obs"], S, t["max_D"], K, H, B, L, device,
                                         per_clique=per_clique)
         if per_clique:
             log_q, per, _ = out
             return log_q.cpu().numpy(), per.t().cpu().numpy(), list(t["cliques"])
         return out.cpu().numpy()
+
+    # ---- the factor graph's joint density and what follows from it --------------------------------------------
+    def _joint_terms(self, pcol):
+        """The table of the physical factors (numpy FACTOR_DTYPE) and its uploaded copies.  Factors are only ever added and a
+        variable's rows are permanent: the table is cached and extended by the records of the factors that arrived since."""
+        factors = self.physical_factors
+        cache = self.__dict__.get("_joint_cache")
+        if cache is None or cache["count"] > len(factors):
+            cache = dict(count=0, terms=np.zeros(0, dtype=_nh.FACTOR_DTYPE), dev={})
+        if cache["count"] < len(factors):
+            fresh = _nh.pack_factor_terms(factors[cache["count"]:], pcol)        # NotImplementedError names the class
+            cache = dict(count=len(factors), terms=np.concatenate([cache["terms"], fresh]), dev={})
+        self._joint_cache = cache
+        return cache
+
+    def _joint_launch(self, S, pcol, device, per_factor: bool = False):
+        cache = self._joint_terms(pcol)
+        _nh.check_factor_terms(cache["terms"], int(S.shape[1]))
+        if device not in cache["dev"] and int(S.shape[0]):
+            cache["dev"][device], = _nh.upload(cache["terms"].view(np.uint8).reshape(-1), device=device, cached=True)
+        return _nh.factor_graph_log_density(cache["terms"], S, device, per_factor=per_factor,
+                                            terms_dev=cache["dev"].get(device))
+
+    def joint_log_pdf(self, samples, per_factor: bool = False):
+        """log p(X, Z) = sum over the measurement factors f of log p_f(x_f) at n points: the reference's JointFactor.log_pdf
+        (src/sampler/sampler_utils.py:85-98) over `physical_factors` -- the factors of the graph, never the FlowsPriorFactor
+        messages of the working graph -- evaluated on the device in float64 at the float32 points
+        (nfisam_factor_graph_log_density; mixtures by log-sum-exp, finite where the reference underflows to -inf).
+
+        samples: as `posterior_log_pdf` (dict or LazyPosterior, numpy or torch, extra keys ignored).
+        -> np.ndarray[n] float64; with per_factor=True: (total [n], terms [n, n_factors], factors in table order); the total
+        is the left-to-right float64 sum of the terms.  Headings count modulo 2 pi.
+        Raises RuntimeError when no factor graph has been built yet, ValueError for a missing variable, a wrong width or
+        ragged n, NotImplementedError naming the class of a factor without a device code -- before anything is launched."""
+        factors = self.physical_factors
+        if not factors or not self._elimination_ordering:
+            raise RuntimeError("joint_log_pdf: no factor graph yet (run an incremental update first)")
+        values, n = self._check_points(samples, "joint_log_pdf")
+        pcol, total_dim = self._post_columns()
+        self._joint_terms(pcol)                              # (packs: an unknown factor class raises here)
+        device = _device()
+        S = self._points_matrix(values, n, pcol, total_dim, device)
+        out = self._joint_launch(S, pcol, device, per_factor=per_factor)
+        if per_factor:
+            return out[0].cpu().numpy(), out[1].t().cpu().numpy(), list(factors)
+        return out.cpu().numpy()
+
+    def posterior_diagnostics(self, samples=None, n: int = None) -> dict:
+        """The solver grading itself without ground truth: log w = log p - log q at posterior samples.
+
+        samples=None draws `n` (default posterior_sample_num) points through the tree walk and scores the device matrix where
+        it lies; otherwise `samples` is scored (as `posterior_log_pdf` / `joint_log_pdf` accept it) and nothing is drawn: the
+        solver's state and random streams are untouched.
+        -> dict: log_p, log_q, log_w (float64 [n]), elbo (mean log w), log_evidence (logsumexp(log w) - log n), ess
+        ((sum w)^2 / sum w^2 from max-shifted weights, in [1, n]), map_index (argmax of log p over the draw: the reference's
+        MAP rule, src/slam/FactorGraphSolver.py:660-671), map_sample (variable -> [dim]).
+
+        p is the unnormalised joint p(X, Z) of the measurement factors and q a normalised density of X, so `log_evidence`
+        estimates log p(Z) and `elbo` bounds it from below; headings are compared modulo 2 pi on both sides.  log_w is
+        therefore not something that should average to zero.  log q is a float32 value of magnitude ~5e3 (spacing 5e-4);
+        log w inherits that."""
+        if not self.physical_factors or not self._elimination_ordering:
+            raise RuntimeError("posterior_diagnostics: no factor graph yet (run an incremental update first)")
+        tree = self._physical_bayes_tree
+        if tree is None or tree.root is None:
+            raise RuntimeError("posterior_diagnostics: no Bayes tree yet (run an incremental update first)")
+        for clique in tree.clique_ordering():
+            if clique not in self._clique_density_model:
+                raise RuntimeError("posterior_diagnostics: clique %s has no trained model yet" % clique)
+        if samples is not None:
+            values, rows = self._check_points(samples, "posterior_diagnostics")
+        t = self._posterior_table()
+        K, H, B, L = t["cfg"]
+        pcol, device = t["pcol"], t["device"]
+        self._joint_terms(pcol)
+        if samples is None:
+            S = self.posterior_launch(n)["S"]                # [n, total_dim] on the device
+        else:
+            S = self._points_matrix(values, rows, pcol, t["total_dim"], device)
+        log_q = _nh.posterior_log_density(t["table"], t["cols"], t["obs"], S, t["max_D"], K, H, B, L, device)
+        log_p = self._joint_launch(S, pcol, device)
+        log_p, log_q = log_p.cpu().numpy(), log_q.cpu().numpy().astype(np.float64)
+        log_w = log_p - log_q
+        out = dict(log_p=log_p, log_q=log_q, log_w=log_w)
+        if log_w.size == 0:
+            raise ValueError("posterior_diagnostics: no points")
+        top = log_w.max()
+        w = np.exp(log_w - top)
+        out["elbo"] = float(log_w.mean())
+        out["log_evidence"] = float(top + np.log(w.sum()) - np.log(log_w.size))
+        out["ess"] = float(w.sum() ** 2 / (w * w).sum())
+        k = int(np.argmax(log_p))
+        row = S[k].cpu().numpy() if torch.is_tensor(S) else S[k]
+        out["map_index"] = k
+        out["map_sample"] = {v: row[pcol[v]:pcol[v] + v.dim].copy() for v in self._elimination_ordering}
+        return out
+
+    def map_estimate(self, samples=None) -> dict:
+        """The sample of highest joint density log p among `samples` (or a fresh posterior draw): the reference's MAP
+        estimate (FactorGraphSolver.plot2d_MAP_rbt_only, src/slam/FactorGraphSolver.py:660-671).  -> variable -> [dim]."""
+        return self.posterior_diagnostics(samples)["map_sample"]
 
     def posterior_collect(self, handle, timer: List = None, copy_stream=None):
         """Second half: wait for the walk, one D2H copy, per-variable views of the sample matrix (in the elimination ordering
