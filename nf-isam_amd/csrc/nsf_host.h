@@ -99,6 +99,25 @@ constexpr int SPAN_WORD_TICKET = 63, SPAN_WORD_DECISION = 62, SPAN_WORD_LAST_T =
 constexpr int CLOSE_WORD_STEP = 58, CLOSE_WORD_STOP = 57;
 
 
+// What is being trained: the cliques of a launch and the flow's hyper-parameters.  Training plans hold one; the entry points
+// without a plan build one on the stack after their argument checks.  Everything that decides how an iteration is launched
+// (nsf_kernels.hip: train_shape and the enqueue_* functions) takes this record.
+struct TrainProblem {
+    const nfisam_clique* dev;       // device array of descriptors (batched), or nullptr: one clique, described by `host[0]`
+    const nfisam_clique* single;    // dev == nullptr ? host : nullptr (the by-value descriptor of TrainArgs / AdamArgs)
+    const nfisam_clique* host;      // host copy of the descriptors when the caller has one (plans, single cliques), else nullptr
+    int n_cliques, max_n, max_D;
+    int K, H, L;                    // H: the COMPILED hidden width (nsf_kernels.hip: compiled_H)
+    float B;
+};
+
+// (clique, dim, particle block) blocks of a launch: the sum over the cliques of D x ceil(n / particles per block)
+static inline long launch_blocks(const nfisam_clique* host, int n_cliques, int per_block) {
+    long blocks = 0;
+    for (int c = 0; c < n_cliques; ++c) blocks += (long)host[c].D * ((host[c].n + per_block - 1) / per_block);
+    return blocks;
+}
+
 // Launchers of one (K, H) pair, exported by the kernel unit that instantiates it.
 struct NsfUnitOps {
     int K, H;
@@ -205,8 +224,7 @@ constexpr int PANEL_BASE = 4;      // LDS words in front of the conditioner pane
 // NFISAM_BIG_W = 1..8 for experiments.  Eight (half the gradient copies for the fused Adam update to read back, half the
 // staging work per thread) measured 13 % SLOWER on a single Plaza clique: two waves per SIMD on 60 CUs instead of one
 // wave per SIMD on 120 -- in the latency regime a wave wants its SIMD to itself.
-static inline int dim_major_waves(int n_cliques, int max_n, int max_D, int T) {
-    (void)n_cliques; (void)max_n; (void)max_D; (void)T;
+static inline int dim_major_waves() {
     const char* e = getenv("NFISAM_BIG_W");
     const int v = e != nullptr ? atoi(e) : 4;
     return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 4;

@@ -690,21 +690,22 @@ extern "C" size_t nfisam_nsf_grad_workspace_count(int n, int D, int K, int H, in
 }
 
 // Launch shape of one training iteration: kernel family, tiles per block, particles per gradient copy (0 = one
-// shared copy accumulated with float atomics).
+// shared copy accumulated with float atomics).  Computed per call -- the NFISAM_* knobs behind it are read per call (tests switch
+// them in-process) -- and handed down within one enqueue_step; never kept in a plan.
 struct TrainShape { int tile, T, slab, W, half; };
-static TrainShape train_shape(int n_cliques, int max_n, int max_D, int L, int H, int K) {
+static TrainShape train_shape(const TrainProblem& q) {
     TrainShape sh;
-    sh.tile = train_tile(n_cliques, max_n, max_D, H, L == 1, (H == 4 || H == 16) && L > 1 && pair_h4_fits(L, max_D, H));
-    sh.T = tiles_per_block(n_cliques, max_n, max_D, L, sh.tile, H);
-    sh.slab = use_slabs(max_n, sh.tile) ? sh.tile * sh.T : 0;      // the workspace holds ceil(n / tile) copies at most
+    sh.tile = train_tile(q.n_cliques, q.max_n, q.max_D, q.H, q.L == 1, (q.H == 4 || q.H == 16) && q.L > 1 && pair_h4_fits(q.L, q.max_D, q.H));
+    sh.T = tiles_per_block(q.n_cliques, q.max_n, q.max_D, q.L, sh.tile, q.H);
+    sh.slab = use_slabs(q.max_n, sh.tile) ? sh.tile * sh.T : 0;      // the workspace holds ceil(n / tile) copies at most
     sh.W = 0;
     sh.half = 0;
-    if (is_dim_major(n_cliques, max_n, max_D, L, sh.tile, H)) {
-        sh.W = dim_major_waves(n_cliques, max_n, max_D, sh.T);
+    if (is_dim_major(q.n_cliques, q.max_n, q.max_D, q.L, sh.tile, q.H)) {
+        sh.W = dim_major_waves();
         sh.slab *= sh.W;                                            // one copy per block
         // two lanes per particle (nsf_half.h): 32 particles per wave; a function of the launch shape only, like everything
         // here, so that the gradient, Adam and bookkeeping launches of an iteration agree on the number of gradient copies
-        if (sh.slab != 0 && half_shape(n_cliques, max_n, max_D, K, H, L, sh.T)) {
+        if (sh.slab != 0 && half_shape(q.n_cliques, q.max_n, q.max_D, q.K, q.H, q.L, sh.T)) {
             sh.half = 1;
             sh.W = half_waves();
             sh.slab = 32 * sh.T * sh.W;
@@ -713,67 +714,111 @@ static TrainShape train_shape(int n_cliques, int max_n, int max_D, int L, int H,
     return sh;
 }
 
+// The problem record of an entry point without a plan (after its argument checks): the descriptors are on the host (one clique,
+// passed by value) or on the device.
+static TrainProblem make_problem(const nfisam_clique* cliques, bool on_host, int n_cliques, int max_n, int max_D, int K, int H, int L, float B) {
+    TrainProblem q;
+    q.dev = on_host ? nullptr : cliques;
+    q.host = on_host ? cliques : nullptr;
+    q.single = q.host;
+    q.n_cliques = n_cliques; q.max_n = max_n; q.max_D = max_D;
+    q.K = K; q.H = H; q.L = L; q.B = B;
+    return q;
+}
+
 // The Adam update of iteration j rides at the START of iteration j+1's gradient kernel (nsf_train1_kernel with the
 // MFMA conditioner, nsf_cond_mfma.h) when the launch is dim-major with few gradient copies; the chunk's last update is
 // applied by nsf_adam_kernel in `close_chunk` mode.  Saves one kernel boundary (~3-4 us) per iteration.
-static bool fused_adam_shape(int n_cliques, int max_n, int max_D, int L, int H, const TrainShape& sh) {
+static bool fused_adam_shape(const TrainProblem& q, const TrainShape& sh) {
     const char* e = getenv("NFISAM_FUSED_ADAM");
     if (e != nullptr && e[0] == '0') return false;
-    if (!is_dim_major(n_cliques, max_n, max_D, L, sh.tile, H) || sh.slab == 0) return false;
-    return (max_n + sh.slab - 1) / sh.slab <= 8;              // nsf_adam_kernel's one-thread-per-parameter summation order
+    if (!is_dim_major(q.n_cliques, q.max_n, q.max_D, q.L, sh.tile, q.H) || sh.slab == 0) return false;
+    return (q.max_n + sh.slab - 1) / sh.slab <= 8;              // nsf_adam_kernel's one-thread-per-parameter summation order
 }
 
 // Multi-layer training launches that go to nsf_train3_kernel keep a PANEL IMAGE per clique (behind the loss ring): the Adam
 // kernel of iteration j writes it, the gradient kernel of iteration j + 1 copies it (iteration 0 of a chunk stages from
 // the parameters themselves: whoever set them -- the caller, an earlier run -- did not go through the Adam kernel).
-static bool pair_image_shape(int max_D, int K, int H, int L, const TrainShape& sh) {
-    if (L < 2 || sh.tile != TILE2 || max_D > PAIR_MAX_D) return false;
+static bool pair_image_shape(const TrainProblem& q, const TrainShape& sh) {
+    if (q.L < 2 || sh.tile != TILE2 || q.max_D > PAIR_MAX_D) return false;
     const char* e = getenv("NFISAM_PAIR_IMAGE");
     if (e != nullptr && e[0] == '0') return false;
-    const NsfUnitOps* ops = find_ops(K, H);
-    return ops != nullptr && ops->pair_lds(L, max_D) > 0;
+    const NsfUnitOps* ops = find_ops(q.K, q.H);
+    return ops != nullptr && ops->pair_lds(q.L, q.max_D) > 0;
 }
 
-static int enqueue_grad(const nfisam_clique* dev_cliques, const nfisam_clique* single, int n_cliques, int max_n,
-                        int max_D, int K, int H, float B, int L, int max_iters, int iter_idx, hipStream_t s,
-                        const nfisam_adam_cfg* fused_cfg = nullptr, const nfisam_clique* host_cliques = nullptr,
-                        int chain = 0, int n_chains = 1, bool pair_image = false, int persist_iters = 0, int span_window = 0,
-                        nfisam_train_state* span_mirror = nullptr) {
+// What ONE gradient launch adds to the problem and its shape (enqueue_grad; enqueue_step takes the caller's part of it:
+// iter_idx, chain / n_chains, persist_iters -- and fills in the rest)
+struct GradLaunch {
+    int iter_idx = 0;                            // iteration inside the chunk
+    int max_iters = 0x7fffffff;                  // the run's budget (launches without a train state: none)
+    const nfisam_adam_cfg* fused_cfg = nullptr;  // != nullptr: the launch applies the previous iteration's Adam update on its way in
+    int chain = 0, n_chains = 1;                 // this launch covers the octets of groups chain, chain + n_chains, ...
+    bool pair_image = false;                     // nsf_train3_kernel: the cliques keep a panel image (current from iteration 1 on)
+    int persist_iters = 0;                       // > 0: iterations 0 .. persist_iters - 1 of the chunk in this one launch
+    int span_window = 0;                         // > 0: window-spanning launch, closes every window of this many iterations itself
+    nfisam_train_state* span_mirror = nullptr;   // ... and publishes to the plan's host-pinned mirror
+};
+static GradLaunch at_iteration(int iter_idx) {
+    GradLaunch g;
+    g.iter_idx = iter_idx;
+    return g;
+}
+static GradLaunch persistent_chunk(int iters) {    // (iters == 0: iteration 0 as a launch of its own)
+    GradLaunch g;
+    g.persist_iters = iters;
+    return g;
+}
+
+static int enqueue_grad(const TrainProblem& q, const TrainShape& sh, const GradLaunch& g, hipStream_t s) {
     TrainArgs a;
     memset(&a, 0, sizeof(a));
-    a.span_window = span_window;
-    a.span_mirror = span_mirror;
-    const TrainShape sh = train_shape(n_cliques, max_n, max_D, L, H, K);
+    a.span_window = g.span_window;
+    a.span_mirror = g.span_mirror;
     a.tile = sh.tile; a.tiles_per_block = sh.T; a.slab = sh.slab; a.waves = sh.W; a.half = sh.half;
-    if (fused_cfg != nullptr) {
+    if (g.fused_cfg != nullptr) {
         a.fused_adam = 1;
-        a.adam = *fused_cfg;
-        a.log_b1 = (float)log((double)fused_cfg->beta1);
-        a.log_b2 = (float)log((double)fused_cfg->beta2);
+        a.adam = *g.fused_cfg;
+        a.log_b1 = (float)log((double)g.fused_cfg->beta1);
+        a.log_b2 = (float)log((double)g.fused_cfg->beta2);
     }
-    a.cliques = dev_cliques;
-    a.host_cliques = host_cliques;
-    a.chain = chain; a.n_chains = n_chains;
-    if (single != nullptr) a.single = *single;
-    a.B = B; a.L = L; a.max_iters = max_iters; a.nll_mode = 1; a.iter_idx = iter_idx;
-    a.persist_iters = persist_iters;                           // > 0: iterations 0 .. persist_iters - 1 of the chunk in this one launch
-    a.pair_image = (pair_image && iter_idx > 0) ? 1 : 0;
+    a.cliques = q.dev;
+    a.host_cliques = q.dev != nullptr ? q.host : nullptr;
+    a.chain = g.chain; a.n_chains = g.n_chains;
+    if (q.single != nullptr) a.single = *q.single;
+    a.B = q.B; a.L = q.L; a.max_iters = g.max_iters; a.nll_mode = 1; a.iter_idx = g.iter_idx;
+    a.persist_iters = g.persist_iters;
+    a.pair_image = (g.pair_image && g.iter_idx > 0) ? 1 : 0;
     a.pair_ws = 1;                                             // clique descriptors: kgrad is a workspace by contract
-    const NsfUnitOps* ops = find_ops(K, H);
+    const NsfUnitOps* ops = find_ops(q.K, q.H);
     if (ops == nullptr) return NFISAM_ERR_ARG;
-    return ops->train(a, n_cliques, max_n, max_D, s);
+    return ops->train(a, q.n_cliques, q.max_n, q.max_D, s);
 }
 
-static void fill_adam_args(AdamArgs& ad, const nfisam_clique* dev_cliques, const nfisam_clique* single, int n_cliques,
-                           int max_n, int max_D, int K, int H, int L, const nfisam_adam_cfg* cfg) {
+static void fill_adam_args(AdamArgs& ad, const TrainProblem& q, const TrainShape& sh, const nfisam_adam_cfg* cfg) {
     memset(&ad, 0, sizeof(ad));
-    ad.cliques = dev_cliques;
-    if (single != nullptr) ad.single = *single;
+    ad.cliques = q.dev;
+    if (q.single != nullptr) ad.single = *q.single;
     ad.cfg = *cfg;
-    ad.slab = train_shape(n_cliques, max_n, max_D, L, H, K).slab;
+    ad.slab = sh.slab;
     ad.log_b1 = (float)log((double)cfg->beta1);
     ad.log_b2 = (float)log((double)cfg->beta2);
-    ad.L = L; ad.K = K; ad.H = H; ad.max_n = max_n;
+    ad.L = q.L; ad.K = q.K; ad.H = q.H; ad.max_n = q.max_n;
+}
+
+// grid.x of an nsf_adam_kernel launch (Adam blocks per clique) and ad.few_copies: 256 parameters per block when every clique has
+// at most eight gradient copies (one thread per parameter), else 32 (x 8 tile-lanes) -- a few hundred small blocks spread the
+// latency-bound work; at most 1024 blocks: one pass for up to 32 k parameters (C2: 275 blocks; a second pass is a second memory
+// round trip).  `closing`: the launch that applies a chunk's last pending update (its launches always have gradient slabs).
+// The per-iteration launch (`closing` false) does NOT clamp the 256-per-block count and tests ad.slab: beyond 262144 parameters
+// (many layers) its grid is larger than the closing rule's, so each keeps the rule it had.
+static int adam_blocks(const TrainProblem& q, AdamArgs& ad, bool closing) {
+    const size_t Pmax = (size_t)q.L * kcount(q.max_D, q.K, q.H);
+    const size_t per32 = (Pmax + 31) / 32, per256 = (Pmax + 255) / 256;
+    const auto clamped = [](size_t b) { return b < 1 ? 1 : (b > 1024 ? 1024 : (int)b); };
+    ad.few_copies = ((closing || ad.slab != 0) && (q.max_n + ad.slab - 1) / ad.slab <= 8) ? 1 : 0;
+    if (!ad.few_copies) return clamped(per32);
+    return closing ? clamped(per256) : (int)per256;
 }
 
 // The chunk-persistent form of the dim-major kernel (nsf_unit.hip: nsf_train1_kernel<K, H, true>) needs every block of the
@@ -791,11 +836,11 @@ static inline double mono_seconds() {
     return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
 static std::atomic<bool> g_persist_broken{false};     // a persistent launch of this process stalled once: never again (nfisam_nsf_train_plan_run)
-static bool persist_shape(const nfisam_clique* host, int n_cliques, int max_n, int max_D, int K, int H, int L,
-                          long* blocks_out = nullptr, long* places_out = nullptr) {
+static bool persist_shape(const TrainProblem& q, long* blocks_out = nullptr, long* places_out = nullptr) {
+    const int max_n = q.max_n, max_D = q.max_D, K = q.K, H = q.H, L = q.L;
     static const bool on = !(getenv("NFISAM_PERSIST") != nullptr && getenv("NFISAM_PERSIST")[0] == '0');
-    if (!on || g_persist_broken.load() || host == nullptr || L != 1 || (H != 16 && H != 8 && H != 4) || max_D > FUSED_COUNTERS) return false;
-    const TrainShape sh = train_shape(n_cliques, max_n, max_D, L, H, K);
+    if (!on || g_persist_broken.load() || q.host == nullptr || L != 1 || (H != 16 && H != 8 && H != 4) || max_D > FUSED_COUNTERS) return false;
+    const TrainShape sh = train_shape(q);
     // (the one-launch-per-iteration fused form sums at most eight gradient copies -- fused_adam_shape --; the persistent
     //  exchange takes up to sixteen, round 5: single cliques of up to 4096 particles, whose plain graph is then gradient
     //  kernel + Adam kernel per iteration; nsf_adam_kernel's lane-partial order for that many copies is the order the
@@ -804,11 +849,10 @@ static bool persist_shape(const nfisam_clique* host, int n_cliques, int max_n, i
         const char* fe = getenv("NFISAM_FUSED_ADAM");
         if (fe != nullptr && fe[0] == '0') return false;
     }
-    if (!is_dim_major(n_cliques, max_n, max_D, L, sh.tile, H) || sh.T != 1 || sh.slab == 0 || (sh.W != 4 && !sh.half) ||
+    if (!is_dim_major(q.n_cliques, max_n, max_D, L, sh.tile, H) || sh.T != 1 || sh.slab == 0 || (sh.W != 4 && !sh.half) ||
         (max_n + sh.slab - 1) / sh.slab > PERSIST_MAX_COPIES)
         return false;
-    long blocks = 0;
-    for (int c = 0; c < n_cliques; ++c) blocks += (long)host[c].D * ((host[c].n + sh.slab - 1) / sh.slab);
+    const long blocks = launch_blocks(q.host, q.n_cliques, sh.slab);
     // (asked once per (K, H, clique width, device): the query costs a device-properties call, and replica schedulers
     //  create plans by the hundred)
     static std::mutex mu;
@@ -937,80 +981,69 @@ static bool device_is_quiet(long blocks, long places) {
     return quiet;
 }
 
-// iteration `iter_idx` of the current chunk: gradient kernel + Adam kernel
-static int enqueue_step(const nfisam_clique* dev_cliques, const nfisam_clique* single, int n_cliques, int max_n,
-                        int max_D, int K, int H, float B, int L, const nfisam_adam_cfg* cfg, int iter_idx,
-                        hipStream_t s, const nfisam_clique* host_cliques = nullptr, int chain = 0, int n_chains = 1,
-                        int persist_iters = 0) {
-    const TrainShape sh = train_shape(n_cliques, max_n, max_D, L, H, K);
-    const bool fused = fused_adam_shape(n_cliques, max_n, max_D, L, H, sh) || persist_iters > 0;   // (the persistent form applies its own updates: up to 16 copies)
-    if (!fused && n_chains > 1) return NFISAM_ERR_ARG;
-    const bool image = !fused && pair_image_shape(max_D, K, H, L, sh);
-    int rc = enqueue_grad(dev_cliques, single, n_cliques, max_n, max_D, K, H, B, L, cfg->max_iters, iter_idx, s,
-                          fused ? cfg : nullptr, host_cliques, chain, n_chains, image, persist_iters);
+// iteration `g.iter_idx` of the current chunk: gradient kernel + Adam kernel (the caller fills g's iter_idx, chain / n_chains
+// and persist_iters; the rest is decided here)
+static int enqueue_step(const TrainProblem& q, const nfisam_adam_cfg* cfg, GradLaunch g, hipStream_t s) {
+    const TrainShape sh = train_shape(q);
+    const bool fused = fused_adam_shape(q, sh) || g.persist_iters > 0;   // (the persistent form applies its own updates: up to 16 copies)
+    if (!fused && g.n_chains > 1) return NFISAM_ERR_ARG;
+    const bool image = !fused && pair_image_shape(q, sh);
+    g.max_iters = cfg->max_iters;
+    g.fused_cfg = fused ? cfg : nullptr;
+    g.pair_image = image;
+    int rc = enqueue_grad(q, sh, g, s);
     if (rc || fused) return rc;
     AdamArgs ad;
-    fill_adam_args(ad, dev_cliques, single, n_cliques, max_n, max_D, K, H, L, cfg);
-    ad.iter_idx = iter_idx;
+    fill_adam_args(ad, q, sh, cfg);
+    ad.iter_idx = g.iter_idx;
     if (image) {
-        rc = find_ops(K, H)->pair_map(&ad.pair_map, ad.pair_off);
+        rc = find_ops(q.K, q.H)->pair_map(&ad.pair_map, ad.pair_off);
         if (rc) return rc;
     }
-    // 32 parameters per block (x 8 tile-lanes); a few hundred small blocks spread the latency-bound work
-    const size_t Pmax = (size_t)L * kcount(max_D, K, H);
-    int ablocks = (int)((Pmax + 31) / 32);
-    if (ablocks < 1) ablocks = 1;
-    if (ablocks > 1024) ablocks = 1024;   // one pass for up to 32 k parameters (C2: 275 blocks; a second pass is a second memory round trip)
-    ad.few_copies = (ad.slab != 0 && (max_n + ad.slab - 1) / ad.slab <= 8) ? 1 : 0;
-    if (ad.few_copies) ablocks = (int)((Pmax + 255) / 256);
-    hipLaunchKernelGGL(nsf_adam_kernel, dim3(ablocks, n_cliques), dim3(256), 0, s, ad);
+    const int ablocks = adam_blocks(q, ad, false);
+    hipLaunchKernelGGL(nsf_adam_kernel, dim3(ablocks, q.n_cliques), dim3(256), 0, s, ad);
     HIP_TRY(hipGetLastError());
     return NFISAM_OK;
 }
 
 // closes a chunk of `chunk` iterations: loss record, early-stop rule, step counter
-static int enqueue_bookkeeping(const nfisam_clique* dev_cliques, const nfisam_clique* single, int n_cliques, int max_n,
-                               int max_D, int K, int H, int L, const nfisam_adam_cfg* cfg, int chunk, hipStream_t s,
-                               nfisam_train_state* mirror = nullptr) {
+static int enqueue_bookkeeping(const TrainProblem& q, const TrainShape& sh, const nfisam_adam_cfg* cfg, int chunk, hipStream_t s,
+                               nfisam_train_state* mirror) {
     AdamArgs ad;
-    fill_adam_args(ad, dev_cliques, single, n_cliques, max_n, max_D, K, H, L, cfg);
+    fill_adam_args(ad, q, sh, cfg);
     ad.chunk = chunk;
     ad.mirror = mirror;
-    hipLaunchKernelGGL(nsf_bookkeep_kernel, dim3(n_cliques), dim3(256), 0, s, ad);
+    hipLaunchKernelGGL(nsf_bookkeep_kernel, dim3(q.n_cliques), dim3(256), 0, s, ad);
     HIP_TRY(hipGetLastError());
     return NFISAM_OK;
 }
 
 // end of a chunk: (fused-Adam launches) the last iteration's pending update, then the bookkeeping
-static int enqueue_chunk_end(const nfisam_clique* dev_cliques, const nfisam_clique* single, int n_cliques, int max_n,
-                             int max_D, int K, int H, int L, const nfisam_adam_cfg* cfg, int chunk, hipStream_t s,
+static int enqueue_chunk_end(const TrainProblem& q, const nfisam_adam_cfg* cfg, int chunk, hipStream_t s,
                              nfisam_train_state* mirror = nullptr, bool persistent_chunk = false) {
     // (`persistent_chunk`: the chunk ran as a chunk-persistent launch, whose last update is always pending -- also for
     //  groups of 9 .. 16 copies, which the one-launch-per-iteration form does not fuse)
-    if (persistent_chunk || fused_adam_shape(n_cliques, max_n, max_D, L, H, train_shape(n_cliques, max_n, max_D, L, H, K))) {
+    const TrainShape sh = train_shape(q);
+    if (persistent_chunk || fused_adam_shape(q, sh)) {
         AdamArgs ad;
-        fill_adam_args(ad, dev_cliques, single, n_cliques, max_n, max_D, K, H, L, cfg);
+        fill_adam_args(ad, q, sh, cfg);
         ad.close_chunk = chunk;
-        const size_t Pmax = (size_t)L * kcount(max_D, K, H);
-        ad.few_copies = ((max_n + ad.slab - 1) / ad.slab <= 8) ? 1 : 0;
-        int ablocks = ad.few_copies ? (int)((Pmax + 255) / 256) : (int)((Pmax + 31) / 32);
-        if (ablocks < 1) ablocks = 1;
-        if (ablocks > 1024) ablocks = 1024;
+        const int ablocks = adam_blocks(q, ad, true);
         // behind a chunk-persistent launch of cliques of up to SPAN_MAX_D dims: ONE kernel, the bookkeeping block next to the Adam
         // blocks (nsf_adam_kernel with `fused_close`; NFISAM_FUSED_CLOSE=0: two kernels, the same bits)
         static const bool fuse_on = !(getenv("NFISAM_FUSED_CLOSE") != nullptr && getenv("NFISAM_FUSED_CLOSE")[0] == '0');
-        if (persistent_chunk && fuse_on && max_D <= SPAN_MAX_D) {
+        if (persistent_chunk && fuse_on && q.max_D <= SPAN_MAX_D) {
             ad.fused_close = 1;
             ad.chunk = chunk;
             ad.mirror = mirror;
-            hipLaunchKernelGGL(nsf_adam_kernel, dim3(ablocks + 1, n_cliques), dim3(256), 0, s, ad);
+            hipLaunchKernelGGL(nsf_adam_kernel, dim3(ablocks + 1, q.n_cliques), dim3(256), 0, s, ad);
             HIP_TRY(hipGetLastError());
             return NFISAM_OK;
         }
-        hipLaunchKernelGGL(nsf_adam_kernel, dim3(ablocks, n_cliques), dim3(256), 0, s, ad);
+        hipLaunchKernelGGL(nsf_adam_kernel, dim3(ablocks, q.n_cliques), dim3(256), 0, s, ad);
         HIP_TRY(hipGetLastError());
     }
-    return enqueue_bookkeeping(dev_cliques, single, n_cliques, max_n, max_D, K, H, L, cfg, chunk, s, mirror);
+    return enqueue_bookkeeping(q, sh, cfg, chunk, s, mirror);
 }
 
 // Iterations per chunk: the early-stop rule is evaluated when a chunk is closed, so the chunk length has to
@@ -1032,16 +1065,15 @@ static int check_cfg(const nfisam_adam_cfg* cfg, int K, int H, int L, float B) {
 }
 
 // Parallel launches per iteration of a training plan (see nfisam_nsf_train_plan_create): NFISAM_CHAINS=n, default by size.
-static int plan_chains(int n_cliques, int max_n, int max_D, int K, int H, int L) {
-    (void)K;
-    const TrainShape sh = train_shape(n_cliques, max_n, max_D, L, H, K);
-    if (!fused_adam_shape(n_cliques, max_n, max_D, L, H, sh)) return 1;
-    const long waves = (long)n_cliques * max_D * ((max_n + 64 * sh.T - 1) / (64 * sh.T));
+static int plan_chains(const TrainProblem& q) {
+    const TrainShape sh = train_shape(q);
+    if (!fused_adam_shape(q, sh)) return 1;
+    const long waves = (long)q.n_cliques * q.max_D * ((q.max_n + 64 * sh.T - 1) / (64 * sh.T));
     // measured (MI355X): C3 (3072 waves) 15.0 -> 14.5 us per iteration, 64 cliques (7680 waves) 89.5 -> 82.5;
     // one Plaza clique (480 waves) 11.3 -> 11.7: stays one launch
     int chains = waves >= 1536 ? 2 : 1;
     if (const char* ce = getenv("NFISAM_CHAINS")) chains = atoi(ce);
-    const int octets = (n_cliques * max_D + 7) / 8;
+    const int octets = (q.n_cliques * q.max_D + 7) / 8;
     if (chains > octets) chains = octets;
     if (chains < 1) chains = 1;
     if (chains > 8) chains = 8;
@@ -1051,7 +1083,7 @@ static int plan_chains(int n_cliques, int max_n, int max_D, int K, int H, int L)
 extern "C" int nfisam_nsf_train_chains(int n_cliques, int max_n, int max_D, int K, int H, int L) {
     H = compiled_H(H);                                        // any hidden_dim <= 16: the next compiled width, zero-padded
     if (n_cliques < 1 || max_n < 1 || max_D < 1 || L < 1 || !nfisam_nsf_supported(K, H)) return 1;
-    return plan_chains(n_cliques, max_n, max_D, K, H, L);
+    return plan_chains(make_problem(nullptr, false, n_cliques, max_n, max_D, K, H, L, 0.0f));
 }
 
 extern "C" int nfisam_nsf_train_gradient_part(const nfisam_clique* cliques, int n_cliques, int cliques_on_host, int max_n,
@@ -1061,15 +1093,14 @@ extern "C" int nfisam_nsf_train_gradient_part(const nfisam_clique* cliques, int 
     if (cliques == nullptr || n_cliques < 1 || max_n < 1 || max_D < 1 || L < 1 || !(B > 0) ||
         !nfisam_nsf_supported(K, H) || n_chains < 1 || chain < 0 || chain >= n_chains)
         return NFISAM_ERR_ARG;
-    if (n_chains > 1 && !fused_adam_shape(n_cliques, max_n, max_D, L, H, train_shape(n_cliques, max_n, max_D, L, H, K)))
-        return NFISAM_ERR_ARG;
-    if (cliques_on_host) {
-        if (n_cliques != 1) return NFISAM_ERR_ARG;
-        return enqueue_grad(nullptr, cliques, 1, max_n, max_D, K, H, B, L, 0x7fffffff, 0, (hipStream_t)stream, nullptr,
-                            nullptr, chain, n_chains);
-    }
-    return enqueue_grad(cliques, nullptr, n_cliques, max_n, max_D, K, H, B, L, 0x7fffffff, 0, (hipStream_t)stream, nullptr,
-                        nullptr, chain, n_chains);
+    const TrainProblem q = make_problem(cliques, cliques_on_host != 0, n_cliques, max_n, max_D, K, H, L, B);
+    const TrainShape sh = train_shape(q);
+    if (n_chains > 1 && !fused_adam_shape(q, sh)) return NFISAM_ERR_ARG;
+    if (cliques_on_host && n_cliques != 1) return NFISAM_ERR_ARG;
+    GradLaunch g;
+    g.chain = chain;
+    g.n_chains = n_chains;
+    return enqueue_grad(q, sh, g, (hipStream_t)stream);
 }
 
 extern "C" int nfisam_nsf_train_gradient(const nfisam_clique* cliques, int n_cliques, int cliques_on_host, int max_n,
@@ -1078,11 +1109,9 @@ extern "C" int nfisam_nsf_train_gradient(const nfisam_clique* cliques, int n_cli
     if (cliques == nullptr || n_cliques < 1 || max_n < 1 || max_D < 1 || L < 1 || !(B > 0) ||
         !nfisam_nsf_supported(K, H))
         return NFISAM_ERR_ARG;
-    if (cliques_on_host) {
-        if (n_cliques != 1) return NFISAM_ERR_ARG;
-        return enqueue_grad(nullptr, cliques, 1, max_n, max_D, K, H, B, L, 0x7fffffff, 0, (hipStream_t)stream);
-    }
-    return enqueue_grad(cliques, nullptr, n_cliques, max_n, max_D, K, H, B, L, 0x7fffffff, 0, (hipStream_t)stream);
+    if (cliques_on_host && n_cliques != 1) return NFISAM_ERR_ARG;
+    const TrainProblem q = make_problem(cliques, cliques_on_host != 0, n_cliques, max_n, max_D, K, H, L, B);
+    return enqueue_grad(q, train_shape(q), GradLaunch(), (hipStream_t)stream);
 }
 
 extern "C" int nfisam_nsf_train_step(const nfisam_clique* cliques, int n_cliques, int cliques_on_host, int max_n,
@@ -1092,12 +1121,11 @@ extern "C" int nfisam_nsf_train_step(const nfisam_clique* cliques, int n_cliques
     int rc = check_cfg(cfg, K, H, L, B);
     if (rc) return rc;
     if (cliques == nullptr || n_cliques < 1 || max_n < 1 || max_D < 1) return NFISAM_ERR_ARG;
-    const nfisam_clique* dev = cliques_on_host ? nullptr : cliques;
-    const nfisam_clique* single = cliques_on_host ? cliques : nullptr;
     if (cliques_on_host && n_cliques != 1) return NFISAM_ERR_ARG;
-    rc = enqueue_step(dev, single, n_cliques, max_n, max_D, K, H, B, L, cfg, 0, (hipStream_t)stream);
+    const TrainProblem q = make_problem(cliques, cliques_on_host != 0, n_cliques, max_n, max_D, K, H, L, B);
+    rc = enqueue_step(q, cfg, at_iteration(0), (hipStream_t)stream);
     if (rc) return rc;
-    return enqueue_chunk_end(dev, single, n_cliques, max_n, max_D, K, H, L, cfg, 1, (hipStream_t)stream);
+    return enqueue_chunk_end(q, cfg, 1, (hipStream_t)stream);
 }
 
 // ---- training plan: descriptors + (optionally) a hipGraph of `chunk` iterations, built once ----
@@ -1106,9 +1134,8 @@ static std::atomic<bool> g_persist_busy{false};      // a run of a chunk-persist
 
 struct nfisam_train_plan {
     std::vector<nfisam_clique> host;
-    const nfisam_clique* dev = nullptr;
-    int n_cliques = 0, K = 0, H = 0, L = 0, max_n = 0, max_D = 0, chunk = 0;
-    float B = 0;
+    TrainProblem prob = {};                // what is trained (prob.host points into `host`)
+    int chunk = 0;
     nfisam_adam_cfg cfg;
     hipStream_t cap = nullptr;
     hipEvent_t ev = nullptr;
@@ -1225,8 +1252,10 @@ static int plan_create_impl(const nfisam_clique* host_cliques, const nfisam_cliq
         return NFISAM_ERR_ARG;
     nfisam_train_plan* p = new nfisam_train_plan();
     p->host.assign(host_cliques, host_cliques + n_cliques);
-    p->dev = dev_cliques;
-    p->n_cliques = n_cliques; p->K = K; p->H = H; p->L = L; p->B = B; p->cfg = *cfg;
+    p->prob.host = p->host.data();
+    p->prob.dev = dev_cliques;
+    p->prob.single = dev_cliques == nullptr ? p->prob.host : nullptr;
+    p->prob.n_cliques = n_cliques; p->prob.K = K; p->prob.H = H; p->prob.L = L; p->prob.B = B; p->cfg = *cfg;
     (void)hipGetDevice(&p->device);
     p->chunk = chunk_length(cfg);
     if (val != nullptr) {                  // hold-out validation: one chunk = one validation period, the window rule is off (NFiSAM.py:481: `if testing_data is None`)
@@ -1244,12 +1273,12 @@ static int plan_create_impl(const nfisam_clique* host_cliques, const nfisam_cliq
     memset(p->hst, 0, sizeof(nfisam_train_state) * (size_t)n_cliques);
     for (int c = 0; c < n_cliques; ++c) {
         if (host_cliques[c].n < 1 || host_cliques[c].D < 1) { nfisam_nsf_train_plan_destroy(p); return NFISAM_ERR_ARG; }
-        p->max_n = host_cliques[c].n > p->max_n ? host_cliques[c].n : p->max_n;
-        p->max_D = host_cliques[c].D > p->max_D ? host_cliques[c].D : p->max_D;
+        p->prob.max_n = host_cliques[c].n > p->prob.max_n ? host_cliques[c].n : p->prob.max_n;
+        p->prob.max_D = host_cliques[c].D > p->prob.max_D ? host_cliques[c].D : p->prob.max_D;
     }
     {   // device tables of the training kernels: built here, outside the capture below
         const NsfUnitOps* ops = find_ops(K, H);
-        rc = ops != nullptr ? ops->prepare(p->max_D) : NFISAM_ERR_ARG;
+        rc = ops != nullptr ? ops->prepare(p->prob.max_D) : NFISAM_ERR_ARG;
         if (rc) { nfisam_nsf_train_plan_destroy(p); return rc; }
     }
     if (use_graph) {
@@ -1270,7 +1299,7 @@ static int plan_create_impl(const nfisam_clique* host_cliques, const nfisam_cliq
         //  which 20 iterations do not earn back -- C3, 20 iterations: 18.2 vs 18.8 us per iteration; with several chunks the
         //  launch of chunk k + 1 hides behind chunk k and two branches win from 20 iterations per chunk up: 15.2 -> 14.5)
         const bool one_short_chunk = cfg->max_iters <= p->chunk && p->chunk < 40 && getenv("NFISAM_CHAINS") == nullptr;
-        const int chains = (one_short_chunk || !p->val.empty()) ? 1 : plan_chains(n_cliques, p->max_n, p->max_D, K, H, L);
+        const int chains = (one_short_chunk || !p->val.empty()) ? 1 : plan_chains(p->prob);
         for (int g = 1; g < chains && e == hipSuccess; ++g) {
             hipStream_t st = nullptr;
             hipEvent_t ev2 = nullptr;
@@ -1279,7 +1308,7 @@ static int plan_create_impl(const nfisam_clique* host_cliques, const nfisam_cliq
             if (e == hipSuccess) p->side_ev.push_back(ev2);
         }
         long p_blocks = 0, p_places = 0;
-        bool can_persist = persist_shape(p->host.data(), n_cliques, p->max_n, p->max_D, K, H, L, &p_blocks, &p_places) && p->chunk > (p->val.empty() ? 1 : 2);
+        bool can_persist = persist_shape(p->prob, &p_blocks, &p_places) && p->chunk > (p->val.empty() ? 1 : 2);
         // probe before persisting (device_is_quiet): is the device ours right now?  (outside the capture below)
         // (not while a hand-stepped conveyor of this process fills the machine -- slam.ReplicaNFiSAM creates plans by the hundred
         //  next to one: the probe's blocks would queue behind its chunks, and no run takes the persistent graph then anyway)
@@ -1296,16 +1325,18 @@ static int plan_create_impl(const nfisam_clique* host_cliques, const nfisam_cliq
         const int ch = persist ? 1 : chains;
         if (e == hipSuccess) e = hipStreamBeginCapture(p->cap, hipStreamCaptureModeThreadLocal);
         if (e == hipSuccess) {
-            const nfisam_clique* single = (p->dev == nullptr) ? p->host.data() : nullptr;
             for (int g = 1; g < ch && e == hipSuccess; ++g) {      // fork
                 e = hipEventRecord(p->ev, p->cap);
                 if (e == hipSuccess) e = hipStreamWaitEvent(p->side[g - 1], p->ev, 0);
             }
             if (!p->val.empty()) status = enqueue_validated_period(p, p->cap, persist);
             for (int it = 0; p->val.empty() && it < (persist ? 1 : p->chunk) && status == NFISAM_OK && e == hipSuccess; ++it)
-                for (int g = 0; g < ch && status == NFISAM_OK; ++g)
-                    status = enqueue_step(p->dev, single, n_cliques, p->max_n, p->max_D, K, H, B, L, &p->cfg, it,
-                                          g == 0 ? p->cap : p->side[g - 1], p->host.data(), g, ch, persist ? p->chunk : 0);
+                for (int g = 0; g < ch && status == NFISAM_OK; ++g) {
+                    GradLaunch gl = persist ? persistent_chunk(p->chunk) : at_iteration(it);
+                    gl.chain = g;
+                    gl.n_chains = ch;
+                    status = enqueue_step(p->prob, &p->cfg, gl, g == 0 ? p->cap : p->side[g - 1]);
+                }
             for (int g = 1; g < ch && e == hipSuccess; ++g) {      // join
                 e = hipEventRecord(p->side_ev[g - 1], p->side[g - 1]);
                 if (e == hipSuccess) e = hipStreamWaitEvent(p->cap, p->side_ev[g - 1], 0);
@@ -1315,13 +1346,12 @@ static int plan_create_impl(const nfisam_clique* host_cliques, const nfisam_cliq
             //  events recorded INSIDE a captured graph cannot be asked for their elapsed time)
             const bool split_end = persist && p->evk0 != nullptr && p->val.empty();
             if (status == NFISAM_OK && e == hipSuccess && p->val.empty() && !split_end)
-                status = enqueue_chunk_end(p->dev, single, n_cliques, p->max_n, p->max_D, K, H, L, &p->cfg, p->chunk,
-                                           p->cap, p->hst_dev, persist);
+                status = enqueue_chunk_end(p->prob, &p->cfg, p->chunk, p->cap, p->hst_dev, persist);
             e = hipStreamEndCapture(p->cap, graph_out);
             if (split_end && e == hipSuccess && status == NFISAM_OK) {
                 e = hipStreamBeginCapture(p->cap, hipStreamCaptureModeThreadLocal);
                 if (e == hipSuccess) {
-                    status = enqueue_chunk_end(p->dev, single, n_cliques, p->max_n, p->max_D, K, H, L, &p->cfg, p->chunk, p->cap, p->hst_dev, true);
+                    status = enqueue_chunk_end(p->prob, &p->cfg, p->chunk, p->cap, p->hst_dev, true);
                     e = hipStreamEndCapture(p->cap, &p->graph_end);
                 }
                 if (e == hipSuccess && status == NFISAM_OK) e = hipGraphInstantiate(&p->exec_end, p->graph_end, nullptr, nullptr, 0);
@@ -1348,25 +1378,25 @@ static int plan_create_impl(const nfisam_clique* host_cliques, const nfisam_cliq
         const char* span_env = getenv("NFISAM_SPAN");
         const bool span_on = (span_env != nullptr && span_env[0] == '1') || (use_graph & 4) != 0;      // (bit 2 of use_graph: the caller wants nfisam_nsf_train_plan_launch_async)
         p->span_run = span_env != nullptr && span_env[0] == '1';
-        if (span_on && p->exec_p != nullptr && n_cliques == 1 && p->val.empty() && L == 1 && (use_graph & 2) == 0 && p->max_D <= SPAN_MAX_D &&
+        if (span_on && p->exec_p != nullptr && n_cliques == 1 && p->val.empty() && L == 1 && (use_graph & 2) == 0 && p->prob.max_D <= SPAN_MAX_D &&
             cfg->max_iters > p->chunk && cfg->average_window > 0) {
-            const nfisam_clique* single = (p->dev == nullptr) ? p->host.data() : nullptr;
             hipError_t es = hipStreamBeginCapture(p->cap, hipStreamCaptureModeThreadLocal);
             int ss = NFISAM_ERR_LAUNCH;
             if (es == hipSuccess) {
-                ss = enqueue_grad(p->dev, single, n_cliques, p->max_n, p->max_D, K, H, B, L, p->cfg.max_iters, 0, p->cap, &p->cfg, p->host.data(),
-                                  0, 1, false, p->cfg.max_iters, p->chunk, p->hst_dev);
+                const TrainShape sh = train_shape(p->prob);
+                GradLaunch gl = persistent_chunk(p->cfg.max_iters);      // the whole budget in one launch ...
+                gl.max_iters = p->cfg.max_iters;
+                gl.fused_cfg = &p->cfg;
+                gl.span_window = p->chunk;                               // ... that closes every window itself
+                gl.span_mirror = p->hst_dev;
+                ss = enqueue_grad(p->prob, sh, gl, p->cap);
                 if (ss == NFISAM_OK) {
                     AdamArgs ad;
-                    fill_adam_args(ad, p->dev, single, n_cliques, p->max_n, p->max_D, K, H, L, &p->cfg);
+                    fill_adam_args(ad, p->prob, sh, &p->cfg);
                     ad.close_chunk = p->chunk;
                     ad.span = 1;
                     ad.mirror = p->hst_dev;
-                    const size_t Pmax = (size_t)L * kcount(p->max_D, K, H);
-                    ad.few_copies = ((p->max_n + ad.slab - 1) / ad.slab <= 8) ? 1 : 0;
-                    int ablocks = ad.few_copies ? (int)((Pmax + 255) / 256) : (int)((Pmax + 31) / 32);
-                    if (ablocks < 1) ablocks = 1;
-                    if (ablocks > 1024) ablocks = 1024;
+                    const int ablocks = adam_blocks(p->prob, ad, true);
                     hipLaunchKernelGGL(nsf_adam_kernel, dim3(ablocks, n_cliques), dim3(256), 0, p->cap, ad);
                     hipLaunchKernelGGL(nsf_span_close_kernel, dim3(n_cliques), dim3(64), 0, p->cap, ad);
                     if (hipGetLastError() != hipSuccess) ss = NFISAM_ERR_LAUNCH;
@@ -1375,7 +1405,7 @@ static int plan_create_impl(const nfisam_clique* host_cliques, const nfisam_cliq
             }
             if (es == hipSuccess && ss == NFISAM_OK) es = hipGraphInstantiate(&p->exec_s, p->graph_s, nullptr, nullptr, 0);
             if (getenv("NFISAM_SPAN_DEBUG") != nullptr)
-                fprintf(stderr, "nfisam: window-spanning graph of a plan (n %d, D %d, chunk %d, max_iters %d): capture %d, launcher %d\n", p->max_n, p->max_D,
+                fprintf(stderr, "nfisam: window-spanning graph of a plan (n %d, D %d, chunk %d, max_iters %d): capture %d, launcher %d\n", p->prob.max_n, p->prob.max_D,
                         p->chunk, (int)cfg->max_iters, (int)es, ss);
             if (es != hipSuccess || ss != NFISAM_OK) {             // (not an error of the plan: it keeps to one launch per chunk)
                 if (p->exec_s) { (void)hipGraphExecDestroy(p->exec_s); p->exec_s = nullptr; }
@@ -1389,34 +1419,33 @@ static int plan_create_impl(const nfisam_clique* host_cliques, const nfisam_cliq
 }
 
 static int enqueue_validated_period(const nfisam_train_plan* p, hipStream_t s, bool persist) {
-    const nfisam_clique* single = (p->dev == nullptr) ? p->host.data() : nullptr;
     const int head = p->chunk - 1;                              // iterations in front of the evaluation
     int rc = NFISAM_OK;
     if (head > 0) {
         if (persist && head > 1) {
-            rc = enqueue_step(p->dev, single, p->n_cliques, p->max_n, p->max_D, p->K, p->H, p->B, p->L, &p->cfg, 0, s, p->host.data(), 0, 1, head);
+            rc = enqueue_step(p->prob, &p->cfg, persistent_chunk(head), s);
         } else {
             for (int it = 0; it < head && rc == NFISAM_OK; ++it)
-                rc = enqueue_step(p->dev, single, p->n_cliques, p->max_n, p->max_D, p->K, p->H, p->B, p->L, &p->cfg, it, s, p->host.data());
+                rc = enqueue_step(p->prob, &p->cfg, at_iteration(it), s);
         }
         if (rc == NFISAM_OK)
-            rc = enqueue_chunk_end(p->dev, single, p->n_cliques, p->max_n, p->max_D, p->K, p->H, p->L, &p->cfg, head, s, nullptr, persist && head > 1);
+            rc = enqueue_chunk_end(p->prob, &p->cfg, head, s, nullptr, persist && head > 1);
         if (rc) return rc;
     }
-    const NsfUnitOps* ops = find_ops(p->K, p->H);
+    const NsfUnitOps* ops = find_ops(p->prob.K, p->prob.H);
     if (ops == nullptr) return NFISAM_ERR_ARG;
-    for (int c = 0; c < p->n_cliques; ++c) {
+    for (int c = 0; c < p->prob.n_cliques; ++c) {
         const nfisam_clique& q = p->host[c];
         const nfisam_validation& v = p->val[(size_t)c];
-        rc = ops->forward(v.x_val, q.kparams, v.n_val, q.D, p->B, p->L, 0, nullptr, nullptr, v.logprob, s);
+        rc = ops->forward(v.x_val, q.kparams, v.n_val, q.D, p->prob.B, p->prob.L, 0, nullptr, nullptr, v.logprob, s);
         if (rc) return rc;
         hipLaunchKernelGGL(nsf_validate_kernel, dim3(1), dim3(256), 0, s, (const float*)v.logprob, (int)v.n_val, q.state, p->val_rate,
                            (int)p->cfg.max_iters, p->chunk, v.val_loss);
         HIP_TRY(hipGetLastError());
     }
-    rc = enqueue_step(p->dev, single, p->n_cliques, p->max_n, p->max_D, p->K, p->H, p->B, p->L, &p->cfg, 0, s, p->host.data());
+    rc = enqueue_step(p->prob, &p->cfg, at_iteration(0), s);
     if (rc) return rc;
-    return enqueue_chunk_end(p->dev, single, p->n_cliques, p->max_n, p->max_D, p->K, p->H, p->L, &p->cfg, 1, s, p->hst_dev);
+    return enqueue_chunk_end(p->prob, &p->cfg, 1, s, p->hst_dev);
 }
 
 // Waits until the bookkeeping kernel of chunk number `k` (1-based, this run) has written every clique's mirror.  The
@@ -1434,7 +1463,7 @@ static int wait_chunk(const nfisam_train_plan* p, int k, hipStream_t work, bool*
     double t0 = 0.0, last_query = 0.0;
     for (long looks = 0;; ++looks) {
         bool all = true;
-        for (int c = 0; c < p->n_cliques; ++c)
+        for (int c = 0; c < p->prob.n_cliques; ++c)
             if (m[c].reserved[0] < k) { all = false; break; }
         if (all) break;
         if (looks < 256) { __builtin_ia32_pause(); continue; }         // (~10 us before the first clock read)
@@ -1481,7 +1510,6 @@ extern "C" int nfisam_nsf_train_plan_run(nfisam_train_plan* p, int32_t* iters_ru
     }
     hipStream_t user = (hipStream_t)stream;
     hipStream_t work = user;
-    const nfisam_clique* single = (p->dev == nullptr) ? p->host.data() : nullptr;
     // The chunks' graphs were captured on the plan's private stream; they are REPLAYED on the caller's own stream (round 4:
     // two event record / wait pairs per run, ~12 us of a 20-iteration plan's 330, bought nothing -- a graph may be launched into
     // any stream, the legacy null stream included; NFISAM_PLAN_STREAM=private restores the hand-over).
@@ -1519,7 +1547,7 @@ extern "C" int nfisam_nsf_train_plan_run(nfisam_train_plan* p, int32_t* iters_ru
     // Nothing of an earlier run writes the mirror any more: its last closed chunk was waited for, and a chunk enqueued
     // ahead of an early stop only republishes the final state, so restarting the sequence needs that chunk drained.
     if (p->ahead) { HIP_TRY(hipStreamSynchronize(work)); p->ahead = false; }
-    for (int c = 0; c < p->n_cliques; ++c) p->hst[c].reserved[0] = 0;
+    for (int c = 0; c < p->prob.n_cliques; ++c) p->hst[c].reserved[0] = 0;
     __atomic_thread_fence(__ATOMIC_RELEASE);
     const int total_chunks = (p->cfg.max_iters + p->chunk - 1) / p->chunk;
     int launched = 0, closed = 0, status = NFISAM_OK;
@@ -1547,9 +1575,8 @@ extern "C" int nfisam_nsf_train_plan_run(nfisam_train_plan* p, int32_t* iters_ru
             // chunk (up to 2 x 128 kernels) stays a graph.
             static const bool direct = !(getenv("NFISAM_PERSIST_DIRECT") != nullptr && getenv("NFISAM_PERSIST_DIRECT")[0] == '0');
             if (direct && persist && p->val.empty()) {
-                int rc = enqueue_step(p->dev, single, p->n_cliques, p->max_n, p->max_D, p->K, p->H, p->B, p->L, &p->cfg, 0, work, p->host.data(), 0, 1, p->chunk);
-                if (rc == NFISAM_OK)
-                    rc = enqueue_chunk_end(p->dev, single, p->n_cliques, p->max_n, p->max_D, p->K, p->H, p->L, &p->cfg, p->chunk, work, p->hst_dev, true);
+                int rc = enqueue_step(p->prob, &p->cfg, persistent_chunk(p->chunk), work);
+                if (rc == NFISAM_OK) rc = enqueue_chunk_end(p->prob, &p->cfg, p->chunk, work, p->hst_dev, true);
                 if (rc) return rc;
             } else {
                 const hipError_t e = hipGraphLaunch(exec, work);
@@ -1560,12 +1587,10 @@ extern "C" int nfisam_nsf_train_plan_run(nfisam_train_plan* p, int32_t* iters_ru
             if (rcv) return rcv;
         } else {
             for (int it = 0; it < todo; ++it) {
-                int rc = enqueue_step(p->dev, single, p->n_cliques, p->max_n, p->max_D, p->K, p->H, p->B, p->L,
-                                      &p->cfg, it, work, p->host.data());
+                int rc = enqueue_step(p->prob, &p->cfg, at_iteration(it), work);
                 if (rc) return rc;
             }
-            int rcb = enqueue_chunk_end(p->dev, single, p->n_cliques, p->max_n, p->max_D, p->K, p->H, p->L, &p->cfg,
-                                        todo, work, p->hst_dev);
+            int rcb = enqueue_chunk_end(p->prob, &p->cfg, todo, work, p->hst_dev);
             if (rcb) return rcb;
         }
         ++launched;
@@ -1588,7 +1613,7 @@ extern "C" int nfisam_nsf_train_plan_run(nfisam_train_plan* p, int32_t* iters_ru
         if (rc) return fail(rc);
         ++closed;
         bool all_stopped = true;
-        for (int c = 0; c < p->n_cliques; ++c) {
+        for (int c = 0; c < p->prob.n_cliques; ++c) {
             if ((p->hst[c].domain_err & NFISAM_STATE_STALLED) != 0) {          // a group barrier of a persistent chunk timed out
                 status = NFISAM_ERR_STALL;
                 if (!g_persist_broken.exchange(true))
@@ -1608,7 +1633,7 @@ extern "C" int nfisam_nsf_train_plan_run(nfisam_train_plan* p, int32_t* iters_ru
     p->ahead = closed < launched || span;      // an enqueued chunk behind the stop: empty launches still draining on `work` (span: its closing kernels)
     if (total_chunks == 0) {           // max_iters = 0: report the state as it is
         HIP_TRY(hipMemcpyAsync(p->hst, p->host[0].state, sizeof(nfisam_train_state), hipMemcpyDeviceToHost, work));
-        for (int c = 1; c < p->n_cliques; ++c)
+        for (int c = 1; c < p->prob.n_cliques; ++c)
             HIP_TRY(hipMemcpyAsync(&p->hst[c], p->host[c].state, sizeof(nfisam_train_state), hipMemcpyDeviceToHost, work));
         HIP_TRY(hipStreamSynchronize(work));
     }
@@ -1616,7 +1641,7 @@ extern "C" int nfisam_nsf_train_plan_run(nfisam_train_plan* p, int32_t* iters_ru
         HIP_TRY(hipEventRecord(p->ev, work));
         HIP_TRY(hipStreamWaitEvent(user, p->ev, 0));
     }
-    if (iters_run != nullptr) for (int c = 0; c < p->n_cliques; ++c) iters_run[c] = p->hst[c].step;
+    if (iters_run != nullptr) for (int c = 0; c < p->prob.n_cliques; ++c) iters_run[c] = p->hst[c].step;
     return status;
 }
 
@@ -1637,7 +1662,7 @@ extern "C" int nfisam_nsf_train_plan_xcd_span(const nfisam_train_plan* p) {
     if (p == nullptr || p->hst == nullptr) return -1;
     int span = 0;
     const volatile nfisam_train_state* m = p->hst;
-    for (int c = 0; c < p->n_cliques; ++c) span = m[c].reserved[1] > span ? m[c].reserved[1] : span;
+    for (int c = 0; c < p->prob.n_cliques; ++c) span = m[c].reserved[1] > span ? m[c].reserved[1] : span;
     return span;
 }
 
@@ -1660,7 +1685,7 @@ extern "C" int nfisam_nsf_train_plan_begin(nfisam_train_plan* p, nfisam_stream_t
         HIP_TRY(hipStreamSynchronize(p->cap));
         p->ahead = false;
     }
-    for (int c = 0; c < p->n_cliques; ++c) p->hst[c].reserved[0] = 0;
+    for (int c = 0; c < p->prob.n_cliques; ++c) p->hst[c].reserved[0] = 0;
     __atomic_thread_fence(__ATOMIC_RELEASE);
     p->enqueued.store(0);
     p->refills.store(0);
@@ -1689,7 +1714,7 @@ static void feeder_main(nfisam_train_plan* p) {
             const long closed = m[0].reserved[0];
             // a chunk is worth launching while some slot trains: as of the last closed chunk, or refilled since the last launch
             bool work = p->refills.load() > 0;
-            for (int c = 0; c < p->n_cliques && !work; ++c) work = (m[c].stop == 0 && m[c].step < p->cfg.max_iters);
+            for (int c = 0; c < p->prob.n_cliques && !work; ++c) work = (m[c].stop == 0 && m[c].step < p->cfg.max_iters);
             if (work && p->enqueued.load() - closed < depth) {
                 p->feed_busy.store(1);
                 if (p->feed_depth.load() > 0) {          // (a pause that arrived meanwhile wins)
@@ -1719,20 +1744,20 @@ extern "C" long nfisam_nsf_train_plan_enqueued(const nfisam_train_plan* p) { ret
 // `stream`), moments / workspace / loss record and -- last -- the state zeroed, all on the plan's stream, i.e. between chunks.
 extern "C" int nfisam_nsf_train_plan_refill(nfisam_train_plan* p, int c, const float* x, const float* kparams,
                                             nfisam_stream_t stream) {
-    if (p == nullptr || p->exec == nullptr || c < 0 || c >= p->n_cliques || x == nullptr || kparams == nullptr) return NFISAM_ERR_ARG;
+    if (p == nullptr || p->exec == nullptr || c < 0 || c >= p->prob.n_cliques || x == nullptr || kparams == nullptr) return NFISAM_ERR_ARG;
     const nfisam_clique& q = p->host[(size_t)c];
     std::lock_guard<std::mutex> lk(p->enqueue_mu);
     // (the slot's own event: p->ev belongs to begin / end)
-    if (p->slot_ev.size() != (size_t)p->n_cliques) p->slot_ev.assign((size_t)p->n_cliques, nullptr);
+    if (p->slot_ev.size() != (size_t)p->prob.n_cliques) p->slot_ev.assign((size_t)p->prob.n_cliques, nullptr);
     if (p->slot_ev[(size_t)c] == nullptr) HIP_TRY(hipEventCreateWithFlags(&p->slot_ev[(size_t)c], hipEventDisableTiming));
     HIP_TRY(hipEventRecord(p->slot_ev[(size_t)c], (hipStream_t)stream));
     HIP_TRY(hipStreamWaitEvent(p->cap, p->slot_ev[(size_t)c], 0));
-    const size_t pk = (size_t)p->L * kcount(q.D, p->K, p->H) * sizeof(float);
+    const size_t pk = (size_t)p->prob.L * kcount(q.D, p->prob.K, p->prob.H) * sizeof(float);
     HIP_TRY(hipMemcpyAsync((void*)q.x, x, (size_t)q.n * q.D * sizeof(float), hipMemcpyDeviceToDevice, p->cap));
     HIP_TRY(hipMemcpyAsync(q.kparams, kparams, pk, hipMemcpyDeviceToDevice, p->cap));
     HIP_TRY(hipMemsetAsync(q.adam_m, 0, pk, p->cap));
     HIP_TRY(hipMemsetAsync(q.adam_v, 0, pk, p->cap));
-    HIP_TRY(hipMemsetAsync(q.kgrad, 0, nfisam_nsf_grad_workspace_count(p->max_n, q.D, p->K, p->H, p->L) * sizeof(float), p->cap));
+    HIP_TRY(hipMemsetAsync(q.kgrad, 0, nfisam_nsf_grad_workspace_count(p->prob.max_n, q.D, p->prob.K, p->prob.H, p->prob.L) * sizeof(float), p->cap));
     HIP_TRY(hipMemsetAsync(q.iter_loss, 0, (size_t)(p->cfg.max_iters > 0 ? p->cfg.max_iters : 1) * sizeof(float), p->cap));
     HIP_TRY(hipMemsetAsync(q.state, 0, sizeof(nfisam_train_state), p->cap));
     p->refills.fetch_add(1);
@@ -1742,7 +1767,7 @@ extern "C" int nfisam_nsf_train_plan_peek(const nfisam_train_plan* p, nfisam_tra
     if (p == nullptr || out == nullptr) return NFISAM_ERR_ARG;
     if (p->feed_error.load() != 0) { nfisam_g_last_hip_error = p->feed_error.load(); return NFISAM_ERR_LAUNCH; }   // the feeder's launch failed
     const volatile nfisam_train_state* m = p->hst;
-    for (int c = 0; c < p->n_cliques; ++c) {
+    for (int c = 0; c < p->prob.n_cliques; ++c) {
         // the sequence word is written last (system-scope release): read it first, the state behind an acquire fence, and
         // again -- a chunk closing in between gives a torn copy that the next look repairs, so it is reported as not closed
         const int s0 = m[c].reserved[0];

@@ -3578,14 +3578,22 @@ static int unit_density(const nfisam_post_clique* table, int n_cliques, const in
     return NFISAM_OK;
 }
 
-template <int KK, int HH, bool MF, bool WL, int OCC>
-static int launch_train_variant(const TrainArgs& a, int n_cliques, int max_n, int W, int groups, size_t lds, hipStream_t s) {
-    int rc = set_lds(nsf_train_kernel<KK, HH, MF, WL, OCC>, lds);
-    if (rc) return rc;
-    const int T = a.tiles_per_block > 1 ? a.tiles_per_block : 1;
-    hipLaunchKernelGGL((nsf_train_kernel<KK, HH, MF, WL, OCC>), dim3((max_n + TILE * T - 1) / (TILE * T), n_cliques, groups),
-                       dim3(64 * W), lds, s, a);
-    return NFISAM_OK;
+// The tile-major kernels (nsf_train_kernel, nsf_train2_kernel) take the launch's arguments alone: one pointer type, so a launcher
+// picks its instantiation once and sets the LDS attribute on the kernel it launches.
+using TrainKernel = void (*)(TrainArgs);
+// nsf_train_kernel of one (K, H): MFMA weight gradients (hidden_dim 8 only: use_mfma_grad) x LDS copy of the parameters
+template <int KK, int HH>
+static TrainKernel train_kernel_of(bool mf, bool wl) {
+    if (mf) {
+        if constexpr (HH == 8) {
+            if (wl) return nsf_train_kernel<KK, HH, true, true, 1>;
+            return nsf_train_kernel<KK, HH, true, false, 1>;
+        } else {
+            return nullptr;
+        }
+    }
+    if (wl) return nsf_train_kernel<KK, HH, false, true, 1>;
+    return nsf_train_kernel<KK, HH, false, false, 1>;
 }
 
 // parameter floats one block must hold: all layers, or (dims spread over grid.z) its own dims' blocks
@@ -3637,8 +3645,6 @@ static size_t pair_kernel_lds(int L, int max_D) {
         const int W = ((max_D + 1) / 2 < 8) ? (max_D + 1) / 2 : 8;
         const size_t fl = (size_t)pair_tile_floats(L, max_D, 1) + (size_t)W * pair_wave_floats<16>() + (size_t)max_D * PairPanel<KK, HH>::floats(max_D);
         return fl * sizeof(float) <= 160 * 1024 ? fl * sizeof(float) : 0;
-    } else if constexpr (HH != 8 && HH != 4) {
-        return 0;
     } else {
         // Narrow cliques stay with nsf_train2_kernel: up to four dims are one wave per SIMD there too, and its units get
         // cheaper with the dim (measured, us per iteration split / pair: D 3, L 4: 28.8 / 30.6; D 4: 30.8 / 31.3; D 5: 33.9 /
@@ -3654,47 +3660,40 @@ static size_t pair_kernel_lds(int L, int max_D) {
 }
 template <int KK, int HH>
 static int unit_pair_map(const uint32_t** map, uint32_t* offsets) {
-    if constexpr (HH != 8 && HH != 4 && HH != 16) {
-        return NFISAM_ERR_ARG;
-    } else {
-        PairMapOffsets o;
-        const int rc = PairMap<KK, HH>::get(map, &o);
-        if (rc == NFISAM_OK && offsets != nullptr) memcpy(offsets, o.at, sizeof(o.at));
-        return rc;
-    }
+    PairMapOffsets o;
+    const int rc = PairMap<KK, HH>::get(map, &o);
+    if (rc == NFISAM_OK && offsets != nullptr) memcpy(offsets, o.at, sizeof(o.at));
+    return rc;
 }
 
 template <int KK, int HH>
 static int unit_train2(TrainArgs a, int n_cliques, int max_n, int max_D, hipStream_t s) {
-    if constexpr (HH != 8 && HH != 4 && HH != 16) {
-        return NFISAM_ERR_ARG;
-    } else {
-        const long tiles = (long)((max_n + TILE2 - 1) / TILE2) * n_cliques;
-        if (!(a.L == 1 && a.gx == nullptr)) {
-            // layers / dL/dx couple the dims of a tile: two dims per wave on the MFMA conditioner (nsf_train3_kernel)
-            const size_t lds3 = pair_kernel_lds<KK, HH>(a.L, max_D);
-            if (lds3 > 0) {
-                const uint32_t* map = nullptr;
-                PairMapOffsets offs;
-                int rc = PairMap<KK, HH>::get(&map, &offs);
-                if (rc) return rc;
-                a.g_tiles = 1;
-                a.xrows = max_D;
-                {
-                    const char* se = getenv("NFISAM_PAIR_STASH");
-                    a.pair_stash = ((HH != 16 || KK <= 11) && a.pair_ws && a.L > 1 && pair_stash_fits(max_n, max_D) && !(se != nullptr && se[0] == '0')) ? 1 : 0;
-                }
-                const int W = ((max_D + 1) / 2 < 8) ? (max_D + 1) / 2 : 8;
-                rc = set_lds(nsf_train3_kernel<KK, HH>, lds3);
-                if (rc) return rc;
-                hipLaunchKernelGGL((nsf_train3_kernel<KK, HH>), dim3((max_n + TILE2 - 1) / TILE2, n_cliques), dim3(64 * W), lds3, s, a, map, offs);
-                HIP_TRY(hipGetLastError());
-                return NFISAM_OK;
+    const long tiles = (long)((max_n + TILE2 - 1) / TILE2) * n_cliques;
+    if (!(a.L == 1 && a.gx == nullptr)) {
+        // layers / dL/dx couple the dims of a tile: two dims per wave on the MFMA conditioner (nsf_train3_kernel)
+        const size_t lds3 = pair_kernel_lds<KK, HH>(a.L, max_D);
+        if (lds3 > 0) {
+            const uint32_t* map = nullptr;
+            PairMapOffsets offs;
+            int rc = PairMap<KK, HH>::get(&map, &offs);
+            if (rc) return rc;
+            a.g_tiles = 1;
+            a.xrows = max_D;
+            {
+                const char* se = getenv("NFISAM_PAIR_STASH");
+                a.pair_stash = ((HH != 16 || KK <= 11) && a.pair_ws && a.L > 1 && pair_stash_fits(max_n, max_D) && !(se != nullptr && se[0] == '0')) ? 1 : 0;
             }
+            const int W = ((max_D + 1) / 2 < 8) ? (max_D + 1) / 2 : 8;
+            rc = set_lds(nsf_train3_kernel<KK, HH>, lds3);
+            if (rc) return rc;
+            hipLaunchKernelGGL((nsf_train3_kernel<KK, HH>), dim3((max_n + TILE2 - 1) / TILE2, n_cliques), dim3(64 * W), lds3, s, a, map, offs);
+            HIP_TRY(hipGetLastError());
+            return NFISAM_OK;
         }
-        if constexpr (HH != 8) {
-            return NFISAM_ERR_ARG;                             // (train_tile sends hidden_dim 4 here only when the pair kernel takes the launch)
-        } else {
+    }
+    if constexpr (HH != 8) {
+        return NFISAM_ERR_ARG;                             // (train_tile sends hidden_dim 4 / 16 here only when the pair kernel takes the launch)
+    } else {
         // L == 1 and no dL/dx requested: the dims of a tile never exchange data, so a small (latency-bound) launch
         // turns every (tile, dim) unit into its own single-wave block; big batches keep a tile's dims together.
         const bool independent_dims = (a.L == 1 && a.gx == nullptr);
@@ -3713,21 +3712,12 @@ static int unit_train2(TrainArgs a, int n_cliques, int max_n, int max_D, hipStre
         const bool wl = weights_mode() != 0 && (tile_floats + wfloats) * sizeof(float) <= 150 * 1024;
         a.wl_floats = wl ? (int)wfloats : 0;
         const size_t lds = (tile_floats + (wl ? wfloats : 0)) * sizeof(float);
-        int rc;
-        if (wl) {
-            rc = set_lds(nsf_train2_kernel<KK, HH, true>, lds);
-            if (rc) return rc;
-            hipLaunchKernelGGL((nsf_train2_kernel<KK, HH, true>), dim3((max_n + TILE2 - 1) / TILE2, n_cliques, groups), dim3(64 * W),
-                               lds, s, a);
-        } else {
-            rc = set_lds(nsf_train2_kernel<KK, HH, false>, lds);
-            if (rc) return rc;
-            hipLaunchKernelGGL((nsf_train2_kernel<KK, HH, false>), dim3((max_n + TILE2 - 1) / TILE2, n_cliques, groups), dim3(64 * W),
-                               lds, s, a);
-        }
+        const TrainKernel kernel = wl ? nsf_train2_kernel<KK, HH, true> : nsf_train2_kernel<KK, HH, false>;
+        const int rc = set_lds(kernel, lds);
+        if (rc) return rc;
+        hipLaunchKernelGGL(kernel, dim3((max_n + TILE2 - 1) / TILE2, n_cliques, groups), dim3(64 * W), lds, s, a);
         HIP_TRY(hipGetLastError());
         return NFISAM_OK;
-        }
     }
 }
 
@@ -3763,21 +3753,59 @@ template <int KK, int HH> constexpr bool lean_persist_v = HH <= 8 && KK > NSF_PE
 // top of the iteration -- tried and dropped -- and to let the compiler hoist the loop's derivations (nsf_train1_kernel: ROOMY)
 // (... and of every other num_knots at hidden_dim <= 8: the helper waves need a two-wave build)
 template <int KK, int HH> constexpr bool lean_persist_inst_v = HH <= 8;
+// two lanes per particle (nsf_half.h): hidden_dim 8 and sixteen theta columns per half
+template <int KK, int HH> constexpr bool half_kh_v = (HH == 8 && hp_of(KK) == 16);
+
+// The dim-major kernels of one (K, H): every instantiation of nsf_train1_kernel / nsf_train1_plain_kernel has the same
+// parameter list, so ONE function maps a launch's variant to its kernel -- the launcher and the occupancy questions
+// (lean_launch_fits, unit_persist_places) take it from here and cannot disagree.  nullptr: the pair has no such build.
+using Train1Kernel = void (*)(const nfisam_clique*, const uint32_t*, unsigned, int, int, int, int, TrainArgs, Train1Few);
+struct Train1Variant {
+    bool persist;      // chunk-persistent form (else one iteration per launch)
+    bool lean;         // the two-waves-per-SIMD build of the pairs whose three-wave build spills
+    bool wide;         // persist only: groups of 9 .. 16 blocks
+    bool spl;          // two lanes per particle
+};
+template <int KK, int HH>
+static Train1Kernel train1_kernel_of(Train1Variant v) {
+    if (v.wide && !v.persist) return nullptr;
+    if (v.spl) {
+        // (the one-launch-per-iteration twin is the same template with PERSIST = false: the same arithmetic in the same order)
+        if constexpr (half_kh_v<KK, HH>) {
+            if (v.lean) return nullptr;
+            if (v.persist && v.wide) return nsf_train1_kernel<KK, HH, true, false, true, true>;
+            if (v.persist) return nsf_train1_kernel<KK, HH, true, false, false, true>;
+            return nsf_train1_kernel<KK, HH, false, false, false, true>;
+        } else {
+            return nullptr;
+        }
+    }
+    if (v.persist && v.wide) {
+        if (!v.lean) return nsf_train1_kernel<KK, HH, true, false, true>;
+        if constexpr (lean_persist_inst_v<KK, HH>) return nsf_train1_kernel<KK, HH, true, true, true>;
+        else return nullptr;
+    }
+    if (v.persist) {
+        if (!v.lean) return nsf_train1_kernel<KK, HH, true>;
+        if constexpr (lean_persist_inst_v<KK, HH>) return nsf_train1_kernel<KK, HH, true, true>;
+        else return nullptr;
+    }
+    if (!v.lean) return nsf_train1_plain_kernel<KK, HH>;
+    if constexpr (lean_plain_v<KK, HH>) return nsf_train1_plain_kernel<KK, HH, true>;
+    else return nullptr;
+}
+
 template <int KK, int HH>
 static int unit_prepare(int max_D) {
-    if constexpr (HH == 8 || HH == 4 || HH == 16) {
-        {
-            const int rc = PairMap<KK, HH>::get(nullptr, nullptr);
-            if (rc) return rc;
-        }
-        // (the occupancy answers the launcher will want: asked here, outside the capture of the plan's graph)
-        (void)device_cus();
-        if constexpr (lean_persist_inst_v<KK, HH>) (void)lean_launch_fits<KK, HH, true>(1, max_D);
-        if constexpr (lean_plain_v<KK, HH>) (void)lean_launch_fits<KK, HH, false>(1, max_D);
-        return max_D <= PANEL_MAP_MAX_D ? PanelMap<KK, HH>::get(max_D, nullptr) : NFISAM_OK;
-    } else {
-        return NFISAM_OK;
+    {
+        const int rc = PairMap<KK, HH>::get(nullptr, nullptr);
+        if (rc) return rc;
     }
+    // (the occupancy answers the launcher will want: asked here, outside the capture of the plan's graph)
+    (void)device_cus();
+    if constexpr (lean_persist_inst_v<KK, HH>) (void)lean_launch_fits<KK, HH, true>(1, max_D);
+    if constexpr (lean_plain_v<KK, HH>) (void)lean_launch_fits<KK, HH, false>(1, max_D);
+    return max_D <= PANEL_MAP_MAX_D ? PanelMap<KK, HH>::get(max_D, nullptr) : NFISAM_OK;
 }
 
 template <int KK, int HH>
@@ -3785,24 +3813,20 @@ static size_t train1_lds_bytes(int max_D, int W, bool persist = false) {
     return ((size_t)PANEL_BASE + CondPanel<KK, HH>::floats(max_D) + ONES_ROW + (size_t)W * train1_wave_floats(max_D, HH) +
             (persist ? (size_t)3 * persist_keep_stride<KK, HH>(max_D) : 0)) * sizeof(float);
 }
-// co-resident blocks of nsf_train1_kernel<K, H, true> on this device (what its registers and LDS allow per CU x CUs)
-// blocks of 256 threads with `lds` bytes of dynamic LDS that the current device holds at once for `kernel`
-template <typename Kern>
-static long resident_blocks(Kern kernel, size_t lds) {
-    if (set_lds(kernel, lds) != NFISAM_OK) return 0;
+// blocks of 256 threads with `lds` bytes of dynamic LDS that the current device holds at once for `kernel` (what its
+// registers and LDS allow per CU x CUs)
+static long resident_blocks(Train1Kernel kernel, size_t lds) {
+    if (kernel == nullptr || set_lds(kernel, lds) != NFISAM_OK) return 0;
     int per_cu = 0, dev = 0;
     hipDeviceProp_t prop;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds) != hipSuccess) return 0;
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
     return (long)per_cu * (long)prop.multiProcessorCount;
 }
+// co-resident blocks of nsf_train1_kernel<K, H, true> on this device
 template <int KK, int HH>
 static long unit_persist_places(int max_D) {
-    if constexpr (HH != 8 && HH != 4 && HH != 16) {
-        return 0;
-    } else {
-        return resident_blocks(nsf_train1_kernel<KK, HH, true>, train1_lds_bytes<KK, HH>(max_D, 4, true));
-    }
+    return resident_blocks(train1_kernel_of<KK, HH>({true, false, false, false}), train1_lds_bytes<KK, HH>(max_D, 4, true));
 }
 // the LEAN instantiations (two waves per SIMD, no scratch) exist for the (K, H) pairs whose three-wave build spills
 // (lean_plain_v / lean_persist_v: declared in front of unit_prepare)
@@ -3827,8 +3851,7 @@ static bool lean_launch_fits(long blocks, int max_D) {
         pl = places[dev][max_D];
     }
     if (pl == 0) {
-        if constexpr (PERSIST) pl = resident_blocks(nsf_train1_kernel<KK, HH, true, true>, train1_lds_bytes<KK, HH>(max_D, 4, true));
-        else pl = resident_blocks(nsf_train1_plain_kernel<KK, HH, true>, train1_lds_bytes<KK, HH>(max_D, 4, false));
+        pl = resident_blocks(train1_kernel_of<KK, HH>({PERSIST, true, false, false}), train1_lds_bytes<KK, HH>(max_D, 4, PERSIST));
         if (pl <= 0) pl = -1;
         std::lock_guard<std::mutex> lk(mu);
         places[dev][max_D] = pl;
@@ -3838,168 +3861,98 @@ static bool lean_launch_fits(long blocks, int max_D) {
 
 template <int KK, int HH>
 static int unit_train1(TrainArgs a, int n_cliques, int max_n, int max_D, hipStream_t s) {
-    if constexpr (HH != 8 && HH != 4 && HH != 16) {
-        return NFISAM_ERR_ARG;
-    } else {
-        // one wave = one dim x T tiles, dim-major blocks (nsf_train1_kernel)
-        const int T = a.tiles_per_block > 1 ? a.tiles_per_block : 1;
-        a.tiles_per_block = T;
-        const int W = a.waves > 0 ? a.waves : dim_major_waves(n_cliques, max_n, max_D, T);
-        if ((T & (T - 1)) != 0 || (W & (W - 1)) != 0 || W > 8 || T > 8) return NFISAM_ERR_ARG;
-        a.t_shift = __builtin_ctz((unsigned)T);
-        a.w_shift = __builtin_ctz((unsigned)W);
-        a.xrows = max_D;
-        // two lanes per particle (nsf_half.h; the shape decision is train_shape's, nsf_kernels.hip): 32 particles per wave
-        constexpr bool half_kh = (HH == 8 && hp_of(KK) == 16);
-        const bool spl = a.half != 0;
-        if (spl && (!half_kh || T != 1 || !a.slab || max_D > 16 || a.L != 1)) return NFISAM_ERR_ARG;
-        const int TP = spl ? 32 : TILE;                       // particles per wave-tile
-        const int waves = (max_n + TP * T - 1) / (TP * T);
-        const int gx = (waves + W - 1) / W;
-        a.n_copies = gx;                                       // one gradient copy per block (a.slab = TP * T * W particles)
-        a.grid_cliques = n_cliques;
-        a.groups = n_cliques * max_D;                          // (clique, dim) groups of gx blocks, padded to the 8 XCDs
-        if ((long)a.groups * (long)n_cliques >= (1L << 31) || gx > 65535 || (a.groups + 7) / 8 > 65535) return NFISAM_ERR_ARG;
-        a.magic_cliques = n_cliques > 1 ? (unsigned)(((1ull << 32) + (unsigned)n_cliques - 1) / (unsigned)n_cliques) : 0u;
-        int rc = PanelMap<KK, HH>::get(max_D, &a.panel_map);
-        if (rc) return rc;
-        const size_t lds = train1_lds_bytes<KK, HH>(max_D, W, a.persist_iters > 0);
-        size_t lds_launch = lds;
-        if (const char* pe = getenv("NFISAM_LDS_PAD_KB")) lds_launch += (size_t)atoi(pe) * 1024;   // experiments: fewer blocks per CU
-        const bool persist = a.persist_iters > 0;
-        if (persist && (T != 1 || !a.slab || !a.fused_adam || a.L != 1 || max_D > FUSED_COUNTERS)) return NFISAM_ERR_ARG;
-        // the (clique, dim, 256 particles) blocks this launch really has
-        long real_blocks = 0;
-        {
-            const nfisam_clique* hc = (a.cliques == nullptr) ? &a.single : a.host_cliques;
-            if (hc != nullptr)
-                for (int c = 0; c < n_cliques; ++c) real_blocks += (long)hc[c].D * ((hc[c].n + W * T * TP - 1) / (W * T * TP));
-            else
-                real_blocks = (long)n_cliques * max_D * gx;
-        }
-        // LEAN build (two waves per SIMD, no scratch: see the kernels' attribute) when the launch is resident at that occupancy anyway
-        bool lean = false;
-        if constexpr (lean_persist_v<KK, HH>) { if (persist && W == 4 && !spl) lean = lean_launch_fits<KK, HH, true>(real_blocks, max_D); }
-        else if constexpr (lean_persist_inst_v<KK, HH>) {
-            static const bool lone_lean = !(getenv("NFISAM_LONE_LEAN") != nullptr && getenv("NFISAM_LONE_LEAN")[0] == '0');
-            if (persist && W == 4 && !spl && lone_lean && real_blocks <= 256) lean = lean_launch_fits<KK, HH, true>(real_blocks, max_D);
-        }
-        if constexpr (lean_plain_v<KK, HH>) { if (!persist && W == 4 && !spl) lean = lean_launch_fits<KK, HH, false>(real_blocks, max_D); }
-        // a window-spanning launch closes its windows in the kernel: that code exists in the two-wave builds (nsf_train1_kernel: ROOMY)
-        if (a.span_window > 0 && !(persist && (spl || lean) && W == 4 && max_D <= SPAN_MAX_D && n_cliques == 1)) return NFISAM_ERR_ARG;
-        const bool wide = persist && gx > 8;                   // groups of 9 .. 16 blocks (n > 2048): the WIDE instantiation
-        // helper waves (round 6): a two-wave build whose blocks get a CU each is launched with eight waves per block -- waves 4 .. 7
-        // own no particles and take part in the staging only (one parameter per thread: stage_cond_panel_persist_solo)
-        static const bool helpers_on = !(getenv("NFISAM_HELPERS") != nullptr && getenv("NFISAM_HELPERS")[0] == '0');
-        // (MI355X: 256 CUs -> at most 224 such blocks, 240 for groups of nine to sixteen.  The dispatcher deals workgroups round-robin to
-        //  the eight XCDs, so what must fit is the busiest XCD's share -- (octets of groups) x (blocks per group), padding included -- into
-        //  its cus / 8 CUs: at most 7/8 of them by default; the sixteen-copy launches of NFISAM_HALF=2 may fill an XCD)
-        const long cus = device_cus();
-        const long per_xcd = (long)((a.groups + 7) / 8) * gx;
-        const bool helpers = helpers_on && persist && (spl || lean || HH == 16) && W == 4 &&      // (hidden_dim 16 compiles to two waves per SIMD anyway)
-                             real_blocks <= (wide ? cus - cus / 16 : cus - cus / 8) &&
-                             per_xcd <= (wide ? cus / 8 : cus / 8 - cus / 64);       // (also the window-spanning launch: the in-kernel bookkeeping's work is its first four waves')
-        const int BW = helpers ? 2 * W : W;                    // waves per block
-        if (persist && gx > PERSIST_MAX_COPIES) return NFISAM_ERR_ARG;
-        if constexpr (half_kh) {
-            if (spl) {
-                // (the one-launch-per-iteration twin is the same template with PERSIST = false: the same arithmetic in the same order)
-                if (persist && wide) rc = set_lds(nsf_train1_kernel<KK, HH, true, false, true, true>, lds_launch);
-                else if (persist) rc = set_lds(nsf_train1_kernel<KK, HH, true, false, false, true>, lds_launch);
-                else rc = set_lds(nsf_train1_kernel<KK, HH, false, false, false, true>, lds_launch);
-                if (rc) return rc;
-            }
-        }
-        if (spl) {
-        } else if (persist && wide) {
-            rc = set_lds(nsf_train1_kernel<KK, HH, true, false, true>, lds_launch);
-            if constexpr (lean_persist_inst_v<KK, HH>) { if (lean) rc = set_lds(nsf_train1_kernel<KK, HH, true, true, true>, lds_launch); }
-        } else if (persist) {
-            rc = set_lds(nsf_train1_kernel<KK, HH, true>, lds_launch);
-            if constexpr (lean_persist_inst_v<KK, HH>) { if (lean) rc = set_lds(nsf_train1_kernel<KK, HH, true, true>, lds_launch); }
-        } else {
-            rc = set_lds(nsf_train1_plain_kernel<KK, HH>, lds_launch);
-            if constexpr (lean_plain_v<KK, HH>) { if (lean) rc = set_lds(nsf_train1_plain_kernel<KK, HH, true>, lds_launch); }
-        }
-        if (rc) return rc;
-        // few cliques: their descriptors travel in the kernel arguments (host copy: the plan's, or the single one)
-        static_assert(offsetof(Train1Head, shifts) == 32 && sizeof(Train1Head) == 40, "scalar head of the kernel arguments");
-        Train1Few few;
-        memset(&few, 0, sizeof(few));
-        const nfisam_clique* dev = a.cliques;
-        const nfisam_clique* host = (a.cliques == nullptr) ? &a.single : a.host_cliques;
-        if (host != nullptr && n_cliques <= TRAIN1_KERNARG_CLIQUES) {
-            memcpy(few.c, host, sizeof(nfisam_clique) * (size_t)n_cliques);
-            dev = nullptr;
-        } else if (dev == nullptr) {
-            return NFISAM_ERR_ARG;
-        }
-        const int nch = a.n_chains > 1 ? a.n_chains : 1, ch = a.n_chains > 1 ? a.chain : 0;
-        const int octets = (a.groups + 7) / 8;
-        const int gz = (octets - ch + nch - 1) / nch;          // octets ch, ch + nch, ...
-        if (nch > 255 || ch < 0 || ch >= nch) return NFISAM_ERR_ARG;
-        {   // contended launches (more than one block per CU: several waves share a SIMD) divide the Adam update among a group's blocks
-            static const char* se = getenv("NFISAM_PERSIST_SPLIT");
-            long blocks = 0;
-            const nfisam_clique* hc = (a.cliques == nullptr) ? &a.single : a.host_cliques;
-            for (int c = 0; c < n_cliques && hc != nullptr; ++c) blocks += (long)hc[c].D * ((hc[c].n + W * TP - 1) / (W * TP));
-            a.persist_split = (se != nullptr) ? (se[0] == '1') : (blocks > 256);
-        }
-        static const int spin_log2 = getenv("NFISAM_PERSIST_SPINS") != nullptr ? atoi(getenv("NFISAM_PERSIST_SPINS")) : 15;           // (~1 us per look: a member that never arrives costs tens of milliseconds, not seconds -- round 4: 22)
-        a.persist_spins = spin_log2 < 1 ? 1 : (spin_log2 > 30 ? 30 : spin_log2);
-        static const bool drop = getenv("NFISAM_PERSIST_DROP") != nullptr && getenv("NFISAM_PERSIST_DROP")[0] == '1';                  // (test knob)
-        static const bool scatter = getenv("NFISAM_PERSIST_SCATTER") != nullptr && getenv("NFISAM_PERSIST_SCATTER")[0] == '1';   // (test knob)
-        const int pshifts = a.t_shift | (scatter ? 0x80 : 0) | (drop ? 0x40 : 0) | (a.w_shift << 8) | (ch << 16) | (nch << 24);
-        const int shifts = a.t_shift | (a.w_shift << 8) | (ch << 16) | (nch << 24);
-        bool launched = false;
-        if constexpr (half_kh) {
-            if (gz > 0 && spl) {
-                if (persist && wide)
-                    hipLaunchKernelGGL((nsf_train1_kernel<KK, HH, true, false, true, true>), scatter ? dim3(gx, 8, gz) : dim3(8, gx, gz), dim3(64 * BW), lds_launch, s,
-                                       dev, a.panel_map, a.magic_cliques, a.groups, a.grid_cliques, a.xrows, pshifts, a, few);
-                else if (persist)
-                    hipLaunchKernelGGL((nsf_train1_kernel<KK, HH, true, false, false, true>), scatter ? dim3(gx, 8, gz) : dim3(8, gx, gz), dim3(64 * BW), lds_launch, s,
-                                       dev, a.panel_map, a.magic_cliques, a.groups, a.grid_cliques, a.xrows, pshifts, a, few);
-                else
-                    hipLaunchKernelGGL((nsf_train1_kernel<KK, HH, false, false, false, true>), dim3(8, gx, gz), dim3(64 * W), lds_launch, s, dev, a.panel_map,
-                                       a.magic_cliques, a.groups, a.grid_cliques, a.xrows, shifts, a, few);
-                launched = true;
-            }
-        }
-        if (spl && !launched && gz > 0) return NFISAM_ERR_ARG;
-        if constexpr (lean_persist_inst_v<KK, HH>) {
-            if (gz > 0 && persist && lean) {
-                if (wide)
-                    hipLaunchKernelGGL((nsf_train1_kernel<KK, HH, true, true, true>), scatter ? dim3(gx, 8, gz) : dim3(8, gx, gz), dim3(64 * BW), lds_launch, s,
-                                       dev, a.panel_map, a.magic_cliques, a.groups, a.grid_cliques, a.xrows, pshifts, a, few);
-                else
-                    hipLaunchKernelGGL((nsf_train1_kernel<KK, HH, true, true>), scatter ? dim3(gx, 8, gz) : dim3(8, gx, gz), dim3(64 * BW), lds_launch, s,
-                                       dev, a.panel_map, a.magic_cliques, a.groups, a.grid_cliques, a.xrows, pshifts, a, few);
-                launched = true;
-            }
-        }
-        if (!launched && gz > 0 && persist && wide) {
-            hipLaunchKernelGGL((nsf_train1_kernel<KK, HH, true, false, true>), scatter ? dim3(gx, 8, gz) : dim3(8, gx, gz), dim3(64 * BW), lds_launch, s,
-                               dev, a.panel_map, a.magic_cliques, a.groups, a.grid_cliques, a.xrows, pshifts, a, few);
-            launched = true;
-        }
-        if constexpr (lean_plain_v<KK, HH>) {
-            if (gz > 0 && !persist && lean) {
-                hipLaunchKernelGGL((nsf_train1_plain_kernel<KK, HH, true>), dim3(8, gx, gz), dim3(64 * W), lds_launch, s, dev, a.panel_map,
-                                   a.magic_cliques, a.groups, a.grid_cliques, a.xrows, shifts, a, few);
-                launched = true;
-            }
-        }
-        if (launched) {
-        } else if (gz > 0 && persist)
-            hipLaunchKernelGGL((nsf_train1_kernel<KK, HH, true>), scatter ? dim3(gx, 8, gz) : dim3(8, gx, gz), dim3(64 * BW), lds_launch, s,
-                               dev, a.panel_map, a.magic_cliques, a.groups, a.grid_cliques, a.xrows, pshifts, a, few);
-        else if (gz > 0)
-            hipLaunchKernelGGL((nsf_train1_plain_kernel<KK, HH>), dim3(8, gx, gz), dim3(64 * W), lds_launch, s, dev, a.panel_map,
-                               a.magic_cliques, a.groups, a.grid_cliques, a.xrows, shifts, a, few);
-        HIP_TRY(hipGetLastError());
-        return NFISAM_OK;
+    // one wave = one dim x T tiles, dim-major blocks (nsf_train1_kernel)
+    const int T = a.tiles_per_block > 1 ? a.tiles_per_block : 1;
+    a.tiles_per_block = T;
+    const int W = a.waves > 0 ? a.waves : dim_major_waves();
+    if ((T & (T - 1)) != 0 || (W & (W - 1)) != 0 || W > 8 || T > 8) return NFISAM_ERR_ARG;
+    a.t_shift = __builtin_ctz((unsigned)T);
+    a.w_shift = __builtin_ctz((unsigned)W);
+    a.xrows = max_D;
+    // two lanes per particle (nsf_half.h; the shape decision is train_shape's, nsf_kernels.hip): 32 particles per wave
+    const bool spl = a.half != 0;
+    if (spl && (!half_kh_v<KK, HH> || T != 1 || !a.slab || max_D > 16 || a.L != 1)) return NFISAM_ERR_ARG;
+    const int TP = spl ? 32 : TILE;                       // particles per wave-tile
+    const int waves = (max_n + TP * T - 1) / (TP * T);
+    const int gx = (waves + W - 1) / W;
+    a.n_copies = gx;                                       // one gradient copy per block (a.slab = TP * T * W particles)
+    a.grid_cliques = n_cliques;
+    a.groups = n_cliques * max_D;                          // (clique, dim) groups of gx blocks, padded to the 8 XCDs
+    if ((long)a.groups * (long)n_cliques >= (1L << 31) || gx > 65535 || (a.groups + 7) / 8 > 65535) return NFISAM_ERR_ARG;
+    a.magic_cliques = n_cliques > 1 ? (unsigned)(((1ull << 32) + (unsigned)n_cliques - 1) / (unsigned)n_cliques) : 0u;
+    int rc = PanelMap<KK, HH>::get(max_D, &a.panel_map);
+    if (rc) return rc;
+    const size_t lds = train1_lds_bytes<KK, HH>(max_D, W, a.persist_iters > 0);
+    size_t lds_launch = lds;
+    if (const char* pe = getenv("NFISAM_LDS_PAD_KB")) lds_launch += (size_t)atoi(pe) * 1024;   // experiments: fewer blocks per CU
+    const bool persist = a.persist_iters > 0;
+    if (persist && (T != 1 || !a.slab || !a.fused_adam || a.L != 1 || max_D > FUSED_COUNTERS)) return NFISAM_ERR_ARG;
+    // the (clique, dim, 256 particles) blocks this launch really has (host copy of the descriptors: the plan's, or the single one)
+    const nfisam_clique* host = (a.cliques == nullptr) ? &a.single : a.host_cliques;
+    const long real_blocks = host != nullptr ? launch_blocks(host, n_cliques, W * T * TP) : (long)n_cliques * max_D * gx;
+
+    // ---- which build of the kernel -------------------------------------------------------------------------------------
+    // LEAN build (two waves per SIMD, no scratch: see the kernels' attribute) when the launch is resident at that occupancy anyway
+    bool lean = false;
+    if constexpr (lean_persist_v<KK, HH>) { if (persist && W == 4 && !spl) lean = lean_launch_fits<KK, HH, true>(real_blocks, max_D); }
+    else if constexpr (lean_persist_inst_v<KK, HH>) {
+        static const bool lone_lean = !(getenv("NFISAM_LONE_LEAN") != nullptr && getenv("NFISAM_LONE_LEAN")[0] == '0');
+        if (persist && W == 4 && !spl && lone_lean && real_blocks <= 256) lean = lean_launch_fits<KK, HH, true>(real_blocks, max_D);
     }
+    if constexpr (lean_plain_v<KK, HH>) { if (!persist && W == 4 && !spl) lean = lean_launch_fits<KK, HH, false>(real_blocks, max_D); }
+    // a window-spanning launch closes its windows in the kernel: that code exists in the two-wave builds (nsf_train1_kernel: ROOMY)
+    if (a.span_window > 0 && !(persist && (spl || lean) && W == 4 && max_D <= SPAN_MAX_D && n_cliques == 1)) return NFISAM_ERR_ARG;
+    const bool wide = persist && gx > 8;                   // groups of 9 .. 16 blocks (n > 2048): the WIDE instantiation
+    // helper waves (round 6): a two-wave build whose blocks get a CU each is launched with eight waves per block -- waves 4 .. 7
+    // own no particles and take part in the staging only (one parameter per thread: stage_cond_panel_persist_solo)
+    static const bool helpers_on = !(getenv("NFISAM_HELPERS") != nullptr && getenv("NFISAM_HELPERS")[0] == '0');
+    // (MI355X: 256 CUs -> at most 224 such blocks, 240 for groups of nine to sixteen.  The dispatcher deals workgroups round-robin to
+    //  the eight XCDs, so what must fit is the busiest XCD's share -- (octets of groups) x (blocks per group), padding included -- into
+    //  its cus / 8 CUs: at most 7/8 of them by default; the sixteen-copy launches of NFISAM_HALF=2 may fill an XCD)
+    const long cus = device_cus();
+    const long per_xcd = (long)((a.groups + 7) / 8) * gx;
+    const bool helpers = helpers_on && persist && (spl || lean || HH == 16) && W == 4 &&      // (hidden_dim 16 compiles to two waves per SIMD anyway)
+                         real_blocks <= (wide ? cus - cus / 16 : cus - cus / 8) &&
+                         per_xcd <= (wide ? cus / 8 : cus / 8 - cus / 64);       // (also the window-spanning launch: the in-kernel bookkeeping's work is its first four waves')
+    const int BW = helpers ? 2 * W : W;                    // waves per block
+    if (persist && gx > PERSIST_MAX_COPIES) return NFISAM_ERR_ARG;
+    const Train1Kernel kernel = train1_kernel_of<KK, HH>({persist, lean, wide, spl});
+    if (kernel == nullptr) return NFISAM_ERR_ARG;
+    rc = set_lds(kernel, lds_launch);
+    if (rc) return rc;
+
+    // few cliques: their descriptors travel in the kernel arguments
+    static_assert(offsetof(Train1Head, shifts) == 32 && sizeof(Train1Head) == 40, "scalar head of the kernel arguments");
+    Train1Few few;
+    memset(&few, 0, sizeof(few));
+    const nfisam_clique* dev = a.cliques;
+    if (host != nullptr && n_cliques <= TRAIN1_KERNARG_CLIQUES) {
+        memcpy(few.c, host, sizeof(nfisam_clique) * (size_t)n_cliques);
+        dev = nullptr;
+    } else if (dev == nullptr) {
+        return NFISAM_ERR_ARG;
+    }
+    const int nch = a.n_chains > 1 ? a.n_chains : 1, ch = a.n_chains > 1 ? a.chain : 0;
+    const int octets = (a.groups + 7) / 8;
+    const int gz = (octets - ch + nch - 1) / nch;          // octets ch, ch + nch, ...
+    if (nch > 255 || ch < 0 || ch >= nch) return NFISAM_ERR_ARG;
+    {   // contended launches (more than one block per CU: several waves share a SIMD) divide the Adam update among a group's blocks
+        // (read by the chunk-persistent kernels only, whose launches have T == 1 and a host copy of the descriptors)
+        static const char* se = getenv("NFISAM_PERSIST_SPLIT");
+        a.persist_split = (se != nullptr) ? (se[0] == '1') : (real_blocks > 256);
+    }
+    static const int spin_log2 = getenv("NFISAM_PERSIST_SPINS") != nullptr ? atoi(getenv("NFISAM_PERSIST_SPINS")) : 15;           // (~1 us per look: a member that never arrives costs tens of milliseconds, not seconds -- round 4: 22)
+    a.persist_spins = spin_log2 < 1 ? 1 : (spin_log2 > 30 ? 30 : spin_log2);
+    static const bool drop = getenv("NFISAM_PERSIST_DROP") != nullptr && getenv("NFISAM_PERSIST_DROP")[0] == '1';                  // (test knob)
+    static const bool scatter = getenv("NFISAM_PERSIST_SCATTER") != nullptr && getenv("NFISAM_PERSIST_SCATTER")[0] == '1';   // (test knob)
+    // the two test knobs reach the chunk-persistent kernels only; `scatter` also transposes their grid
+    const int shifts = a.t_shift | (a.w_shift << 8) | (ch << 16) | (nch << 24) |
+                       (persist ? (scatter ? 0x80 : 0) | (drop ? 0x40 : 0) : 0);
+    if (gz > 0)
+        hipLaunchKernelGGL(kernel, (persist && scatter) ? dim3(gx, 8, gz) : dim3(8, gx, gz), dim3(64 * BW), lds_launch, s, dev, a.panel_map,
+                           a.magic_cliques, a.groups, a.grid_cliques, a.xrows, shifts, a, few);
+    HIP_TRY(hipGetLastError());
+    return NFISAM_OK;
 }
 
 // gradient kernel of one training iteration / VJP: picks the kernel family and block shape for the launch
@@ -4041,24 +3994,19 @@ static int unit_train(const TrainArgs& a_in, int n_cliques, int max_n, int max_D
     const bool wl = fits && (wm == 1 || (wm == -1 && blocks * W <= 4096 && !(independent_dims && blocks * W > 1024)));
     a.wl_floats = wl ? (int)wfloats : 0;
     const size_t lds = (tile_floats + (wl ? wfloats : 0)) * sizeof(float);
-    int rc;
-    if constexpr (HH == 8) {
-        if (mf) {
-            if (wl) rc = launch_train_variant<KK, HH, true, true, 1>(a, n_cliques, max_n, W, groups, lds, s);
-            else rc = launch_train_variant<KK, HH, true, false, 1>(a, n_cliques, max_n, W, groups, lds, s);
-            if (rc) return rc;
-            HIP_TRY(hipGetLastError());
-            return NFISAM_OK;
-        }
-    }
-    if (wl) rc = launch_train_variant<KK, HH, false, true, 1>(a, n_cliques, max_n, W, groups, lds, s);
-    else rc = launch_train_variant<KK, HH, false, false, 1>(a, n_cliques, max_n, W, groups, lds, s);
+    const TrainKernel kernel = train_kernel_of<KK, HH>(mf, wl);
+    if (kernel == nullptr) return NFISAM_ERR_ARG;
+    const int rc = set_lds(kernel, lds);
     if (rc) return rc;
+    hipLaunchKernelGGL(kernel, dim3((max_n + TILE * T - 1) / (TILE * T), n_cliques, groups), dim3(64 * W), lds, s, a);
     HIP_TRY(hipGetLastError());
     return NFISAM_OK;
 }
 
 // ---- the unit's table -------------------------------------------------------------------------------------------
+// every compiled pair has hidden_dim 4, 8 or 16: the launchers above assume it
+#define NSF_CHECK_KH(k, h) static_assert(h == 4 || h == 8 || h == 16, "kernel units are instantiated for hidden_dim 4, 8 and 16");
+NSF_FOR_EACH_KH(NSF_CHECK_KH)
 #define NSF_OPS_ENTRY(k, h) \
     {k, h, unit_forward<k, h>, unit_inverse<k, h>, unit_walk<k, h>, unit_density<k, h>, unit_train<k, h>, unit_prepare<k, h>, pair_kernel_lds<k, h>, unit_pair_map<k, h>, unit_persist_places<k, h>},
 static const NsfUnitOps g_unit_ops[] = {NSF_FOR_EACH_KH(NSF_OPS_ENTRY)};
