@@ -260,6 +260,37 @@ typedef struct nfisam_factor_term {
 int nfisam_factor_graph_log_density(const nfisam_factor_term* terms, int n_terms, const float* St, int total_dim, int n,
                                     double* log_p, double* per_factor, nfisam_stream_t stream);
 
+/* ---- two-sample MMD: the kernel sums of many column blocks in one launch (sample_mmd.hip) ---------------------------------
+ * The reference grades a posterior against a reference sample set with an RBF-kernel MMD (src/utils/Statistics.py:13-84).
+ * Block b of the table compares the entries col_off .. col_off + d of the row lists: entry e pairs row xcols[e] of Xt with
+ * row ycols[e] of Yt (the reference set has its own variable order).  Blocks may overlap and repeat entries. */
+typedef struct nfisam_mmd_block {
+    int32_t col_off;           /* first entry of the block in xcols / ycols / scale / wrap */
+    int32_t d;                 /* number of entries, >= 1 (no upper limit) */
+    double inv_two_sigma2;     /* 1 / (2 sigma^2) of the block's kernel, positive and finite */
+} nfisam_mmd_block;
+
+/* sums[b] = { Sxx, Syy, Sxy } (double[n_blocks][3]): the sums of k_b over ALL ordered pairs of the m columns of Xt, of the n
+ * columns of Yt, and of one of each (a pair i = i contributes exactly 1), with
+ *     k_b(u, v) = exp(-inv_two_sigma2 * sum_e diff_e^2),  diff_e = (double)u_e - (double)v_e,
+ * then wrapped into [-pi, pi) where wrap[e] is set (the sign convention of theta_to_pipi), then multiplied by scale[e].
+ *   Xt[x_rows][m], Yt[y_rows][n]: COLUMN-major float32 device matrices (the layout of the tree walk's St);
+ *   blocks[n_blocks]: HOST copy of the table (validated here), blocks_dev: DEVICE copy of the same table (what the kernel reads);
+ *   xcols, ycols [n_entries] int32, scale [n_entries] double (nullable), wrap [n_entries] uint8 (nullable): DEVICE arrays;
+ *   scratch: nfisam_sample_mmd_scratch_count(m, n, n_blocks) doubles on the device (per-tile partials).
+ * Float32 points in; float64 differences, squared distance, exp and sums.  Two launches, no float atomics: a 256-thread
+ * group per (64 x 64 tile of pairs, block, sum) writes one partial, then a wave per (block, sum) adds the partials in an order
+ * that depends on (m, n) alone: two calls give the same bits, and a block's sums are the same bits alone or among hundreds,
+ * wherever it stands in the table.
+ * NFISAM_ERR_ARG: a NULL pointer (scale and wrap excepted), m, n, x_rows, y_rows, n_entries or n_blocks < 1, a block with
+ * d < 1 or inv_two_sigma2 not positive and finite, more than 65535 blocks or more than 2^31 - 1 tiles.  The device arrays are
+ * not read on the host: a block whose entries leave [0, n_entries) or that names a row outside its matrix yields NaN for its
+ * three sums (nothing is read out of bounds); the Python binding refuses such tables before upload.  (Additive: ABI 1600.) */
+size_t nfisam_sample_mmd_scratch_count(int m, int n, int n_blocks);     /* 0 for arguments the entry refuses */
+int nfisam_sample_mmd(const float* Xt, int x_rows, int m, const float* Yt, int y_rows, int n, const nfisam_mmd_block* blocks,
+                      const nfisam_mmd_block* blocks_dev, int n_blocks, const int32_t* xcols, const int32_t* ycols, int n_entries,
+                      const double* scale, const uint8_t* wrap, double* sums, double* scratch, nfisam_stream_t stream);
+
 /* ---- training -------------------------------------------------------------------------- */
 /* Vector-Jacobian product of the L-layer flow (what torch autograd computes for
  * `loss.backward()` in slam/NFiSAM.py:474): kgrad[L*kparam_count] += d<gz,z>/dtheta + d<gl,logdet>/dtheta,

@@ -28,6 +28,7 @@ EXPORTS = [
     "nfisam_nsf_train_plan_end", "nfisam_nsf_train_plan_xcd_span", "nfisam_nsf_train_plan_kernel_ms", "nfisam_nsf_train_plan_create_validated", "nfisam_nsf_train_plan_feed", "nfisam_nsf_train_plan_enqueued", "nfisam_nsf_train_plan_refill",
     "nfisam_normalize_columns", "nfisam_simulate_clique", "nfisam_nsf_train_plan_launch_async",
     "nfisam_nsf_posterior_log_density", "nfisam_factor_graph_log_density",
+    "nfisam_sample_mmd", "nfisam_sample_mmd_scratch_count",
 ]
 
 
@@ -71,6 +72,13 @@ class FactorTerm(C.Structure):
 assert C.sizeof(TrainState) == 32 and C.sizeof(AdamCfg) == 32 and C.sizeof(Clique) == 64 and C.sizeof(PostClique) == 64
 assert C.sizeof(FactorTerm) == 160
 
+
+class MmdBlock(C.Structure):
+    _fields_ = [("col_off", C.c_int32), ("d", C.c_int32), ("inv_two_sigma2", C.c_double)]
+
+
+assert C.sizeof(MmdBlock) == 16
+
 _lib = None
 
 
@@ -96,6 +104,7 @@ def lib():
         _lib.nfisam_nsf_grad_workspace_count.restype = C.c_size_t
         _lib.nfisam_nsf_train_plan_stream.restype = C.c_void_p
         _lib.nfisam_nsf_train_plan_enqueued.restype = C.c_long
+        _lib.nfisam_sample_mmd_scratch_count.restype = C.c_size_t
         for name in EXPORTS:
             getattr(_lib, name)   # raises AttributeError if the ABI is incomplete
     return _lib
@@ -841,3 +850,113 @@ def factor_graph_log_density_t(terms: np.ndarray, St, device, per_factor=False, 
     if per_factor:
         return log_p, per
     return log_p
+
+
+# ---- two-sample MMD: the kernel sums of many column blocks in one launch (nfisam_sample_mmd) ------------------------------------
+MMD_BLOCK_DTYPE = np.dtype([("col_off", np.int32), ("d", np.int32), ("inv_two_sigma2", np.float64)])
+assert MMD_BLOCK_DTYPE.itemsize == C.sizeof(MmdBlock)
+
+
+def pack_mmd_blocks(dims, sigmas) -> np.ndarray:
+    """The block table (numpy MMD_BLOCK_DTYPE) of consecutive blocks of `dims` entries with kernel bandwidths `sigmas`."""
+    dims = np.asarray(dims, dtype=np.int64).reshape(-1)
+    t = np.zeros(dims.size, dtype=MMD_BLOCK_DTYPE)
+    t["d"] = dims
+    t["col_off"] = np.cumsum(dims) - dims
+    t["inv_two_sigma2"] = 1.0 / (2.0 * np.asarray(sigmas, dtype=np.float64).reshape(-1) ** 2)
+    return t
+
+
+def check_mmd_blocks(blocks: np.ndarray, xcols, ycols, x_rows: int, y_rows: int, scale=None, wrap=None) -> None:
+    """ValueError for tables the kernel must not see: no block or more than 65535, d < 1, a bandwidth term that is not positive
+    and finite, entries outside [0, n_entries), a row outside [0, x_rows) / [0, y_rows), per-entry arrays of another length."""
+    if not isinstance(blocks, np.ndarray) or blocks.dtype != MMD_BLOCK_DTYPE or blocks.ndim != 1:
+        raise ValueError("blocks must be a 1-D numpy array of MMD_BLOCK_DTYPE")
+    xcols, ycols = np.asarray(xcols), np.asarray(ycols)
+    if xcols.ndim != 1 or ycols.ndim != 1 or xcols.size != ycols.size or xcols.size < 1:
+        raise ValueError("xcols and ycols must be 1-D lists of the same length >= 1")
+    ne = int(xcols.size)
+    for name, a in (("scale", scale), ("wrap", wrap)):
+        if a is not None and (np.ndim(a) != 1 or np.size(a) != ne):
+            raise ValueError("%s must have one value per entry (%d)" % (name, ne))
+    if not 1 <= blocks.size <= 65535:
+        raise ValueError("1..65535 blocks are supported, got %d" % blocks.size)
+    off, d = blocks["col_off"].astype(np.int64), blocks["d"].astype(np.int64)
+    bad = (d < 1) | (off < 0) | (off + d > ne)
+    if np.any(bad):
+        raise ValueError("block %d: entries %d..%d leave the %d entries of the column lists (d >= 1 is required)"
+                         % (int(np.argmax(bad)), int(off[np.argmax(bad)]), int((off + d)[np.argmax(bad)]), ne))
+    v = blocks["inv_two_sigma2"]
+    if not np.all(np.isfinite(v) & (v > 0)):
+        raise ValueError("block %d: inv_two_sigma2 must be positive and finite" % int(np.argmin(np.isfinite(v) & (v > 0))))
+    for name, cols, rows in (("xcols", xcols, int(x_rows)), ("ycols", ycols, int(y_rows))):
+        if not 0 <= int(cols.min()) <= int(cols.max()) < rows:
+            raise ValueError("%s: a row is out of range of the %d rows of its matrix" % (name, rows))
+    if scale is not None and not np.all(np.isfinite(np.asarray(scale, dtype=np.float64))):
+        raise ValueError("scale must be finite")
+
+
+def _mmd_matrix(A, name, device):
+    if not (torch.is_tensor(A) or isinstance(A, np.ndarray)) or A.ndim != 2:
+        raise ValueError("%s must be a [rows, cols] tensor or array" % name)
+    if torch.is_tensor(A):
+        return A.to(device=device, dtype=torch.float32).t().contiguous()
+    return torch.from_numpy(np.ascontiguousarray(A.T, dtype=np.float32)).to(device)
+
+
+def mmd_sums(X, Y, blocks: np.ndarray, xcols, ycols, scale=None, wrap=None, device=None):
+    """The kernel sums {Sxx, Syy, Sxy} of every block of `blocks` between the sample sets X [m, x_cols] and Y [n, y_cols]
+    (tensor or numpy; float32 points, float64 arithmetic): nfisam_sample_mmd, one launch for all blocks on the current
+    stream.  `blocks`: numpy MMD_BLOCK_DTYPE (`pack_mmd_blocks`); entry e of a block pairs column xcols[e] of X with column
+    ycols[e] of Y; scale [n_entries] multiplies an entry's differences, wrap [n_entries] marks angles (differences brought
+    into [-pi, pi)).  -> [n_blocks, 3] float64 device tensor."""
+    if device is None:
+        device = X.device if torch.is_tensor(X) else "cuda"
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("mmd_sums needs a ROCm device (no CPU path exists)")
+    if not (torch.is_tensor(X) or isinstance(X, np.ndarray)) or X.ndim != 2 or \
+            not (torch.is_tensor(Y) or isinstance(Y, np.ndarray)) or Y.ndim != 2:
+        raise ValueError("X and Y must be [rows, cols] tensors or arrays")
+    check_mmd_blocks(blocks, xcols, ycols, int(X.shape[1]), int(Y.shape[1]), scale, wrap)
+    return mmd_sums_t(_mmd_matrix(X, "X", device), _mmd_matrix(Y, "Y", device), blocks, xcols, ycols, scale, wrap, checked=True)
+
+
+def mmd_sums_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, scale=None, wrap=None, checked=False):
+    """`mmd_sums` on the COLUMN-major matrices Xt [x_rows, m], Yt [y_rows, n] (contiguous float32 device tensors, used in
+    place): what the tree walk wrote."""
+    for name, t in (("Xt", Xt), ("Yt", Yt)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError("%s must be a tensor on a ROCm device (no CPU path exists)" % name)
+        if t.ndim != 2 or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float32 [rows, points] tensor" % name)
+    if Xt.device != Yt.device:
+        raise ValueError("Xt and Yt must be on the same device")
+    device = Xt.device
+    x_rows, m, y_rows, n = int(Xt.shape[0]), int(Xt.shape[1]), int(Yt.shape[0]), int(Yt.shape[1])
+    if m < 1 or n < 1:
+        raise ValueError("both sample sets need at least one point")
+    if not checked:
+        check_mmd_blocks(blocks, xcols, ycols, x_rows, y_rows, scale, wrap)
+    nb = int(blocks.shape[0])
+    xc, yc = np.asarray(xcols, dtype=np.int32), np.asarray(ycols, dtype=np.int32)
+    host = [blocks.view(np.uint8).reshape(-1), xc, yc]
+    if scale is not None:
+        host.append(np.asarray(scale, dtype=np.float64))
+    if wrap is not None:
+        host.append(np.asarray(wrap).astype(np.uint8))
+    with torch.cuda.device(device):
+        dev = upload(*host, device=device)
+        blk_d, xc_d, yc_d = dev[:3]
+        sc_d = dev[3] if scale is not None else None
+        wr_d = dev[-1] if wrap is not None else None
+        count = int(lib().nfisam_sample_mmd_scratch_count(m, n, nb))
+        if count < 1:
+            raise ValueError("mmd_sums: %d x %d points in %d blocks exceed the grid" % (m, n, nb))
+        # the per-tile partials come from torch's allocator, like the per-factor rows of factor_graph_log_density_t
+        scratch = torch.empty(count, dtype=torch.float64, device=device)
+        sums = torch.empty(nb, 3, dtype=torch.float64, device=device)
+        blocks = np.ascontiguousarray(blocks)
+        _check(lib().nfisam_sample_mmd(_ptr(Xt), x_rows, m, _ptr(Yt), y_rows, n, blocks.ctypes.data_as(C.c_void_p),
+                                       C.c_void_p(blk_d.data_ptr()), nb, _ptr(xc_d), _ptr(yc_d), int(xc.size), _ptr(sc_d),
+                                       _ptr(wr_d), _ptr(sums), _ptr(scratch), _stream()), "nfisam_sample_mmd")
+    return sums

@@ -969,6 +969,127 @@ class NFiSAM(FactorGraphSolver):
         estimate (FactorGraphSolver.plot2d_MAP_rbt_only, src/slam/FactorGraphSolver.py:660-671).  -> variable -> [dim]."""
         return self.posterior_diagnostics(samples)["map_sample"]
 
+    # ---- the solver graded against a reference sample set --------------------------------------------------------
+    def posterior_mmd(self, reference, samples=None, n: int = None, variables=None, blocks=None, columns: str = "xy",
+                      estimator: str = "mmd", sigma=None, standardise: bool = False, joint: bool = True) -> dict:
+        """MMD between the posterior and a reference sample set -- how the paper grades NF-iSAM (the reference's
+        src/utils/Statistics.py:13-84 and icra_paper/compute_mmd.py: one joint `mmd` per step and the mean over the
+        variables of the xy-marginal `mmd`) -- with the joint block, every variable's marginal and any further blocks in ONE
+        device launch (nfisam_sample_mmd: float32 points, float64 arithmetic).
+
+        reference: mapping variable -> [m, dim] (numpy or torch): a reference solution, another solver's `sample_posterior`
+        output, a LazyPosterior.  samples=None draws `n` (default posterior_sample_num) points through the tree walk and scores
+        the device matrix where it lies; otherwise `samples` is what `posterior_log_pdf` accepts and nothing is drawn.
+        variables: which to compare and in which order (default: those of the elimination ordering that `reference` holds).
+        columns: "xy" the reference's rule, the first two columns of every variable (compute_mmd.py:88-98); "all" adds the
+        headings, compared by differences wrapped into [-pi, pi).  standardise: divide each non-circular column's differences
+        by the reference set's std of that column (floored at 1e-3).  blocks: further blocks, each a tuple of variables
+        (e.g. (pose, landmark)).  estimator, sigma: as `utils.Statistics.mmd_blocks` ("mmd": k_sigma2 = 1; "MMDb" / "MMDu2":
+        sigma = sqrt(columns of the block)).
+        -> dict: joint (None without `joint`), marginal (variable -> value), marginal_mean (the reference's "marginal mmd"),
+        blocks (list), floor = sqrt(1 / m + 1 / n) (the value MMDb takes when no pair of the two sets is within kernel
+        reach: a statistic that sits there says nothing), m (reference points), n (posterior points), estimator.
+        Raises RuntimeError when there is nothing to grade yet, ValueError for an unknown option, a requested variable that
+        the ordering, `reference` or `samples` lack, a wrong width, ragged rows or too few points -- before anything is
+        launched."""
+        from utils.Statistics import ESTIMATORS, mmd_from_sums
+        what = "posterior_mmd"
+        if estimator not in ESTIMATORS:
+            raise ValueError("%s: estimator must be one of %s, got %r" % (what, ESTIMATORS, estimator))
+        if columns not in ("xy", "all"):
+            raise ValueError("%s: columns must be 'xy' or 'all', got %r" % (what, columns))
+        if not self._elimination_ordering:
+            raise RuntimeError("%s: no factor graph yet (run an incremental update first)" % what)
+        if samples is None:
+            tree = self._physical_bayes_tree
+            if tree is None or tree.root is None:
+                raise RuntimeError("%s: no Bayes tree yet (run an incremental update first)" % what)
+            for clique in tree.clique_ordering():
+                if clique not in self._clique_density_model:
+                    raise RuntimeError("%s: clique %s has no trained model yet" % (what, clique))
+        known = set(self._elimination_ordering)
+        if variables is None:
+            variables = [v for v in self._elimination_ordering if v in reference]
+        else:
+            variables = list(variables)
+        extra = [tuple(b) for b in blocks] if blocks is not None else []
+        if not variables:
+            raise ValueError("%s: no variable to compare (the reference holds none of the ordering's)" % what)
+        for v in list(variables) + [v for b in extra for v in b]:
+            if v not in known:
+                raise ValueError("%s: variable %s is not in the elimination ordering" % (what, v.name))
+            if v not in reference:
+                raise ValueError("%s: the reference lacks variable %s" % (what, v.name))
+        for b in extra:
+            if not b or any(v not in variables for v in b):
+                raise ValueError("%s: a block is a non-empty tuple of compared variables" % what)
+        # the reference set: its own column layout, the requested variables side by side
+        m, ref, rcol, width = None, {}, {}, 0
+        for v in variables:
+            a = reference[v]
+            a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+            if a.ndim == 1 and v.dim == 1:
+                a = a.reshape(-1, 1)
+            if a.ndim != 2 or a.shape[1] != v.dim:
+                raise ValueError("%s: reference samples of %s must be [m, %d], got %s" % (what, v.name, v.dim, tuple(a.shape)))
+            if m is None:
+                m = int(a.shape[0])
+            elif int(a.shape[0]) != m:
+                raise ValueError("%s: ragged reference: %s has %d rows, the others %d" % (what, v.name, a.shape[0], m))
+            ref[v], rcol[v] = a, width
+            width += v.dim
+        if samples is not None:
+            values, rows = self._check_points(samples, what)
+        else:
+            rows = int(self._args.posterior_sample_num if n is None else n)
+        need = 1 if estimator == "MMDb" else 2
+        if m < need or rows < need:
+            raise ValueError("%s: %s needs at least %d points in each set (reference %d, posterior %d)"
+                             % (what, estimator, need, m, rows))
+        Y = np.concatenate([ref[v] for v in variables], axis=1).astype(np.float32)
+        pcol, total_dim = self._post_columns()
+
+        def cols_of(v):
+            return range(v.dim if columns == "all" else min(v.dim, 2))
+
+        table = ([tuple(variables)] if joint else []) + [(v,) for v in variables] + extra
+        xcols, ycols, wrap, dims = [], [], [], []
+        for blk in table:
+            k = 0
+            for v in blk:
+                circ = v.circular_dim_list
+                for c in cols_of(v):
+                    xcols.append(pcol[v] + c); ycols.append(rcol[v] + c); wrap.append(bool(circ[c]))
+                    k += 1
+            dims.append(k)
+        xcols, ycols, wrap = np.asarray(xcols, dtype=np.int32), np.asarray(ycols, dtype=np.int32), np.asarray(wrap, dtype=np.uint8)
+        dims = np.asarray(dims)
+        if sigma is None:
+            sig = np.ones(len(table)) if estimator == "mmd" else np.sqrt(dims.astype(np.float64))
+        else:
+            sig = np.broadcast_to(np.asarray(sigma, dtype=np.float64).reshape(-1), (len(table),)) if np.size(sigma) == 1 else \
+                np.asarray(sigma, dtype=np.float64).reshape(-1)
+            if sig.size != len(table) or not np.all(np.isfinite(sig) & (sig > 0)):
+                raise ValueError("%s: sigma is one positive bandwidth, or one per block (%d)" % (what, len(table)))
+        scale = None
+        if standardise:
+            std = np.maximum(Y.astype(np.float64).std(axis=0), 1e-3)
+            scale = np.where(wrap != 0, 1.0, 1.0 / std[ycols])
+        blocks_np = _nh.pack_mmd_blocks(dims, sig)
+        device = _device()
+        if samples is None:
+            S = self.posterior_launch(rows)["S"]                 # [n, total_dim] on the device: scored where it lies
+        else:
+            S = self._points_matrix(values, rows, pcol, total_dim, device)
+        sums = _nh.mmd_sums(S, Y, blocks_np, xcols, ycols, scale=scale, wrap=wrap if wrap.any() else None, device=device)
+        val = mmd_from_sums(sums.cpu().numpy(), rows, m, estimator)
+        k0 = 1 if joint else 0
+        marginal = {v: float(val[k0 + i]) for i, v in enumerate(variables)}
+        return dict(joint=float(val[0]) if joint else None, marginal=marginal,
+                    marginal_mean=float(np.mean(list(marginal.values()))),
+                    blocks=[float(x) for x in val[k0 + len(variables):]], floor=float(np.sqrt(1.0 / m + 1.0 / rows)),
+                    m=m, n=rows, estimator=estimator)
+
     def posterior_collect(self, handle, timer: List = None, copy_stream=None):
         """Second half: wait for the walk, one D2H copy, per-variable views of the sample matrix (in the elimination ordering
         of the launch).  `copy_stream`: copy behind the walk's event on that stream instead of the walk's own (which may
