@@ -291,6 +291,68 @@ int nfisam_sample_mmd(const float* Xt, int x_rows, int m, const float* Yt, int y
                       const nfisam_mmd_block* blocks_dev, int n_blocks, const int32_t* xcols, const int32_t* ycols, int n_entries,
                       const double* scale, const uint8_t* wrap, double* sums, double* scratch, nfisam_stream_t stream);
 
+/* ---- sample summaries: means, resultant lengths, covariances and quantiles of many column blocks (sample_summary.hip) -------
+ * The reference summarises a draw on the host: `sample_mean` (src/utils/Statistics.py:151-171: np.mean, and scipy's
+ * circmean(high = pi, low = -pi) for headings) and, built on it, `rmse` (:142-148), `geodesic_distance` (:179-191) and
+ * `translation_distance` (:204-214).  Here the COLUMN-major float32 device matrix Xt[x_rows][n] (the tree walk's St, the layout
+ * of nfisam_sample_mmd) is summarised where it lies.  Entry e names the row cols[e] of Xt; block b of the table is the run of
+ * entries col_off .. col_off + d.  Rows may repeat within a block and between blocks.
+ * Float32 points in; every difference, product, transcendental and sum is float64.  No float atomics: an entry's and a block's
+ * results are the same bits alone, repeated, anywhere in a table, and on a second call. */
+#define NFISAM_MOMENTS_MAX_D  16     /* widest block: a pose is 3, a pose and a landmark 5, two poses 6 */
+#define NFISAM_QUANTILE_MAX_N 16384  /* most points per column the quantile sort takes: 128 KiB of float64 keys in LDS */
+typedef struct nfisam_moment_block {
+    int32_t col_off;           /* first entry of the block in cols / circular / mean / resultant */
+    int32_t d;                 /* number of entries, 1 .. NFISAM_MOMENTS_MAX_D */
+    int64_t cov_off;           /* where the block's d x d row-major matrix starts in cov */
+} nfisam_moment_block;
+
+/* nfisam_sample_moments replaces Statistics.py:151-171 (and the per-variable np.cov of the run scripts).  With w = weights
+ * (NULL: all ones) and W = sum_i w_i:
+ *   mean[e]       Euclidean entry: sum w x / W, evaluated as x_0 + sum w (x - x_0) / W (a constant column gives x_0 exactly);
+ *                 circular entry (circular[e] != 0): atan2(S, C), C = sum w cos x / W, S = sum w sin x / W, reported in
+ *                 [-pi, pi) (pi becomes -pi): scipy's circmean(high = pi, low = -pi).  Evaluated about the first point as
+ *                 x_0 + atan2(S', C') with the sums of sin / cos (x - x_0): the same direction and length, and x_0 exactly
+ *                 for a constant column;
+ *   resultant[e]  hypot(C', S') = hypot(C, S), the mean resultant length in [0, 1], for a circular entry; NaN for a Euclidean one;
+ *   cov           block b's d x d matrix at cov[cov_off]: sum w r_e r_f / W -- the POPULATION form (divided by W, not W - 1)
+ *                 -- with r = x - mean for a Euclidean entry and r = wrap_pi(x - mean) in [-pi, pi) for a circular one.
+ *                 For a circular entry this is the mean squared WRAPPED deviation about the circular mean (and the mean product
+ *                 of wrapped deviations off the diagonal), not a variance about an arithmetic mean: the wrapped residuals need
+ *                 not average to zero.  Two passes: the residuals are taken about the float64 mean, never sum x^2 - (sum x)^2.
+ *   Xt[x_rows][n]: float32, device;  blocks[n_blocks]: HOST copy of the table (validated here), blocks_dev: DEVICE copy (what
+ *   the kernel reads);  cols [n_entries] int32, circular [n_entries] uint8 (nullable), weights [n] float64 (nullable,
+ *   non-negative, not all zero: W = 0 gives NaN), mean, resultant [n_entries], cov [cov_count]: DEVICE arrays.
+ * Two launches: a 256-thread group per entry (thread t adds points t, t + 256, ...; a fixed shuffle tree; the four waves in
+ * order), then a group per block (wave w owns every fourth product of the upper triangle; lane l adds points l, l + 64, ...;
+ * the same tree).  The sum of a product depends on n, its two rows and their flags alone: the diagonal blocks of a pair's
+ * matrix are the bits of its variables' own matrices.
+ * NFISAM_ERR_ARG: a NULL pointer (circular and weights excepted), n, x_rows, n_entries, n_blocks or cov_count < 1, more than
+ * 65535 blocks, a block with d outside 1 .. 16 or a matrix outside [0, cov_count).  The device arrays are not read on the host:
+ * an entry whose row is outside [0, x_rows) has NaN mean and resultant, and a block that holds such an entry or whose entries
+ * leave [0, n_entries) has an all-NaN matrix (nothing is read out of bounds, every other entry and block is untouched); the
+ * Python binding refuses such tables before upload.  (Additive: ABI 1600.) */
+int nfisam_sample_moments(const float* Xt, int x_rows, int n, const nfisam_moment_block* blocks, const nfisam_moment_block* blocks_dev,
+                          int n_blocks, const int32_t* cols, int n_entries, const uint8_t* circular, const double* weights,
+                          double* mean, double* resultant, double* cov, long long cov_count, nfisam_stream_t stream);
+
+/* out[e][q] (double[n_entries][n_probs]) = the quantile at probs[q] of the n float64 keys of entry e: x for a Euclidean
+ * entry, wrap_pi(x - center[e]) for a circular one (the caller passes the means of nfisam_sample_moments; NULL: 0).  numpy's
+ * default "linear" rule on the sorted keys s: h = p (n - 1), s[floor h] + (h - floor h) (s[ceil h] - s[floor h]); where h is
+ * an integer the key itself, bit for bit.  A circular entry reports center + quantile UNWRAPPED, so the ends of an interval
+ * stay ordered and may lie outside [-pi, pi): the caller wraps for display.  No weights.  (What the reference's mean and
+ * ellipse plots, built on Statistics.py:151-171, cannot show of a non-Gaussian posterior.)
+ *   probs[n_probs]: HOST copy (validated here), probs_dev: DEVICE copy (what the kernel reads);  cols, circular (nullable),
+ *   center (nullable) [n_entries], out: DEVICE arrays.
+ * One launch: a 256-thread group per entry sorts the keys in dynamic LDS (bitonic, padded with +inf to the next power of two:
+ * 8 bytes per padded point, so small draws keep several groups per CU).
+ * NFISAM_ERR_ARG, before any launch: a NULL pointer (circular and center excepted), n, x_rows, n_entries or n_probs < 1,
+ * n > NFISAM_QUANTILE_MAX_N, a probability outside [0, 1] (or NaN).  An entry whose row is outside [0, x_rows), or a device
+ * probability outside [0, 1], yields NaN (nothing is read out of bounds).  (Additive: ABI 1600.) */
+int nfisam_sample_quantiles(const float* Xt, int x_rows, int n, const int32_t* cols, int n_entries, const uint8_t* circular,
+                            const double* center, const double* probs, const double* probs_dev, int n_probs, double* out,
+                            nfisam_stream_t stream);
+
 /* ---- training -------------------------------------------------------------------------- */
 /* Vector-Jacobian product of the L-layer flow (what torch autograd computes for
  * `loss.backward()` in slam/NFiSAM.py:474): kgrad[L*kparam_count] += d<gz,z>/dtheta + d<gl,logdet>/dtheta,

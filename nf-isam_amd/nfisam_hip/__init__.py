@@ -29,6 +29,7 @@ EXPORTS = [
     "nfisam_normalize_columns", "nfisam_simulate_clique", "nfisam_nsf_train_plan_launch_async",
     "nfisam_nsf_posterior_log_density", "nfisam_factor_graph_log_density",
     "nfisam_sample_mmd", "nfisam_sample_mmd_scratch_count",
+    "nfisam_sample_moments", "nfisam_sample_quantiles",
 ]
 
 
@@ -78,6 +79,14 @@ class MmdBlock(C.Structure):
 
 
 assert C.sizeof(MmdBlock) == 16
+
+
+class MomentBlock(C.Structure):
+    _fields_ = [("col_off", C.c_int32), ("d", C.c_int32), ("cov_off", C.c_int64)]
+
+
+assert C.sizeof(MomentBlock) == 16
+MOMENTS_MAX_D, QUANTILE_MAX_N = 16, 16384        # NFISAM_MOMENTS_MAX_D, NFISAM_QUANTILE_MAX_N
 
 _lib = None
 
@@ -960,3 +969,205 @@ def mmd_sums_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, scale=None, wrap=None, 
                                        C.c_void_p(blk_d.data_ptr()), nb, _ptr(xc_d), _ptr(yc_d), int(xc.size), _ptr(sc_d),
                                        _ptr(wr_d), _ptr(sums), _ptr(scratch), _stream()), "nfisam_sample_mmd")
     return sums
+
+
+# ---- sample summaries: means, resultant lengths, covariances, quantiles (nfisam_sample_moments, nfisam_sample_quantiles) --------
+MOMENT_BLOCK_DTYPE = np.dtype([("col_off", np.int32), ("d", np.int32), ("cov_off", np.int64)])
+assert MOMENT_BLOCK_DTYPE.itemsize == C.sizeof(MomentBlock)
+
+
+def pack_moment_blocks(dims) -> np.ndarray:
+    """The block table (numpy MOMENT_BLOCK_DTYPE) of consecutive blocks of `dims` entries, their d x d matrices one after
+    another in `cov`."""
+    dims = np.asarray(dims, dtype=np.int64).reshape(-1)
+    t = np.zeros(dims.size, dtype=MOMENT_BLOCK_DTYPE)
+    t["d"] = dims
+    t["col_off"] = np.cumsum(dims) - dims
+    t["cov_off"] = np.cumsum(dims * dims) - dims * dims
+    return t
+
+
+def check_moment_blocks(blocks: np.ndarray, cols, x_rows: int, circular=None, cov_count: int = None) -> None:
+    """ValueError for tables the kernel must not see: no block or more than 65535, d outside 1..16, entries outside
+    [0, n_entries), a matrix outside [0, cov_count) (default: the end of the last matrix), a row outside [0, x_rows), flags of
+    another length."""
+    if not isinstance(blocks, np.ndarray) or blocks.dtype != MOMENT_BLOCK_DTYPE or blocks.ndim != 1:
+        raise ValueError("blocks must be a 1-D numpy array of MOMENT_BLOCK_DTYPE")
+    cols = np.asarray(cols)
+    if cols.ndim != 1 or cols.size < 1:
+        raise ValueError("cols must be a 1-D list of at least one row")
+    ne = int(cols.size)
+    if circular is not None and (np.ndim(circular) != 1 or np.size(circular) != ne):
+        raise ValueError("circular must have one flag per entry (%d)" % ne)
+    if not 1 <= blocks.size <= 65535:
+        raise ValueError("1..65535 blocks are supported, got %d" % blocks.size)
+    off, d, coff = blocks["col_off"].astype(np.int64), blocks["d"].astype(np.int64), blocks["cov_off"].astype(np.int64)
+    bad = (d < 1) | (d > MOMENTS_MAX_D)
+    if np.any(bad):
+        raise ValueError("block %d: width %d is outside 1..%d" % (int(np.argmax(bad)), int(d[np.argmax(bad)]), MOMENTS_MAX_D))
+    bad = (off < 0) | (off + d > ne)
+    if np.any(bad):
+        raise ValueError("block %d: entries %d..%d leave the %d entries of the column list"
+                         % (int(np.argmax(bad)), int(off[np.argmax(bad)]), int((off + d)[np.argmax(bad)]), ne))
+    count = int((coff + d * d).max()) if cov_count is None else int(cov_count)
+    bad = (coff < 0) | (coff + d * d > count)
+    if np.any(bad):
+        raise ValueError("block %d: its matrix at %d leaves the %d values of cov" % (int(np.argmax(bad)), int(coff[np.argmax(bad)]), count))
+    if not 0 <= int(cols.min()) <= int(cols.max()) < int(x_rows):
+        raise ValueError("cols: a row is out of range of the %d rows of the matrix" % int(x_rows))
+
+
+def _check_weights(weights, n):
+    """None, or float64 [n] weights (tensor or numpy): non-negative, finite, not all zero.  A device tensor is taken as it is
+    (checking it would read it back): its length and dtype alone are checked."""
+    if weights is None:
+        return None
+    if torch.is_tensor(weights) and weights.is_cuda:
+        if weights.ndim != 1 or int(weights.shape[0]) != n:
+            raise ValueError("weights must be [n] = [%d], got %s" % (n, tuple(weights.shape)))
+        return weights
+    w = weights.detach().numpy() if torch.is_tensor(weights) else np.asarray(weights)
+    if w.ndim != 1 or w.size != n:
+        raise ValueError("weights must be [n] = [%d], got %s" % (n, tuple(w.shape)))
+    w = w.astype(np.float64)
+    if not np.all(np.isfinite(w)) or np.any(w < 0) or not np.any(w > 0):
+        raise ValueError("weights must be finite, non-negative and not all zero")
+    return w
+
+
+def sample_moments(X, blocks: np.ndarray, cols, circular=None, weights=None, device=None):
+    """Means, resultant lengths and covariances of every block of `blocks` over the n rows of X [n, x_cols] (tensor or numpy;
+    float32 points, float64 arithmetic): nfisam_sample_moments, all blocks in one call on the current stream.  `blocks`: numpy
+    MOMENT_BLOCK_DTYPE (`pack_moment_blocks`); entry e is column cols[e] of X; circular [n_entries] marks angles (circular mean
+    in [-pi, pi), residuals wrapped); weights [n] float64 (None: all ones).
+    -> (mean [n_entries], resultant [n_entries] (NaN for a Euclidean entry), cov [sum d^2], block b's row-major d x d matrix
+    at blocks["cov_off"][b]): float64 device tensors."""
+    if device is None:
+        device = X.device if torch.is_tensor(X) else "cuda"
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("sample_moments needs a ROCm device (no CPU path exists)")
+    if not (torch.is_tensor(X) or isinstance(X, np.ndarray)) or X.ndim != 2:
+        raise ValueError("X must be a [rows, cols] tensor or array")
+    if int(X.shape[0]) < 1:
+        raise ValueError("sample_moments: no points")
+    check_moment_blocks(blocks, cols, int(X.shape[1]), circular)
+    weights = _check_weights(weights, int(X.shape[0]))
+    return sample_moments_t(_mmd_matrix(X, "X", device), blocks, cols, circular, weights, checked=True)
+
+
+def sample_moments_t(Xt, blocks: np.ndarray, cols, circular=None, weights=None, checked=False):
+    """`sample_moments` on the COLUMN-major matrix Xt [x_rows, n] (a contiguous float32 device tensor, used in place): what
+    the tree walk wrote.  `checked` skips the table check (the caller has made it)."""
+    if not torch.is_tensor(Xt) or not Xt.is_cuda:
+        raise RuntimeError("Xt must be a tensor on a ROCm device (no CPU path exists)")
+    if Xt.ndim != 2 or Xt.dtype != torch.float32 or not Xt.is_contiguous():
+        raise ValueError("Xt must be a contiguous float32 [rows, points] tensor")
+    device = Xt.device
+    x_rows, n = int(Xt.shape[0]), int(Xt.shape[1])
+    if n < 1:
+        raise ValueError("sample_moments: no points")
+    if not checked:
+        check_moment_blocks(blocks, cols, x_rows, circular)
+        weights = _check_weights(weights, n)
+    nb = int(blocks.shape[0])
+    cc = np.asarray(cols, dtype=np.int32)
+    ne = int(cc.size)
+    d = blocks["d"].astype(np.int64)
+    cov_count = max(int((blocks["cov_off"].astype(np.int64) + d * d).max()), 1)
+    blocks = np.ascontiguousarray(blocks)
+    host = [blocks.view(np.uint8).reshape(-1), cc]
+    if circular is not None:
+        host.append(np.asarray(circular).astype(np.uint8))
+    with torch.cuda.device(device):
+        dev = upload(*host, device=device)
+        ci_d = dev[2] if circular is not None else None
+        w_d = None
+        if weights is not None:
+            w_d = weights.to(device=device, dtype=torch.float64).contiguous() if torch.is_tensor(weights) else \
+                torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float64)).to(device)
+        mean = torch.empty(ne, dtype=torch.float64, device=device)
+        res = torch.empty(ne, dtype=torch.float64, device=device)
+        cov = torch.full((cov_count,), float("nan"), dtype=torch.float64, device=device)
+        _check(lib().nfisam_sample_moments(_ptr(Xt), x_rows, n, blocks.ctypes.data_as(C.c_void_p), C.c_void_p(dev[0].data_ptr()), nb,
+                                           _ptr(dev[1]), ne, _ptr(ci_d), _ptr(w_d), _ptr(mean), _ptr(res), _ptr(cov),
+                                           C.c_longlong(cov_count), _stream()), "nfisam_sample_moments")
+    return mean, res, cov
+
+
+def _check_probs(probs):
+    p = np.asarray(probs, dtype=np.float64)
+    if p.ndim != 1 or p.size < 1:
+        raise ValueError("probs must be a 1-D list of at least one probability")
+    if not np.all((p >= 0.0) & (p <= 1.0)):
+        raise ValueError("a probability is outside [0, 1]: %s" % p[~((p >= 0.0) & (p <= 1.0))][:4])
+    return np.ascontiguousarray(p)
+
+
+def sample_quantiles(X, cols, probs, circular=None, center=None, device=None):
+    """Quantiles at `probs` of the columns `cols` of X [n, x_cols] (tensor or numpy; float64 keys from float32 points):
+    nfisam_sample_quantiles, one workgroup per column sorting in LDS, numpy's "linear" rule.  circular [n_entries] marks
+    angles: their keys are wrap_pi(x - center[e]) (center [n_entries] float64, tensor or numpy: the circular means; None: 0)
+    and center + quantile is returned UNWRAPPED -- wrap it for display.  n <= 16384.  -> [n_entries, n_probs] float64 device
+    tensor."""
+    if device is None:
+        device = X.device if torch.is_tensor(X) else "cuda"
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("sample_quantiles needs a ROCm device (no CPU path exists)")
+    if not (torch.is_tensor(X) or isinstance(X, np.ndarray)) or X.ndim != 2:
+        raise ValueError("X must be a [rows, cols] tensor or array")
+    circular, center = _entry_arrays(circular, center)
+    _check_quantile_args(int(X.shape[0]), int(X.shape[1]), cols, probs, circular, center)
+    return sample_quantiles_t(_mmd_matrix(X, "X", device), cols, probs, circular, center, checked=True)
+
+
+def _entry_arrays(circular, center):
+    if circular is not None:
+        circular = circular.detach().cpu().numpy() if torch.is_tensor(circular) else np.asarray(circular)
+    if center is not None and not torch.is_tensor(center):
+        center = np.asarray(center, dtype=np.float64)
+    return circular, center
+
+
+def _check_quantile_args(n, x_rows, cols, probs, circular, center):
+    cols = np.asarray(cols)
+    if cols.ndim != 1 or cols.size < 1:
+        raise ValueError("cols must be a 1-D list of at least one row")
+    if not 0 <= int(cols.min()) <= int(cols.max()) < int(x_rows):
+        raise ValueError("cols: a row is out of range of the %d rows of the matrix" % int(x_rows))
+    _check_probs(probs)
+    if not 1 <= n <= QUANTILE_MAX_N:
+        raise ValueError("sample_quantiles takes 1..%d points, got %d" % (QUANTILE_MAX_N, n))
+    for name, a in (("circular", circular), ("center", center)):
+        if a is not None and (a.ndim != 1 or int(a.shape[0]) != cols.size):
+            raise ValueError("%s must have one value per entry (%d)" % (name, cols.size))
+
+
+def sample_quantiles_t(Xt, cols, probs, circular=None, center=None, checked=False):
+    """`sample_quantiles` on the COLUMN-major matrix Xt [x_rows, n] (a contiguous float32 device tensor, used in place)."""
+    if not torch.is_tensor(Xt) or not Xt.is_cuda:
+        raise RuntimeError("Xt must be a tensor on a ROCm device (no CPU path exists)")
+    if Xt.ndim != 2 or Xt.dtype != torch.float32 or not Xt.is_contiguous():
+        raise ValueError("Xt must be a contiguous float32 [rows, points] tensor")
+    device = Xt.device
+    x_rows, n = int(Xt.shape[0]), int(Xt.shape[1])
+    circular, center = _entry_arrays(circular, center)
+    if not checked:
+        _check_quantile_args(n, x_rows, cols, probs, circular, center)
+    p = _check_probs(probs)
+    cc = np.asarray(cols, dtype=np.int32)
+    host = [cc, p]
+    if circular is not None:
+        host.append(np.asarray(circular).astype(np.uint8))
+    if center is not None and not torch.is_tensor(center):
+        host.append(np.ascontiguousarray(center, dtype=np.float64))
+    with torch.cuda.device(device):
+        dev = upload(*host, device=device)
+        ci_d = dev[2] if circular is not None else None
+        ce_d = None
+        if center is not None:
+            ce_d = center.to(device=device, dtype=torch.float64).contiguous() if torch.is_tensor(center) else dev[-1]
+        out = torch.empty(int(cc.size), int(p.size), dtype=torch.float64, device=device)
+        _check(lib().nfisam_sample_quantiles(_ptr(Xt), x_rows, n, _ptr(dev[0]), int(cc.size), _ptr(ci_d), _ptr(ce_d),
+                                             p.ctypes.data_as(C.c_void_p), _ptr(dev[1]), int(p.size), _ptr(out), _stream()),
+               "nfisam_sample_quantiles")
+    return out

@@ -1090,6 +1090,158 @@ class NFiSAM(FactorGraphSolver):
                     blocks=[float(x) for x in val[k0 + len(variables):]], floor=float(np.sqrt(1.0 / m + 1.0 / rows)),
                     m=m, n=rows, estimator=estimator)
 
+    # ---- what the posterior says: point estimates, spreads, intervals ---------------------------------------------
+    def posterior_summary(self, samples=None, n: int = None, variables=None, pairs=None, weights=None, quantiles=None,
+                          truth=None) -> dict:
+        """Means, covariances, heading concentrations and quantiles of the posterior, computed on the device from the sample
+        matrix the tree walk left there -- transposed on the device back into the walk's column-major layout, never copied
+        to the host -- (nfisam_sample_moments / nfisam_sample_quantiles: float32 points, float64
+        arithmetic, every variable and pair in one call) -- what the reference does on the host with `sample_mean` and numpy
+        after copying the whole matrix out (src/utils/Statistics.py:142-214 and its run scripts).
+
+        samples=None draws `n` (default posterior_sample_num) points through the tree walk; otherwise `samples` is what
+        `posterior_log_pdf` accepts, nothing is drawn and no solver state is touched.  variables: which to summarise (default:
+        the elimination ordering).  pairs: (a, b) tuples, each summarised as ONE joint block of a.dim + b.dim <= 16 columns.
+        weights: None, an [n] array of non-negative weights, or "importance": the self-normalised importance weights
+        exp(log p - log q - max) of the same matrix (the log w of `posterior_diagnostics`), kept on the device.  quantiles: a
+        list of probabilities (not together with weights; n <= 16384).  truth: variable -> [dim] ground truth.
+        -> dict: mean (variable -> [dim]; a heading's is the circular mean in [-pi, pi)), cov (variable -> [dim, dim]: population
+        form; a heading's deviations are wrapped about its circular mean), resultant (variable -> mean resultant length of its
+        heading, for variables that have one), pair_cov ((a, b) -> matrix), quantiles (variable -> [n_probs, dim], None when not
+        asked for; a heading's are NOT wrapped back into [-pi, pi) so that an interval's ends stay ordered), n, ess
+        ((sum w)^2 / sum w^2; n without weights), and with `truth`, over the summarised variables that `truth` holds:
+        translation_rmse (utils.Statistics.translation_distance of the means), translation_error (variable -> its term, the
+        squared xy distance), geodesic (utils.Statistics.geodesic_distance).
+        Raises RuntimeError when there is nothing to summarise yet; ValueError for an unknown variable, a wrong width, ragged
+        rows, bad weights or probabilities, quantiles with weights or with more than 16384 points, a pair wider than 16 columns
+        -- before anything is launched."""
+        from utils import Statistics as ST
+        what = "posterior_summary"
+        if not self._elimination_ordering:
+            raise RuntimeError("%s: no factor graph yet (run an incremental update first)" % what)
+        importance = isinstance(weights, str)
+        if importance and weights != "importance":
+            raise ValueError("%s: weights is None, an [n] array or 'importance', got %r" % (what, weights))
+        if samples is None or importance:
+            if importance and not self.physical_factors:
+                raise RuntimeError("%s: no factor graph yet (run an incremental update first)" % what)
+            tree = self._physical_bayes_tree
+            if tree is None or tree.root is None:
+                raise RuntimeError("%s: no Bayes tree yet (run an incremental update first)" % what)
+            for clique in tree.clique_ordering():
+                if clique not in self._clique_density_model:
+                    raise RuntimeError("%s: clique %s has no trained model yet" % (what, clique))
+        known = set(self._elimination_ordering)
+        variables = list(self._elimination_ordering) if variables is None else list(variables)
+        pairs = [tuple(p) for p in pairs] if pairs is not None else []
+        if not variables:
+            raise ValueError("%s: no variable to summarise" % what)
+        for p in pairs:
+            if len(p) != 2:
+                raise ValueError("%s: a pair is a tuple (a, b) of two variables" % what)
+        for v in variables + [v for p in pairs for v in p]:
+            if v not in known:
+                raise ValueError("%s: variable %s is not in the elimination ordering" % (what, getattr(v, "name", v)))
+        for a, b in pairs:
+            if a.dim + b.dim > _nh.MOMENTS_MAX_D:
+                raise ValueError("%s: the pair (%s, %s) is %d columns wide; a block holds at most %d"
+                                 % (what, a.name, b.name, a.dim + b.dim, _nh.MOMENTS_MAX_D))
+        probs = None
+        if quantiles is not None:
+            if weights is not None:
+                raise ValueError("%s: quantiles are unweighted; ask for them without weights" % what)
+            probs = np.asarray(quantiles, dtype=np.float64).reshape(-1)
+            if probs.size < 1 or not np.all((probs >= 0.0) & (probs <= 1.0)):
+                raise ValueError("%s: quantiles is a non-empty list of probabilities in [0, 1]" % what)
+        if samples is not None:
+            values, rows = self._check_points(samples, what)
+        else:
+            rows = int(self._args.posterior_sample_num if n is None else n)
+        if rows < 1:
+            raise ValueError("%s: no points" % what)
+        if probs is not None and rows > _nh.QUANTILE_MAX_N:
+            raise ValueError("%s: quantiles take at most %d points, got %d" % (what, _nh.QUANTILE_MAX_N, rows))
+        w_host = None
+        if weights is not None and not importance:
+            w_host = weights.detach().cpu().numpy() if torch.is_tensor(weights) else np.asarray(weights)
+            if w_host.ndim != 1 or w_host.size != rows:
+                raise ValueError("%s: weights must be [n] = [%d], got %s" % (what, rows, tuple(w_host.shape)))
+            w_host = w_host.astype(np.float64)
+            if not np.all(np.isfinite(w_host)) or np.any(w_host < 0) or not np.any(w_host > 0):
+                raise ValueError("%s: weights must be finite, non-negative and not all zero" % what)
+        graded = []
+        if truth is not None:
+            graded = [v for v in variables if v in truth]
+            if not graded:
+                raise ValueError("%s: truth holds none of the summarised variables" % what)
+            for v in graded:
+                if np.ndim(truth[v]) != 1 or len(truth[v]) != v.dim:
+                    raise ValueError("%s: truth of %s must be [%d], got shape %s" % (what, v.name, v.dim, np.shape(truth[v])))
+
+        # the table: every variable, then every pair; entry = one column of the sample matrix
+        pcol, total_dim = self._post_columns()
+        table = [(v,) for v in variables] + pairs
+        cols, circ = [], []
+        for blk in table:
+            for v in blk:
+                cols.extend(pcol[v] + c for c in range(v.dim))
+                circ.extend(bool(c) for c in v.circular_dim_list)
+        cols, circ = np.asarray(cols, dtype=np.int32), np.asarray(circ, dtype=np.uint8)
+        blocks = _nh.pack_moment_blocks([sum(v.dim for v in blk) for blk in table])
+        _nh.check_moment_blocks(blocks, cols, total_dim, circ)
+        flags = circ if circ.any() else None
+        if importance:
+            t = self._posterior_table()
+            self._joint_terms(pcol)                          # (packs: an unknown factor class raises here)
+            device = t["device"]
+        else:
+            device = _device()
+        if samples is None:
+            S = self.posterior_launch(rows)["S"]             # [n, total_dim] on the device: it stays there
+        else:
+            S = self._points_matrix(values, rows, pcol, total_dim, device)
+        St = S.t().contiguous() if torch.is_tensor(S) else torch.from_numpy(np.ascontiguousarray(S.T)).to(device)
+        w_dev, ess = None, float(rows)
+        if importance:
+            K, H, B, L = t["cfg"]
+            log_q = _nh.posterior_log_density(t["table"], t["cols"], t["obs"], S, t["max_D"], K, H, B, L, device)
+            log_w = self._joint_launch(S, pcol, device) - log_q.to(torch.float64)
+            w_dev = torch.exp(log_w - log_w.max())
+            ess = float((w_dev.sum() ** 2 / (w_dev * w_dev).sum()).item())
+            if not np.isfinite(ess):
+                raise ValueError("%s: the importance weights are not finite" % what)
+        elif w_host is not None:
+            w_dev = w_host
+            ess = float(w_host.sum() ** 2 / (w_host * w_host).sum())
+        mean_d, res_d, cov_d = _nh.sample_moments_t(St, blocks, cols, flags, w_dev, checked=True)
+        q = None
+        if probs is not None:
+            nq = sum(v.dim for v in variables)
+            q = _nh.sample_quantiles_t(St, cols[:nq], probs, None if flags is None else circ[:nq], mean_d[:nq], checked=True)
+            q = q.cpu().numpy()
+        mean, res, cov = mean_d.cpu().numpy(), res_d.cpu().numpy(), cov_d.cpu().numpy()
+        out = dict(mean={}, cov={}, resultant={}, pair_cov={}, quantiles=None if q is None else {}, n=rows, ess=ess)
+        for blk, row in zip(table, blocks):
+            o, d, c = int(row["col_off"]), int(row["d"]), int(row["cov_off"])
+            m = cov[c:c + d * d].reshape(d, d).copy()
+            if len(blk) == 2:
+                out["pair_cov"][blk] = m
+                continue
+            v = blk[0]
+            out["mean"][v], out["cov"][v] = mean[o:o + d].copy(), m
+            heading = [k for k, f in enumerate(v.circular_dim_list) if f]
+            if heading:
+                out["resultant"][v] = float(res[o + heading[0]]) if len(heading) == 1 else res[o:o + d][heading].copy()
+            if q is not None:
+                out["quantiles"][v] = q[o:o + d].T.copy()
+        if truth is not None:
+            est = {v: out["mean"][v] for v in graded}
+            ref = {v: np.asarray(truth[v], dtype=np.float64) for v in graded}
+            out["translation_rmse"] = float(ST.translation_distance(est, ref))
+            out["translation_error"] = {v: float(e) for v, e in ST.translation_terms(est, ref).items()}
+            out["geodesic"] = float(ST.geodesic_distance(est, ref))
+        return out
+
     def posterior_collect(self, handle, timer: List = None, copy_stream=None):
         """Second half: wait for the walk, one D2H copy, per-variable views of the sample matrix (in the elimination ordering
         of the launch).  `copy_stream`: copy behind the walk's event on that stream instead of the walk's own (which may

@@ -1,7 +1,9 @@
 """utils.Statistics — maximum mean discrepancy used as the posterior parity metric
 (reference: src/utils/Statistics.py:13-84; the biased estimator `MMDb` with an RBF kernel of
 bandwidth sigma is what the reference's evaluation scripts report,
-example/slam/small_range_gaussian_problem/icra_paper/mmd_rmse_time_da_plot_grid.py:167,245)."""
+example/slam/small_range_gaussian_problem/icra_paper/mmd_rmse_time_da_plot_grid.py:167,245), and the summaries of a
+sample set (reference: src/utils/Statistics.py:142-214): means with circular means for headings, covariances, resultant
+lengths and quantiles on the device, `rmse`, `translation_distance` and `geodesic_distance` on the host."""
 import numpy as np
 
 
@@ -134,3 +136,147 @@ def mmd_blocks(x, y, blocks, estimator: str = "MMDb", sigma=None, scale=None, ci
     table = _nh.pack_mmd_blocks(dims, sig)
     sums = _nh.mmd_sums(x, y, table, xcols, ycols, scale=sc, wrap=wr, device=device)
     return mmd_from_sums(sums.cpu().numpy(), m, n, estimator)
+
+
+# ---- what a sample set says: means, covariances, quantiles on the device (nfisam_sample_moments / nfisam_sample_quantiles) ----
+def _column_blocks(blocks, width):
+    out = []
+    for k, b in enumerate(blocks):
+        c = np.asarray(b, dtype=np.int64)
+        if c.ndim != 1 or c.size < 1:
+            raise ValueError("block %d: a block is a non-empty list of columns" % k)
+        if c.size > 16:
+            raise ValueError("block %d: %d columns; a block holds at most 16 (assemble wider matrices from pair blocks)" % (k, c.size))
+        if c.min() < 0 or c.max() >= width:
+            raise ValueError("block %d names a column outside the %d columns of the sample set" % (k, width))
+        out.append(c)
+    if not out:
+        raise ValueError("no blocks")
+    return out
+
+
+def _column_flags(circular, width):
+    if circular is None:
+        return np.zeros(width, dtype=bool)
+    circular = np.asarray(circular, dtype=bool).reshape(-1)
+    if circular.size != width:
+        raise ValueError("circular: one flag per column of x (%d), got %d" % (width, circular.size))
+    return circular
+
+
+def sample_moments(x, blocks, circular=None, weights=None, device=None):
+    """Mean, covariance and resultant length of the sample set x [n, x_cols] (numpy or torch) restricted to each of `blocks`
+    (lists of at most 16 column indices), all blocks in ONE device call (nfisam_hip.sample_moments: float32 points, float64
+    arithmetic, two passes) -> list of (mean [d], cov [d, d], resultant [d]) float64 numpy arrays, one per block.
+
+    circular [x_cols]: columns that are angles -- their mean is the circular mean in [-pi, pi) (scipy's
+    circmean(high=pi, low=-pi), what the reference's `sample_mean` calls), their residuals are wrapped into [-pi, pi), and
+    `resultant` holds their mean resultant length (NaN for the other columns).  cov is the population form (divided by the
+    sum of the weights); for an angle, the mean squared wrapped deviation about the circular mean.  weights [n]: non-negative,
+    None for all ones.  There is no CPU path."""
+    import nfisam_hip as _nh
+    if np.ndim(x) != 2:
+        raise ValueError("x must be [points, columns]")
+    cols = _column_blocks(blocks, int(x.shape[1]))
+    flags = _column_flags(circular, int(x.shape[1]))
+    flat = np.concatenate(cols)
+    table = _nh.pack_moment_blocks([c.size for c in cols])
+    mean, res, cov = _nh.sample_moments(x, table, flat, circular=flags[flat].astype(np.uint8) if flags.any() else None,
+                                        weights=weights, device=device)
+    mean, res, cov = mean.cpu().numpy(), res.cpu().numpy(), cov.cpu().numpy()
+    out = []
+    for row in table:
+        o, d, c = int(row["col_off"]), int(row["d"]), int(row["cov_off"])
+        out.append((mean[o:o + d], cov[c:c + d * d].reshape(d, d), res[o:o + d]))
+    return out
+
+
+def sample_quantiles(x, probs, circular=None, device=None) -> np.ndarray:
+    """Quantiles at `probs` of every column of x [n, x_cols] (numpy or torch; n <= 16384), numpy's "linear" rule on float64
+    keys, sorted on the device (nfisam_hip.sample_quantiles) -> [n_probs, x_cols] float64.
+    circular [x_cols]: an angle's quantiles are those of its deviations from its circular mean, wrapped into [-pi, pi), added
+    back to that mean and NOT wrapped again: the ends of an interval stay ordered and may lie beyond +-pi -- wrap for display."""
+    import nfisam_hip as _nh
+    if np.ndim(x) != 2:
+        raise ValueError("x must be [points, columns]")
+    width = int(x.shape[1])
+    flags = _column_flags(circular, width)
+    cols = np.arange(width)
+    center = circ = None
+    if flags.any():
+        circ = flags.astype(np.uint8)
+        mean, _, _ = _nh.sample_moments(x, _nh.pack_moment_blocks(np.ones(width, dtype=np.int64)), cols, circular=circ, device=device)
+        center = mean                                              # (on the device; a Euclidean column's centre is not read)
+    q = _nh.sample_quantiles(x, cols, probs, circular=circ, center=center, device=device)
+    return q.cpu().numpy().T.copy()
+
+
+def sample_mean(samples, var_ordering):
+    """The reference's `sample_mean` (src/utils/Statistics.py:151-171) on the device: the mean of every column of samples
+    [n, sum of the variables' dims], circular for the columns the variables flag as angles, arithmetic for the others
+    -> (means [columns], {variable: its slice of means})."""
+    import nfisam_hip as _nh
+    flags = np.array([bool(c) for v in var_ordering for c in v.circular_dim_list], dtype=bool)
+    if np.ndim(samples) != 2 or int(samples.shape[1]) != flags.size:
+        raise ValueError("samples must be [n, %d] for these variables" % flags.size)
+    width = flags.size
+    mean, _, _ = _nh.sample_moments(samples, _nh.pack_moment_blocks(np.ones(width, dtype=np.int64)), np.arange(width),
+                                    circular=flags.astype(np.uint8) if flags.any() else None)
+    means = mean.cpu().numpy()
+    var2mean, at = {}, 0
+    for v in var_ordering:
+        var2mean[v] = means[at:at + v.dim]
+        at += v.dim
+    return means, var2mean
+
+
+def rmse(samples1: np.ndarray, samples2: np.ndarray) -> float:
+    """Root of the mean squared elementwise difference of two equally shaped arrays (reference: :142-148)."""
+    a, b = np.asarray(samples1), np.asarray(samples2)
+    if a.shape != b.shape:
+        raise ValueError("the two sample sets differ in shape: %s and %s" % (a.shape, b.shape))
+    diff = a - b
+    return np.sqrt(np.sum(diff ** 2) / a.size)
+
+
+def _planar(var):
+    from slam.Variables import R2Variable, SE2Variable
+    if isinstance(var, SE2Variable):
+        return "SE2"
+    if isinstance(var, R2Variable):
+        return "R2"
+    raise ValueError("Unknown variable type: %r" % (var,))
+
+
+def translation_terms(var2point1, var2point2) -> dict:
+    """variable -> squared distance between the xy parts of its two points (the terms `translation_distance` averages)."""
+    terms = {}
+    for var in var2point1:
+        _planar(var)
+        a, b = np.asarray(var2point1[var]), np.asarray(var2point2[var])
+        terms[var] = sum((a[:2] - b[:2]) ** 2)
+    return terms
+
+
+def translation_distance(var2point1, var2point2):
+    """sqrt of the mean over the variables of the squared xy distance between two assignments (reference: :204-214): the
+    trajectory RMSE the run scripts report."""
+    terms = translation_terms(var2point1, var2point2)
+    err = 0
+    for var in var2point1:
+        err += terms[var]
+    return np.sqrt(err / len(var2point1))
+
+
+def geodesic_distance(var2point1, var2point2):
+    """sqrt of the summed squared geodesic distances between two assignments (reference: :179-191): |Log(p1 p2^-1)|^2 for a
+    pose (geometry.TwoDimension.SE2Pose), |p1 - p2|^2 for a point."""
+    from geometry.TwoDimension import SE2Pose
+    err = 0
+    for var in var2point1:
+        a, b = var2point1[var], var2point2[var]
+        if _planar(var) == "SE2":
+            err += sum((SE2Pose(*a) / SE2Pose(*b)).log_map() ** 2)
+        else:
+            err += sum((np.asarray(a) - np.asarray(b)) ** 2)
+    return np.sqrt(err)
