@@ -353,6 +353,72 @@ int nfisam_sample_quantiles(const float* Xt, int x_rows, int n, const int32_t* c
                             const double* center, const double* probs, const double* probs_dev, int n_probs, double* out,
                             nfisam_stream_t stream);
 
+/* ---- posterior modes: mean-shift over every block's samples, then a merge (sample_modes.hip) -------------------------------
+ * One mean and one covariance per variable put a bimodal posterior's estimate between its hypotheses (a landmark seen by
+ * range only, a pose under ambiguous data association).  Here every point of the COLUMN-major float32 device matrix
+ * Xt[x_rows][n] climbs the Gaussian kernel density estimate of its block, and the converged points are merged into modes.
+ * The block table is that of nfisam_sample_mmd (entry e names the row cols[e] of Xt; block b is the run of entries
+ * col_off .. col_off + d with its own bandwidth), with 1 <= d <= NFISAM_MODES_MAX_D.  For block b, with w = weights (NULL: all
+ * ones):
+ *     u_e(a, y) = scale_e * wrap_e(a_e - y_e)     (scale NULL: 1; wrap_e brings the difference into [-pi, pi) where wrap[e] is
+ *                                                  set -- the sign convention of theta_to_pipi -- and is the identity otherwise)
+ *     k_j(y)    = w_j * exp(-inv_two_sigma2 * sum_e u_e(x_j, y)^2)
+ * ASCENT, one from every point i, y = x_i:  delta_e = sum_j k_j(y) wrap_e(x_je - y_e) / sum_j k_j(y);  y_e += delta_e, a
+ * wrapped entry brought back into [-pi, pi): one iteration.  It stops when 2 inv_two_sigma2 sum_e (scale_e delta_e)^2 <= tol^2
+ * (a shift of at most `tol` sigmas) or after max_iters iterations.  Where the denominator is 0 (a zero-weight start out of
+ * reach of every weighted point) the start stays where it is, with density 0 and 0 iterations.  The shift form -- not a
+ * weighted mean of coordinates -- is right across the +-pi seam, and a constant column stays exactly where it is (all its
+ * differences are 0).  A column with scale 0 does not enter the distances; it is carried along by the others' weights.
+ * MERGE, deterministic: among the unlabelled starts the one of largest final density (lowest index on ties) founds mode m at
+ * its converged point; every unlabelled start whose converged point is within `merge` sigmas of it
+ * (2 inv_two_sigma2 sum_e u_e^2 <= merge^2) takes label m; until no start is unlabelled or max_modes modes exist.  Starts left
+ * over (and starts of NaN density) keep label -1.  How small `merge` may be is set by the ascent, not by rounding: an ascent
+ * that contracts by a factor r per iteration and stops at a shift of `tol` sigmas is still up to tol * r / (1 - r) sigmas short
+ * of its limit, so members of one mode can end that far apart (1e-5 sigma for tol = 1e-7 and r = 0.99, seen on a uniform
+ * square); a radius below that splits modes.  The default 1e-2 leaves three orders of magnitude.
+ * Outputs (DEVICE arrays):
+ *   pos [n_entries][n]                 converged points, by ENTRY: blocks that share entries share these rows -- give every block
+ *                                      its own entries (rows of Xt may repeat freely)
+ *   dens [n_blocks][n]                 sum_j k_j(y_final) / sum_j w_j
+ *   iters [n_blocks][n] int32          shifts applied; negated when the ascent stopped on max_iters without meeting tol
+ *   labels [n_blocks][n] int32, n_modes [n_blocks] int32, unlabelled [n_blocks] int32
+ *   mode_pos [n_blocks][max_modes][16], mode_dens, mode_mass [n_blocks][max_modes]   (slots >= n_modes: NaN);
+ *                                      mode_mass = sum of w over the members / sum of w over all starts
+ *   blocks[n_blocks]: HOST copy of the table (validated here), blocks_dev: DEVICE copy (what the kernels read); cols [n_entries]
+ *   int32, scale [n_entries] double >= 0 (nullable), wrap [n_entries] uint8 (nullable), weights [n] double >= 0, not all zero
+ *   (nullable): DEVICE arrays.
+ * Float32 points in; every difference, exponent, sum and division is float64, by direct differences.  Two launches, no float
+ * atomics: (1) a 256-thread group per (64 starts, block) runs ALL iterations of its starts -- one start per lane, the four
+ * waves each taking a quarter of every 128-point chunk staged in LDS, the partial sums added in wave order; (2) a group per
+ * block merges.  A start's sums depend on n, its block's rows and flags alone: two calls give the same bits, and a block's
+ * results are the same bits alone, repeated, or anywhere in a table.
+ * NFISAM_ERR_ARG, before any launch: a NULL pointer (scale, wrap and weights excepted), x_rows, n_entries or n_blocks < 1,
+ * n < 0, more than 65535 blocks, a block of the host copy with d outside 1 .. 16 or inv_two_sigma2 not positive and finite,
+ * max_iters < 1, tol < 0, merge <= 0 (or either not finite), max_modes outside 1 .. NFISAM_MODES_MAX_MODES.  n == 0 returns
+ * NFISAM_OK and touches nothing.  The device arrays are not read on the host: a block of the device copy whose entries leave
+ * [0, n_entries), that names a row outside [0, x_rows) or whose d is outside 1 .. 16 gets NaN pos (its entries inside the
+ * table), dens and mode_*, labels -1, iters 0, n_modes 0 and unlabelled n; nothing is read out of bounds and every other
+ * block is untouched -- as long as blocks own their entries: `pos` is stored by entry, so a bad block that shares entries
+ * with a good one (the C entry permits it, the binding does not) overwrites those rows of the good block with NaN, in a race; the Python binding refuses such tables before upload.  (Additive: ABI 1600.) */
+#define NFISAM_MODES_MAX_D      16   /* widest block (the mode table's row length) */
+#define NFISAM_MODES_MAX_MODES  32   /* most modes per block */
+int nfisam_sample_modes(const float* Xt, int x_rows, int n, const nfisam_mmd_block* blocks, const nfisam_mmd_block* blocks_dev,
+                        int n_blocks, const int32_t* cols, int n_entries, const double* scale, const uint8_t* wrap,
+                        const double* weights, int max_iters, double tol, double merge, int max_modes, double* pos, double* dens,
+                        int32_t* iters, int32_t* labels, int32_t* n_modes, double* mode_pos, double* mode_dens, double* mode_mass,
+                        int32_t* unlabelled, nfisam_stream_t stream);
+
+/* The second launch of nfisam_sample_modes alone: `pos` and `dens` of an earlier call (same table, cols, scale, wrap, weights
+ * and n) are merged again -- another radius, another max_modes -- without climbing again; labels, n_modes, mode_* and
+ * unlabelled are rewritten (mode_* sized for THIS max_modes), pos and dens are only read.  The same bits as a full call with
+ * these arguments.  x_rows only serves the row check that marks a bad block.  NFISAM_ERR_ARG as above for the arguments it
+ * shares; n == 0 returns NFISAM_OK and touches nothing.  (Additive: ABI 1600.) */
+int nfisam_sample_modes_merge(int x_rows, int n, const nfisam_mmd_block* blocks, const nfisam_mmd_block* blocks_dev, int n_blocks,
+                              const int32_t* cols, int n_entries, const double* scale, const uint8_t* wrap, const double* weights,
+                              double merge, int max_modes, const double* pos, const double* dens, int32_t* labels,
+                              int32_t* n_modes, double* mode_pos, double* mode_dens, double* mode_mass, int32_t* unlabelled,
+                              nfisam_stream_t stream);
+
 /* ---- training -------------------------------------------------------------------------- */
 /* Vector-Jacobian product of the L-layer flow (what torch autograd computes for
  * `loss.backward()` in slam/NFiSAM.py:474): kgrad[L*kparam_count] += d<gz,z>/dtheta + d<gl,logdet>/dtheta,

@@ -30,6 +30,7 @@ EXPORTS = [
     "nfisam_nsf_posterior_log_density", "nfisam_factor_graph_log_density",
     "nfisam_sample_mmd", "nfisam_sample_mmd_scratch_count",
     "nfisam_sample_moments", "nfisam_sample_quantiles",
+    "nfisam_sample_modes", "nfisam_sample_modes_merge",
 ]
 
 
@@ -87,6 +88,7 @@ class MomentBlock(C.Structure):
 
 assert C.sizeof(MomentBlock) == 16
 MOMENTS_MAX_D, QUANTILE_MAX_N = 16, 16384        # NFISAM_MOMENTS_MAX_D, NFISAM_QUANTILE_MAX_N
+MODES_MAX_D, MODES_MAX_MODES = 16, 32            # NFISAM_MODES_MAX_D, NFISAM_MODES_MAX_MODES
 
 _lib = None
 
@@ -1171,3 +1173,192 @@ def sample_quantiles_t(Xt, cols, probs, circular=None, center=None, checked=Fals
                                              p.ctypes.data_as(C.c_void_p), _ptr(dev[1]), int(p.size), _ptr(out), _stream()),
                "nfisam_sample_quantiles")
     return out
+
+
+# ---- posterior modes: mean-shift over every block's samples, then a merge (nfisam_sample_modes) ---------------------------------
+MODE_KEYS = ("pos", "dens", "iters", "labels", "n_modes", "mode_pos", "mode_dens", "mode_mass", "unlabelled")
+
+
+def check_mode_blocks(blocks: np.ndarray, cols, x_rows: int, scale=None, wrap=None) -> None:
+    """ValueError for tables the kernels must not see: no block or more than 65535, d outside 1..16, a bandwidth term that is
+    not positive and finite, entries outside [0, n_entries), two blocks that share an entry (the converged points are stored
+    by entry: list a column twice instead), a row outside [0, x_rows), per-entry arrays of another length, a scale that is
+    negative or not finite (a device tensor's length alone is checked: checking its values would read it back)."""
+    if not isinstance(blocks, np.ndarray) or blocks.dtype != MMD_BLOCK_DTYPE or blocks.ndim != 1:
+        raise ValueError("blocks must be a 1-D numpy array of MMD_BLOCK_DTYPE")
+    cols = np.asarray(cols)
+    if cols.ndim != 1 or cols.size < 1:
+        raise ValueError("cols must be a 1-D list of at least one row")
+    ne = int(cols.size)
+    for name, a in (("scale", scale), ("wrap", wrap)):
+        if a is not None and (tuple(a.shape) if torch.is_tensor(a) else np.shape(a)) != (ne,):
+            raise ValueError("%s must have one value per entry (%d)" % (name, ne))
+    if not 1 <= blocks.size <= 65535:
+        raise ValueError("1..65535 blocks are supported, got %d" % blocks.size)
+    off, d = blocks["col_off"].astype(np.int64), blocks["d"].astype(np.int64)
+    bad = (d < 1) | (d > MODES_MAX_D)
+    if np.any(bad):
+        raise ValueError("block %d: width %d is outside 1..%d" % (int(np.argmax(bad)), int(d[np.argmax(bad)]), MODES_MAX_D))
+    bad = (off < 0) | (off + d > ne)
+    if np.any(bad):
+        raise ValueError("block %d: entries %d..%d leave the %d entries of the column list"
+                         % (int(np.argmax(bad)), int(off[np.argmax(bad)]), int((off + d)[np.argmax(bad)]), ne))
+    order = np.argsort(off, kind="stable")
+    clash = (off[order][1:] < (off + d)[order][:-1])
+    if np.any(clash):
+        raise ValueError("blocks %d and %d share an entry: the converged points are stored by entry (list the column twice)"
+                         % (int(order[:-1][np.argmax(clash)]), int(order[1:][np.argmax(clash)])))
+    v = blocks["inv_two_sigma2"]
+    if not np.all(np.isfinite(v) & (v > 0)):
+        raise ValueError("block %d: inv_two_sigma2 must be positive and finite" % int(np.argmin(np.isfinite(v) & (v > 0))))
+    if not 0 <= int(cols.min()) <= int(cols.max()) < int(x_rows):
+        raise ValueError("cols: a row is out of range of the %d rows of the matrix" % int(x_rows))
+    if scale is not None and not (torch.is_tensor(scale) and scale.is_cuda):     # (a device tensor is taken as it is)
+        sc = np.asarray(scale, dtype=np.float64)
+        if not np.all(np.isfinite(sc)) or np.any(sc < 0):
+            raise ValueError("scale must be finite and non-negative")
+
+
+def check_mode_args(max_iters, tol, merge, max_modes) -> None:
+    """ValueError for the scalar arguments nfisam_sample_modes refuses."""
+    if int(max_iters) != max_iters or int(max_iters) < 1:
+        raise ValueError("max_iters must be an integer >= 1, got %r" % (max_iters,))
+    if not (np.isfinite(tol) and tol >= 0):
+        raise ValueError("tol must be finite and >= 0 (in sigmas), got %r" % (tol,))
+    if not (np.isfinite(merge) and merge > 0):
+        raise ValueError("merge must be finite and > 0 (in sigmas), got %r" % (merge,))
+    if int(max_modes) != max_modes or not 1 <= int(max_modes) <= MODES_MAX_MODES:
+        raise ValueError("max_modes must be an integer in 1..%d, got %r" % (MODES_MAX_MODES, max_modes))
+
+
+def sample_modes(X, blocks: np.ndarray, cols, scale=None, wrap=None, weights=None, tol=1e-7, merge=1e-2, max_iters=500,
+                 max_modes=16, device=None):
+    """The modes of every block of `blocks` over the n rows of X [n, x_cols] (tensor or numpy; float32 points, float64
+    arithmetic): nfisam_sample_modes -- a mean-shift ascent on the block's Gaussian kernel density estimate from every point,
+    all iterations in one launch, and a deterministic merge of the converged points in a second.  `blocks`: numpy
+    MMD_BLOCK_DTYPE (`pack_mmd_blocks`: widths 1..16 and the bandwidths sigma); entry e is column cols[e] of X; scale
+    [n_entries] >= 0 multiplies an entry's differences in distances (0: the column is ignored there and carried along), wrap
+    [n_entries] marks angles; weights [n] float64 (None: all ones); tol and merge in sigmas.  merge should stay well above
+    tol * r / (1 - r), r the contraction per iteration of the slowest ascent (1e-5 sigma at tol = 1e-7 on a flat density):
+    members of one mode end that far apart, and a smaller radius splits it.
+    -> dict of device tensors: pos [n_entries, n] (converged points), dens [n_blocks, n], iters [n_blocks, n] int32 (negative:
+    stopped on max_iters), labels [n_blocks, n] int32 (-1: left over), n_modes [n_blocks], mode_pos [n_blocks, max_modes, 16],
+    mode_dens, mode_mass [n_blocks, max_modes] (NaN past n_modes), unlabelled [n_blocks]."""
+    if device is None:
+        device = X.device if torch.is_tensor(X) else "cuda"
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("sample_modes needs a ROCm device (no CPU path exists)")
+    if not (torch.is_tensor(X) or isinstance(X, np.ndarray)) or X.ndim != 2:
+        raise ValueError("X must be a [rows, cols] tensor or array")
+    if int(X.shape[0]) < 1:
+        raise ValueError("sample_modes: no points")
+    check_mode_blocks(blocks, cols, int(X.shape[1]), scale, wrap)
+    check_mode_args(max_iters, tol, merge, max_modes)
+    weights = _check_weights(weights, int(X.shape[0]))
+    return sample_modes_t(_mmd_matrix(X, "X", device), blocks, cols, scale, wrap, weights, tol, merge, max_iters, max_modes,
+                          checked=True)
+
+
+def sample_modes_t(Xt, blocks: np.ndarray, cols, scale=None, wrap=None, weights=None, tol=1e-7, merge=1e-2, max_iters=500,
+                   max_modes=16, checked=False, out=None):
+    """`sample_modes` on the COLUMN-major matrix Xt [x_rows, n] (a contiguous float32 device tensor, used in place): what the
+    tree walk wrote.  `checked` skips the table and argument checks (the caller has made them); `out`: the dict of an earlier
+    call with the same shapes, written in place."""
+    if not torch.is_tensor(Xt) or not Xt.is_cuda:
+        raise RuntimeError("Xt must be a tensor on a ROCm device (no CPU path exists)")
+    if Xt.ndim != 2 or Xt.dtype != torch.float32 or not Xt.is_contiguous():
+        raise ValueError("Xt must be a contiguous float32 [rows, points] tensor")
+    device = Xt.device
+    x_rows, n = int(Xt.shape[0]), int(Xt.shape[1])
+    if n < 1:
+        raise ValueError("sample_modes: no points")
+    if not checked:
+        check_mode_blocks(blocks, cols, x_rows, scale, wrap)
+        check_mode_args(max_iters, tol, merge, max_modes)
+        weights = _check_weights(weights, n)
+    nb = int(blocks.shape[0])
+    cc = np.asarray(cols, dtype=np.int32)
+    ne = int(cc.size)
+    blocks = np.ascontiguousarray(blocks)
+    host = [blocks.view(np.uint8).reshape(-1), cc]
+    if scale is not None and not torch.is_tensor(scale):
+        host.append(np.ascontiguousarray(scale, dtype=np.float64))
+    if wrap is not None:
+        host.append(np.asarray(wrap).astype(np.uint8))
+    mm = max(int(max_modes), 1)
+    shapes = dict(pos=((ne, n), torch.float64), dens=((nb, n), torch.float64), iters=((nb, n), torch.int32),
+                  labels=((nb, n), torch.int32), n_modes=((nb,), torch.int32), mode_pos=((nb, mm, MODES_MAX_D), torch.float64),
+                  mode_dens=((nb, mm), torch.float64), mode_mass=((nb, mm), torch.float64), unlabelled=((nb,), torch.int32))
+    with torch.cuda.device(device):
+        dev = upload(*host, device=device)
+        sc_d = None
+        if scale is not None:
+            sc_d = scale.to(device=device, dtype=torch.float64).contiguous() if torch.is_tensor(scale) else dev[2]
+        wr_d = dev[-1] if wrap is not None else None
+        w_d = None
+        if weights is not None:
+            w_d = weights.to(device=device, dtype=torch.float64).contiguous() if torch.is_tensor(weights) else \
+                torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float64)).to(device)
+        if out is None:
+            out = {k: torch.empty(shape, dtype=dt, device=device) for k, (shape, dt) in shapes.items()}
+        else:
+            for k, (shape, dt) in shapes.items():
+                t = out.get(k)
+                if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or t.device != device or not t.is_contiguous():
+                    raise ValueError("out[%r] must be a contiguous %s tensor of shape %s on %s" % (k, dt, shape, device))
+        _check(lib().nfisam_sample_modes(_ptr(Xt), x_rows, n, blocks.ctypes.data_as(C.c_void_p), C.c_void_p(dev[0].data_ptr()), nb,
+                                         _ptr(dev[1]), ne, _ptr(sc_d), _ptr(wr_d), _ptr(w_d), C.c_int(int(max_iters)),
+                                         C.c_double(float(tol)), C.c_double(float(merge)), C.c_int(int(max_modes)),
+                                         *[_ptr(out[k]) for k in MODE_KEYS], _stream()), "nfisam_sample_modes")
+    return out
+
+
+def sample_modes_merge_t(out, x_rows: int, blocks: np.ndarray, cols, scale=None, wrap=None, weights=None, merge=1e-2, max_modes=16,
+                         checked=False):
+    """The merge alone (nfisam_sample_modes_merge): the converged points `out["pos"]` and densities `out["dens"]` of an earlier
+    `sample_modes` / `sample_modes_t` call -- same table, cols, scale, wrap, weights -- merged again with another radius or
+    max_modes, without climbing again.  x_rows: the rows of the matrix the call was made on.  -> a new dict that shares pos,
+    dens and iters with `out`; the same bits as a full call with these arguments."""
+    for k in ("pos", "dens", "iters"):
+        t = out.get(k) if isinstance(out, dict) else None
+        if not torch.is_tensor(t) or not t.is_cuda or t.ndim != 2 or not t.is_contiguous():
+            raise ValueError("out[%r] must be the contiguous device tensor of an earlier sample_modes call" % k)
+    pos, dens = out["pos"], out["dens"]
+    device, n = pos.device, int(pos.shape[1])
+    if not checked:
+        check_mode_blocks(blocks, cols, x_rows, scale, wrap)
+        check_mode_args(1, 0.0, merge, max_modes)
+        weights = _check_weights(weights, n)
+    nb, cc = int(blocks.shape[0]), np.asarray(cols, dtype=np.int32)
+    ne = int(cc.size)
+    if pos.dtype != torch.float64 or dens.dtype != torch.float64 or tuple(pos.shape) != (ne, n) or tuple(dens.shape) != (nb, n) or n < 1:
+        raise ValueError("out does not belong to this table: pos %s, dens %s for %d entries, %d blocks" %
+                         (tuple(pos.shape), tuple(dens.shape), ne, nb))
+    blocks = np.ascontiguousarray(blocks)
+    host = [blocks.view(np.uint8).reshape(-1), cc]
+    if scale is not None and not torch.is_tensor(scale):
+        host.append(np.ascontiguousarray(scale, dtype=np.float64))
+    if wrap is not None:
+        host.append(np.asarray(wrap).astype(np.uint8))
+    mm = max(int(max_modes), 1)
+    with torch.cuda.device(device):
+        dev = upload(*host, device=device)
+        sc_d = None
+        if scale is not None:
+            sc_d = scale.to(device=device, dtype=torch.float64).contiguous() if torch.is_tensor(scale) else dev[2]
+        wr_d = dev[-1] if wrap is not None else None
+        w_d = None
+        if weights is not None:
+            w_d = weights.to(device=device, dtype=torch.float64).contiguous() if torch.is_tensor(weights) else \
+                torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float64)).to(device)
+        res = dict(pos=pos, dens=dens, iters=out["iters"], labels=torch.empty(nb, n, dtype=torch.int32, device=device),
+                   n_modes=torch.empty(nb, dtype=torch.int32, device=device),
+                   mode_pos=torch.empty(nb, mm, MODES_MAX_D, dtype=torch.float64, device=device),
+                   mode_dens=torch.empty(nb, mm, dtype=torch.float64, device=device),
+                   mode_mass=torch.empty(nb, mm, dtype=torch.float64, device=device),
+                   unlabelled=torch.empty(nb, dtype=torch.int32, device=device))
+        _check(lib().nfisam_sample_modes_merge(int(x_rows), n, blocks.ctypes.data_as(C.c_void_p), C.c_void_p(dev[0].data_ptr()), nb,
+                                               _ptr(dev[1]), ne, _ptr(sc_d), _ptr(wr_d), _ptr(w_d), C.c_double(float(merge)),
+                                               C.c_int(int(max_modes)), _ptr(pos), _ptr(dens),
+                                               *[_ptr(res[k]) for k in MODE_KEYS[3:]], _stream()), "nfisam_sample_modes_merge")
+    return res

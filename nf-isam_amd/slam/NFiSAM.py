@@ -1090,33 +1090,9 @@ class NFiSAM(FactorGraphSolver):
                     blocks=[float(x) for x in val[k0 + len(variables):]], floor=float(np.sqrt(1.0 / m + 1.0 / rows)),
                     m=m, n=rows, estimator=estimator)
 
-    # ---- what the posterior says: point estimates, spreads, intervals ---------------------------------------------
-    def posterior_summary(self, samples=None, n: int = None, variables=None, pairs=None, weights=None, quantiles=None,
-                          truth=None) -> dict:
-        """Means, covariances, heading concentrations and quantiles of the posterior, computed on the device from the sample
-        matrix the tree walk left there -- transposed on the device back into the walk's column-major layout, never copied
-        to the host -- (nfisam_sample_moments / nfisam_sample_quantiles: float32 points, float64
-        arithmetic, every variable and pair in one call) -- what the reference does on the host with `sample_mean` and numpy
-        after copying the whole matrix out (src/utils/Statistics.py:142-214 and its run scripts).
-
-        samples=None draws `n` (default posterior_sample_num) points through the tree walk; otherwise `samples` is what
-        `posterior_log_pdf` accepts, nothing is drawn and no solver state is touched.  variables: which to summarise (default:
-        the elimination ordering).  pairs: (a, b) tuples, each summarised as ONE joint block of a.dim + b.dim <= 16 columns.
-        weights: None, an [n] array of non-negative weights, or "importance": the self-normalised importance weights
-        exp(log p - log q - max) of the same matrix (the log w of `posterior_diagnostics`), kept on the device.  quantiles: a
-        list of probabilities (not together with weights; n <= 16384).  truth: variable -> [dim] ground truth.
-        -> dict: mean (variable -> [dim]; a heading's is the circular mean in [-pi, pi)), cov (variable -> [dim, dim]: population
-        form; a heading's deviations are wrapped about its circular mean), resultant (variable -> mean resultant length of its
-        heading, for variables that have one), pair_cov ((a, b) -> matrix), quantiles (variable -> [n_probs, dim], None when not
-        asked for; a heading's are NOT wrapped back into [-pi, pi) so that an interval's ends stay ordered), n, ess
-        ((sum w)^2 / sum w^2; n without weights), and with `truth`, over the summarised variables that `truth` holds:
-        translation_rmse (utils.Statistics.translation_distance of the means), translation_error (variable -> its term, the
-        squared xy distance), geodesic (utils.Statistics.geodesic_distance).
-        Raises RuntimeError when there is nothing to summarise yet; ValueError for an unknown variable, a wrong width, ragged
-        rows, bad weights or probabilities, quantiles with weights or with more than 16384 points, a pair wider than 16 columns
-        -- before anything is launched."""
-        from utils import Statistics as ST
-        what = "posterior_summary"
+    # ---- what posterior_summary and posterior_modes share: arguments, block table, the device matrix and its weights ----
+    def _summary_blocks(self, what, samples, variables, pairs, weights):
+        """The checks that need no points -> (importance, variables, pairs)."""
         if not self._elimination_ordering:
             raise RuntimeError("%s: no factor graph yet (run an incremental update first)" % what)
         importance = isinstance(weights, str)
@@ -1146,50 +1122,46 @@ class NFiSAM(FactorGraphSolver):
             if a.dim + b.dim > _nh.MOMENTS_MAX_D:
                 raise ValueError("%s: the pair (%s, %s) is %d columns wide; a block holds at most %d"
                                  % (what, a.name, b.name, a.dim + b.dim, _nh.MOMENTS_MAX_D))
-        probs = None
-        if quantiles is not None:
-            if weights is not None:
-                raise ValueError("%s: quantiles are unweighted; ask for them without weights" % what)
-            probs = np.asarray(quantiles, dtype=np.float64).reshape(-1)
-            if probs.size < 1 or not np.all((probs >= 0.0) & (probs <= 1.0)):
-                raise ValueError("%s: quantiles is a non-empty list of probabilities in [0, 1]" % what)
+        return importance, variables, pairs
+
+    def _summary_points(self, what, samples, n):
+        """-> (values, rows): the checked points (None when they are to be drawn) and how many there are."""
+        values = None
         if samples is not None:
             values, rows = self._check_points(samples, what)
         else:
             rows = int(self._args.posterior_sample_num if n is None else n)
         if rows < 1:
             raise ValueError("%s: no points" % what)
-        if probs is not None and rows > _nh.QUANTILE_MAX_N:
-            raise ValueError("%s: quantiles take at most %d points, got %d" % (what, _nh.QUANTILE_MAX_N, rows))
-        w_host = None
-        if weights is not None and not importance:
-            w_host = weights.detach().cpu().numpy() if torch.is_tensor(weights) else np.asarray(weights)
-            if w_host.ndim != 1 or w_host.size != rows:
-                raise ValueError("%s: weights must be [n] = [%d], got %s" % (what, rows, tuple(w_host.shape)))
-            w_host = w_host.astype(np.float64)
-            if not np.all(np.isfinite(w_host)) or np.any(w_host < 0) or not np.any(w_host > 0):
-                raise ValueError("%s: weights must be finite, non-negative and not all zero" % what)
-        graded = []
-        if truth is not None:
-            graded = [v for v in variables if v in truth]
-            if not graded:
-                raise ValueError("%s: truth holds none of the summarised variables" % what)
-            for v in graded:
-                if np.ndim(truth[v]) != 1 or len(truth[v]) != v.dim:
-                    raise ValueError("%s: truth of %s must be [%d], got shape %s" % (what, v.name, v.dim, np.shape(truth[v])))
+        return values, rows
 
-        # the table: every variable, then every pair; entry = one column of the sample matrix
-        pcol, total_dim = self._post_columns()
+    @staticmethod
+    def _summary_weights(what, weights, importance, rows):
+        """-> the checked [rows] float64 host weights, None without weights or for "importance"."""
+        if weights is None or importance:
+            return None
+        w_host = weights.detach().cpu().numpy() if torch.is_tensor(weights) else np.asarray(weights)
+        if w_host.ndim != 1 or w_host.size != rows:
+            raise ValueError("%s: weights must be [n] = [%d], got %s" % (what, rows, tuple(w_host.shape)))
+        w_host = w_host.astype(np.float64)
+        if not np.all(np.isfinite(w_host)) or np.any(w_host < 0) or not np.any(w_host > 0):
+            raise ValueError("%s: weights must be finite, non-negative and not all zero" % what)
+        return w_host
+
+    @staticmethod
+    def _summary_table(variables, pairs, pcol):
+        """-> (table, cols, circ): every variable, then every pair; entry = one column of the sample matrix."""
         table = [(v,) for v in variables] + pairs
         cols, circ = [], []
         for blk in table:
             for v in blk:
                 cols.extend(pcol[v] + c for c in range(v.dim))
                 circ.extend(bool(c) for c in v.circular_dim_list)
-        cols, circ = np.asarray(cols, dtype=np.int32), np.asarray(circ, dtype=np.uint8)
-        blocks = _nh.pack_moment_blocks([sum(v.dim for v in blk) for blk in table])
-        _nh.check_moment_blocks(blocks, cols, total_dim, circ)
-        flags = circ if circ.any() else None
+        return table, np.asarray(cols, dtype=np.int32), np.asarray(circ, dtype=np.uint8)
+
+    def _summary_matrix(self, what, samples, values, rows, importance, w_host, pcol, total_dim):
+        """The points where the kernels read them -> (St [total_dim, n] column-major on the device, weights (None, host array
+        or device tensor), ess)."""
         if importance:
             t = self._posterior_table()
             self._joint_terms(pcol)                          # (packs: an unknown factor class raises here)
@@ -1213,6 +1185,63 @@ class NFiSAM(FactorGraphSolver):
         elif w_host is not None:
             w_dev = w_host
             ess = float(w_host.sum() ** 2 / (w_host * w_host).sum())
+        return St, w_dev, ess
+
+    # ---- what the posterior says: point estimates, spreads, intervals ---------------------------------------------
+    def posterior_summary(self, samples=None, n: int = None, variables=None, pairs=None, weights=None, quantiles=None,
+                          truth=None) -> dict:
+        """Means, covariances, heading concentrations and quantiles of the posterior, computed on the device from the sample
+        matrix the tree walk left there -- transposed on the device back into the walk's column-major layout, never copied
+        to the host -- (nfisam_sample_moments / nfisam_sample_quantiles: float32 points, float64
+        arithmetic, every variable and pair in one call) -- what the reference does on the host with `sample_mean` and numpy
+        after copying the whole matrix out (src/utils/Statistics.py:142-214 and its run scripts).
+
+        samples=None draws `n` (default posterior_sample_num) points through the tree walk; otherwise `samples` is what
+        `posterior_log_pdf` accepts, nothing is drawn and no solver state is touched.  variables: which to summarise (default:
+        the elimination ordering).  pairs: (a, b) tuples, each summarised as ONE joint block of a.dim + b.dim <= 16 columns.
+        weights: None, an [n] array of non-negative weights, or "importance": the self-normalised importance weights
+        exp(log p - log q - max) of the same matrix (the log w of `posterior_diagnostics`), kept on the device.  quantiles: a
+        list of probabilities (not together with weights; n <= 16384).  truth: variable -> [dim] ground truth.
+        -> dict: mean (variable -> [dim]; a heading's is the circular mean in [-pi, pi)), cov (variable -> [dim, dim]: population
+        form; a heading's deviations are wrapped about its circular mean), resultant (variable -> mean resultant length of its
+        heading, for variables that have one), pair_cov ((a, b) -> matrix), quantiles (variable -> [n_probs, dim], None when not
+        asked for; a heading's are NOT wrapped back into [-pi, pi) so that an interval's ends stay ordered), n, ess
+        ((sum w)^2 / sum w^2; n without weights), and with `truth`, over the summarised variables that `truth` holds:
+        translation_rmse (utils.Statistics.translation_distance of the means), translation_error (variable -> its term, the
+        squared xy distance), geodesic (utils.Statistics.geodesic_distance).
+        Raises RuntimeError when there is nothing to summarise yet; ValueError for an unknown variable, a wrong width, ragged
+        rows, bad weights or probabilities, quantiles with weights or with more than 16384 points, a pair wider than 16 columns
+        -- before anything is launched."""
+        from utils import Statistics as ST
+        what = "posterior_summary"
+        importance, variables, pairs = self._summary_blocks(what, samples, variables, pairs, weights)
+        probs = None
+        if quantiles is not None:
+            if weights is not None:
+                raise ValueError("%s: quantiles are unweighted; ask for them without weights" % what)
+            probs = np.asarray(quantiles, dtype=np.float64).reshape(-1)
+            if probs.size < 1 or not np.all((probs >= 0.0) & (probs <= 1.0)):
+                raise ValueError("%s: quantiles is a non-empty list of probabilities in [0, 1]" % what)
+        values, rows = self._summary_points(what, samples, n)
+        if probs is not None and rows > _nh.QUANTILE_MAX_N:
+            raise ValueError("%s: quantiles take at most %d points, got %d" % (what, _nh.QUANTILE_MAX_N, rows))
+        w_host = self._summary_weights(what, weights, importance, rows)
+        graded = []
+        if truth is not None:
+            graded = [v for v in variables if v in truth]
+            if not graded:
+                raise ValueError("%s: truth holds none of the summarised variables" % what)
+            for v in graded:
+                if np.ndim(truth[v]) != 1 or len(truth[v]) != v.dim:
+                    raise ValueError("%s: truth of %s must be [%d], got shape %s" % (what, v.name, v.dim, np.shape(truth[v])))
+
+        # the table: every variable, then every pair; entry = one column of the sample matrix
+        pcol, total_dim = self._post_columns()
+        table, cols, circ = self._summary_table(variables, pairs, pcol)
+        blocks = _nh.pack_moment_blocks([sum(v.dim for v in blk) for blk in table])
+        _nh.check_moment_blocks(blocks, cols, total_dim, circ)
+        flags = circ if circ.any() else None
+        St, w_dev, ess = self._summary_matrix(what, samples, values, rows, importance, w_host, pcol, total_dim)
         mean_d, res_d, cov_d = _nh.sample_moments_t(St, blocks, cols, flags, w_dev, checked=True)
         q = None
         if probs is not None:
@@ -1240,6 +1269,62 @@ class NFiSAM(FactorGraphSolver):
             out["translation_rmse"] = float(ST.translation_distance(est, ref))
             out["translation_error"] = {v: float(e) for v, e in ST.translation_terms(est, ref).items()}
             out["geodesic"] = float(ST.geodesic_distance(est, ref))
+        return out
+
+    # ---- which hypotheses the posterior holds: modes, their masses, who belongs to which -----------------------------
+    def posterior_modes(self, samples=None, n: int = None, variables=None, pairs=None, weights=None, sigma=None, tol=1e-7,
+                        merge=1e-2, max_iters=500, max_modes=16) -> dict:
+        """The modes of every variable's marginal posterior, found on the device from the sample matrix the tree walk left
+        there (nfisam_sample_modes: from every sample a mean-shift ascent on the Gaussian kernel density estimate of the
+        variable's own samples, then a deterministic merge of the converged points; float32 points, float64 arithmetic, every
+        variable and pair in one call).  Where `posterior_summary` reports one mean between the hypotheses of a bimodal
+        variable, this reports each hypothesis, its mass and its members.
+
+        samples, n, variables, pairs and weights are those of `posterior_summary` (a pair (a, b) is ONE joint block of
+        a.dim + b.dim <= 16 columns; weights: None, an [n] array or "importance").  Columns are standardised by their
+        (weighted) spread -- the circular standard deviation for a heading, whose differences are wrapped: a mode may sit across
+        the +-pi seam -- and a column without spread is ignored.  sigma: one bandwidth or one per block (variables, then pairs)
+        in those units; None: Scott's rule ess^(-1 / (dim + 4)).  tol, merge: in sigmas; max_modes <= 32.
+        Every bump of the density estimate is a mode: with Scott's rule a near-Gaussian marginal of some hundred samples has
+        small ones in its tails, and
+        ascents there can run into max_iters.  Read `mass` before counting hypotheses and `not_converged` before trusting a
+        position; a larger `sigma` smooths the bumps away.
+        -> dict: modes (variable -> list of {position [dim], mass, density}, by falling density), pair_modes ((a, b) -> list),
+        labels (variable -> device int32 [n]: the mode of every sample, -1 for one left over when max_modes was reached), n,
+        ess, sigma (variable or pair -> the bandwidth used), not_converged (variable or pair -> ascents that stopped on
+        max_iters), unlabelled (variable or pair -> count).
+        It changes no solver state and draws random numbers only when `samples` is None.  Raises what `posterior_summary`
+        raises, and ValueError for a bad sigma, tol, merge, max_iters or max_modes -- before anything is launched."""
+        from utils import Statistics as ST
+        what = "posterior_modes"
+        importance, variables, pairs = self._summary_blocks(what, samples, variables, pairs, weights)
+        try:
+            sigma, _ = ST.check_mode_options(len(variables) + len(pairs), 1, sigma, None, tol, merge, max_iters, max_modes)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (what, e)) from None
+        values, rows = self._summary_points(what, samples, n)
+        w_host = self._summary_weights(what, weights, importance, rows)
+        pcol, total_dim = self._post_columns()
+        table, cols, circ = self._summary_table(variables, pairs, pcol)
+        St, w_dev, ess = self._summary_matrix(what, samples, values, rows, importance, w_host, pcol, total_dim)
+        flags = np.zeros(total_dim, dtype=bool)
+        flags[cols] = circ != 0
+        blocks, at = [], 0
+        for blk in table:
+            d = sum(v.dim for v in blk)
+            blocks.append(cols[at:at + d])
+            at += d
+        res = ST.sample_modes_t(St, blocks, circular=flags, weights=w_dev, sigma=sigma, tol=tol, merge=merge,
+                                max_iters=max_iters, max_modes=max_modes, checked=True)
+        out = dict(modes={}, pair_modes={}, labels={}, n=rows, ess=ess, sigma={}, not_converged={}, unlabelled={})
+        for b, blk in enumerate(table):
+            key = blk if len(blk) == 2 else blk[0]
+            out["pair_modes" if len(blk) == 2 else "modes"][key] = res["modes"][b]
+            if len(blk) == 1:
+                out["labels"][key] = res["labels"][b]
+            out["sigma"][key] = float(res["sigma"][b])
+            out["not_converged"][key] = int(res["iterations"]["not_converged"][b])
+            out["unlabelled"][key] = int(res["unlabelled"][b])
         return out
 
     def posterior_collect(self, handle, timer: List = None, copy_stream=None):

@@ -3,7 +3,8 @@
 bandwidth sigma is what the reference's evaluation scripts report,
 example/slam/small_range_gaussian_problem/icra_paper/mmd_rmse_time_da_plot_grid.py:167,245), and the summaries of a
 sample set (reference: src/utils/Statistics.py:142-214): means with circular means for headings, covariances, resultant
-lengths and quantiles on the device, `rmse`, `translation_distance` and `geodesic_distance` on the host."""
+lengths and quantiles on the device, the modes of a multi-modal sample set (mean-shift on the device), `rmse`,
+`translation_distance` and `geodesic_distance` on the host."""
 import numpy as np
 
 
@@ -209,6 +210,138 @@ def sample_quantiles(x, probs, circular=None, device=None) -> np.ndarray:
         center = mean                                              # (on the device; a Euclidean column's centre is not read)
     q = _nh.sample_quantiles(x, cols, probs, circular=circ, center=center, device=device)
     return q.cpu().numpy().T.copy()
+
+
+# ---- which hypotheses a sample set holds: mean-shift modes on the device (nfisam_sample_modes) ---------------------------------
+def effective_sample_size(weights, n: int) -> float:
+    """(sum w)^2 / sum w^2 of non-negative weights (numpy, or a torch tensor: reduced where it lies); n for None."""
+    if weights is None:
+        return float(n)
+    if hasattr(weights, "is_cuda"):
+        w = weights.double()
+        return float((w.sum() ** 2 / (w * w).sum()).item())
+    w = np.asarray(weights, dtype=np.float64)
+    return float(w.sum() ** 2 / (w * w).sum())
+
+
+def mode_scale(variance, resultant, circular) -> np.ndarray:
+    """The factor on a column's differences that standardises it: 1 / spread, with spread the population standard deviation
+    sqrt(variance) of a Euclidean column and the circular standard deviation sqrt(-2 ln R) of an angle (R its mean resultant
+    length); 0 where the spread is 0 (or not finite: R = 0): the column is ignored in distances and stays where it is."""
+    variance, resultant = np.asarray(variance, dtype=np.float64), np.asarray(resultant, dtype=np.float64)
+    circular = np.asarray(circular, dtype=bool)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        spread = np.where(circular, np.sqrt(np.maximum(-2.0 * np.log(np.where(circular, resultant, 1.0)), 0.0)),
+                          np.sqrt(np.maximum(variance, 0.0)))
+        return np.where((spread > 0) & np.isfinite(spread), 1.0 / spread, 0.0)
+
+
+def mode_sigma(n_eff: float, dims) -> np.ndarray:
+    """Scott's rule on standardised columns: sigma_b = n_eff^(-1 / (d_b + 4))."""
+    return float(n_eff) ** (-1.0 / (np.asarray(dims, dtype=np.float64) + 4.0))
+
+
+def check_mode_options(n_blocks, width, sigma, scale, tol, merge, max_iters, max_modes):
+    """ValueError for a bad sigma (one positive bandwidth, or one per block), scale (one finite value >= 0 per column) or
+    scalar argument -> (sigma [n_blocks] or None, scale [width] or None)."""
+    import nfisam_hip as _nh
+    _nh.check_mode_args(max_iters, tol, merge, max_modes)
+    if sigma is not None:
+        sigma = np.broadcast_to(np.asarray(sigma, dtype=np.float64).reshape(-1), (n_blocks,)).copy() if np.size(sigma) == 1 else \
+            np.asarray(sigma, dtype=np.float64).reshape(-1)
+        if sigma.size != n_blocks or not np.all(np.isfinite(sigma) & (sigma > 0)):
+            raise ValueError("sigma is one positive bandwidth, or one per block (%d)" % n_blocks)
+    if scale is not None:
+        scale = np.asarray(scale, dtype=np.float64).reshape(-1)
+        if scale.size != width or not np.all(np.isfinite(scale)) or np.any(scale < 0):
+            raise ValueError("scale: one finite value >= 0 per column of x (%d)" % width)
+    return sigma, scale
+
+
+def sample_modes_t(Xt, blocks, circular=None, weights=None, sigma=None, scale=None, tol=1e-7, merge=1e-2, max_iters=500,
+                   max_modes=16, checked=False) -> dict:
+    """`sample_modes` on the COLUMN-major device matrix Xt [x_cols, n] (contiguous float32, used in place: what the tree walk
+    wrote); `blocks` name rows of Xt, `circular` and `scale` have one value per row, `weights` is None, numpy or a device
+    tensor.  `checked`: the caller has made every check (blocks, options, weights), none is repeated.  `labels` stay on the
+    device."""
+    import nfisam_hip as _nh
+    width, n = int(Xt.shape[0]), int(Xt.shape[1])
+    if n < 1:
+        raise ValueError("sample_modes: no points")
+    if checked:
+        cols = [np.asarray(b, dtype=np.int64) for b in blocks]
+        flags = np.zeros(width, dtype=bool) if circular is None else np.asarray(circular, dtype=bool).reshape(-1)
+        sigma = None if sigma is None else np.broadcast_to(np.asarray(sigma, dtype=np.float64).reshape(-1), (len(cols),)).copy()
+        scale = None if scale is None else np.asarray(scale, dtype=np.float64).reshape(-1)
+    else:
+        cols = _column_blocks(blocks, width)
+        flags = _column_flags(circular, width)
+        sigma, scale = check_mode_options(len(cols), width, sigma, scale, tol, merge, max_iters, max_modes)
+        weights = _nh._check_weights(weights, n)
+    flat = np.concatenate(cols)
+    dims = np.array([c.size for c in cols])
+    n_eff = effective_sample_size(weights, n)
+    if scale is None:
+        used = np.unique(flat)
+        mean, res, cov = _nh.sample_moments_t(Xt, _nh.pack_moment_blocks(np.ones(used.size, dtype=np.int64)), used,
+                                              flags[used].astype(np.uint8) if flags[used].any() else None, weights, checked=True)
+        scale = np.zeros(width)
+        scale[used] = mode_scale(cov.cpu().numpy(), res.cpu().numpy(), flags[used])
+    if sigma is None:
+        sigma = mode_sigma(n_eff, dims)
+    table = _nh.pack_mmd_blocks(dims, sigma)
+    wrap = flags[flat].astype(np.uint8)
+    raw = _nh.sample_modes_t(Xt, table, flat, scale[flat], wrap if wrap.any() else None, weights, tol, merge, max_iters, max_modes,
+                             checked=True)
+    n_modes = raw["n_modes"].cpu().numpy()
+    mpos, mdens, mmass = raw["mode_pos"].cpu().numpy(), raw["mode_dens"].cpu().numpy(), raw["mode_mass"].cpu().numpy()
+    its = raw["iters"]
+    modes = [[dict(position=mpos[b, m, :int(dims[b])].copy(), mass=float(mmass[b, m]), density=float(mdens[b, m]))
+              for m in range(int(n_modes[b]))] for b in range(len(cols))]
+    return dict(modes=modes, labels=raw["labels"],
+                iterations=dict(max=its.abs().max(dim=1).values.cpu().numpy(), not_converged=(its < 0).sum(dim=1).cpu().numpy()),
+                unlabelled=raw["unlabelled"].cpu().numpy(), sigma=np.asarray(sigma, dtype=np.float64), scale=scale, n_eff=n_eff,
+                raw=raw)
+
+
+def sample_modes(x, blocks, circular=None, weights=None, sigma=None, scale=None, tol=1e-7, merge=1e-2, max_iters=500, max_modes=16,
+                 device=None) -> dict:
+    """The modes of the sample set x [n, x_cols] (numpy or torch) restricted to each of `blocks` (lists of at most 16 column
+    indices): from every point a mean-shift ascent on the block's Gaussian kernel density estimate, then a deterministic merge
+    of the converged points -- all blocks in ONE device call (nfisam_hip.sample_modes_t: float32 points, float64 arithmetic).
+
+    circular [x_cols]: columns that are angles (differences wrapped into [-pi, pi): a mode may sit across the +-pi seam).
+    weights [n]: non-negative, None for all ones.  scale [x_cols]: the factor on a column's differences; None: 1 / spread, the
+    weighted population standard deviation of the column from `nfisam_hip.sample_moments_t` (the circular standard deviation
+    sqrt(-2 ln R) of an angle), 0 for a column without spread, which is then ignored in distances and keeps its value exactly.
+    sigma: one bandwidth or one per block, in those standardised units; None: Scott's rule n_eff^(-1 / (d + 4)) with
+    n_eff = (sum w)^2 / sum w^2.  tol, merge: in sigmas: an ascent stops at a shift of at most `tol`, converged points within
+    `merge` of a mode join it (keep merge well above tol * r / (1 - r), r the slowest ascent's contraction per iteration -- 1e-5
+    sigma at the default tol on a flat density --: members of one mode end that far apart).  At most max_modes (<= 32) modes per
+    block, by falling density.  The rule finds every bump of the density estimate: a near-Gaussian sample of some hundred points
+    has small ones in its tails, so read `mass` before counting hypotheses, and `iterations` for ascents that did not converge.
+    -> dict: modes (per block a list of {position [d], mass, density}), labels ([n_blocks, n] int32, -1 for a point left over
+    when max_modes was reached; left on the device when x was a device tensor), iterations ({max, not_converged}: per block),
+    unlabelled (per block), sigma (per block), scale (per column), n_eff, raw (the device tensors of nfisam_hip.sample_modes_t).
+    Every ValueError is raised before anything is launched.  There is no CPU path."""
+    import nfisam_hip as _nh
+    if np.ndim(x) != 2:
+        raise ValueError("x must be [points, columns]")
+    n, width = int(x.shape[0]), int(x.shape[1])
+    if n < 1:
+        raise ValueError("sample_modes: no points")
+    cols = _column_blocks(blocks, width)
+    flags = _column_flags(circular, width)
+    sigma, scale = check_mode_options(len(cols), width, sigma, scale, tol, merge, max_iters, max_modes)
+    weights = _nh._check_weights(weights, n)
+    on_device = hasattr(x, "is_cuda") and x.is_cuda
+    if device is None:
+        device = x.device if on_device else "cuda"
+    out = sample_modes_t(_nh._mmd_matrix(x, "x", device), cols, flags, weights, sigma, scale, tol, merge, max_iters, max_modes,
+                         checked=True)
+    if not on_device:
+        out["labels"] = out["labels"].cpu().numpy()
+    return out
 
 
 def sample_mean(samples, var_ordering):
