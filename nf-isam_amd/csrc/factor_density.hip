@@ -20,23 +20,15 @@
 #include <stdint.h>
 
 #include "../../include/nfisam_hip.h"
-
-extern thread_local int nfisam_g_last_hip_error;      // defined in the common unit
+#include "sample_common.h"
 
 namespace {
+
+using namespace sample_common;
 
 constexpr int FAC_RUN = 8;        // factors per wave in the first pass
 constexpr int SUM_WAVES = 16;     // second pass: waves per 64-point tile ...
 constexpr int SUM_ROWS = 8;       // ... and rows each of them has in flight per stage (16 x 8 x 64 doubles = 64 KB of LDS)
-constexpr double TWO_PI = 6.283185307179586476925286766559;
-constexpr double PI = 3.141592653589793238462643383279;
-
-// (t + pi) mod 2 pi - pi with the sign of Python's `%` (utils/Functions.py:20-21 theta_to_pipi): [-pi, pi)
-__device__ __forceinline__ double wrap_pi(double t) {
-    double m = fmod(t + PI, TWO_PI);
-    if (m < 0.0) m += TWO_PI;
-    return m - PI;
-}
 
 // log N(Log(dT); 0, Sigma) + log|det dLog| for dT = (tx, ty, w); p[3..8] = upper triangle of the precision, p[9] = log normaliser.
 // Log: v = V^-1(w) t with V^-1 = [[a, w/2], [-w/2, a]], a = (w/2) cot(w/2) (the half-angle form of
@@ -202,23 +194,13 @@ extern "C" int nfisam_factor_graph_log_density(const nfisam_factor_term* terms, 
     if (n == 0) return NFISAM_OK;
     hipStream_t s = (hipStream_t)stream;
     hipError_t e;
-    if (n_terms == 0) {                                        // the empty graph: log p = 0
-        e = hipMemsetAsync(log_p, 0, (size_t)n * sizeof(double), s);
-        if (e != hipSuccess) {
-            nfisam_g_last_hip_error = (int)e;
-            return NFISAM_ERR_LAUNCH;
-        }
-        return NFISAM_OK;
-    }
+    if (n_terms == 0)                                          // the empty graph: log p = 0
+        return launch_status(hipMemsetAsync(log_p, 0, (size_t)n * sizeof(double), s));
     double* per = per_factor;
     if (per == nullptr) {
         e = hipMallocAsync((void**)&per, (size_t)n_terms * n * sizeof(double), s);
-        if (e != hipSuccess) {
-            nfisam_g_last_hip_error = (int)e;
-            return NFISAM_ERR_LAUNCH;
-        }
+        if (e != hipSuccess) return launch_status(e);
     }
-    int rc = NFISAM_OK;
     const int tiles = (n + 63) / 64;
     hipLaunchKernelGGL(factor_terms_kernel, dim3(tiles, (n_terms + FAC_RUN - 1) / FAC_RUN), dim3(64), 0, s, terms, n_terms, St,
                        total_dim, n, per);
@@ -227,16 +209,10 @@ extern "C" int nfisam_factor_graph_log_density(const nfisam_factor_term* terms, 
         hipLaunchKernelGGL(factor_sum_kernel, dim3(tiles), dim3(64 * SUM_WAVES), 0, s, per, n_terms, n, log_p);
         e = hipGetLastError();
     }
-    if (e != hipSuccess) {
-        nfisam_g_last_hip_error = (int)e;
-        rc = NFISAM_ERR_LAUNCH;
-    }
+    int rc = launch_status(e);
     if (per_factor == nullptr) {
         e = hipFreeAsync(per, s);
-        if (e != hipSuccess && rc == NFISAM_OK) {
-            nfisam_g_last_hip_error = (int)e;
-            rc = NFISAM_ERR_LAUNCH;
-        }
+        if (rc == NFISAM_OK) rc = launch_status(e);
     }
     return rc;
 }

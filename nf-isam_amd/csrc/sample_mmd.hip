@@ -10,13 +10,13 @@
 // The estimators (MMDb, MMDu2, the reference's `mmd`) are formed from the three sums on the host.
 //
 // Numerics: float32 points in; differences, squared distance, exp and every sum are float64 (the contract of
-// factor_density.hip).  Direct differences, never the Gram identity |x|^2 + |y|^2 - 2 x.y, which cancels at coordinates of
+// sample_common.h).  Direct differences, never the Gram identity |x|^2 + |y|^2 - 2 x.y, which cancels at coordinates of
 // 100 m; MMD^2 is a small difference of O(1) means, so float32 kernel values would cost three digits of it.
 //
 // Two launches, no float atomics.  (1) a 256-thread group owns a 64 x 64 tile of pairs of one block and one of the three
 // sums: a lane keeps its own i and 16 j (16 double accumulators of squared distance) and walks the block's columns in chunks
 // of 16; the i side is read coalesced from the column-major matrix, the j side is staged as a [16][64] double tile in LDS and
-// read by broadcast; then 16 exp, the lane's sum in j order, a fixed shuffle tree, the four waves in order, one store to
+// read by broadcast; then 16 exp, the lane's sum in j order, wave_sum, the four waves in order, one store to
 // partial[b][tile].  Sxx and Syy visit the upper triangle of tiles and count the off-diagonal ones twice (exact).  (2) one
 // wave per (block, sum) adds the tile partials in an order that depends on (m, n) alone.  The block index is blockIdx.y and
 // everything a block brings (its columns, bandwidth, scale, wrap flags) is wave-uniform.  Hence: two calls give the same
@@ -26,23 +26,15 @@
 #include <stdint.h>
 
 #include "../../include/nfisam_hip.h"
-
-extern thread_local int nfisam_g_last_hip_error;      // defined in the common unit
+#include "sample_common.h"
 
 namespace {
+
+using namespace sample_common;
 
 constexpr int TILE = 64;          // pairs tile: 64 i (one per lane) x 64 j (16 per wave-lane, 4 waves)
 constexpr int JPL = 16;           // j per lane
 constexpr int CH = 16;            // columns per staged chunk
-constexpr double TWO_PI = 6.283185307179586476925286766559;
-constexpr double PI = 3.141592653589793238462643383279;
-
-// (t + pi) mod 2 pi - pi with the sign of Python's `%`: [-pi, pi)  (wrap_pi of factor_density.hip)
-__device__ __forceinline__ double wrap_pi(double t) {
-    double m = fmod(t + PI, TWO_PI);
-    if (m < 0.0) m += TWO_PI;
-    return m - PI;
-}
 
 // tiles of the upper triangle (tj >= ti) of a T x T grid are numbered row by row; row ti starts at tri_off(ti, T)
 __host__ __device__ __forceinline__ long long tri_off(long long ti, long long T) { return ti * T - ti * (ti - 1) / 2; }
@@ -56,12 +48,6 @@ __device__ __forceinline__ void tri_decode(long long t, int T, int* ti_out, int*
     while (ti > 0 && tri_off(ti, T) > t) --ti;
     *ti_out = (int)ti;
     *tj_out = (int)(ti + (t - tri_off(ti, T)));
-}
-
-__device__ __forceinline__ double wave_sum(double v) {           // a fixed tree: the same order in every wave of every call
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;                                                      // (lane 0 holds the sum)
 }
 
 template <bool WRAP, bool SCALE>
@@ -180,7 +166,7 @@ __global__ void __launch_bounds__(256) mmd_tile_kernel(const nfisam_mmd_block* _
     if (lane == 0) wsum[w] = s, bad_any[w] = bad ? 1 : 0;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double tot = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+        const double tot = waves_in_order(wsum);
         const bool any = (bad_any[0] | bad_any[1] | bad_any[2] | bad_any[3]) != 0;
         partial[(size_t)b * (size_t)tiles_total + (size_t)t] = any ? (double)NAN : weight * tot;
     }
@@ -244,9 +230,5 @@ extern "C" int nfisam_sample_mmd(const float* Xt, int x_rows, int m, const float
         hipLaunchKernelGGL(mmd_sum_kernel, dim3(3, n_blocks), dim3(64), 0, s, partial, Tx, Ty, total, sums);
         e = hipGetLastError();
     }
-    if (e != hipSuccess) {
-        nfisam_g_last_hip_error = (int)e;
-        return NFISAM_ERR_LAUNCH;
-    }
-    return NFISAM_OK;
+    return launch_status(e);
 }

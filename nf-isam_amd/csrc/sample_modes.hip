@@ -6,10 +6,10 @@
 //     k_j(y) = w_j exp(-inv_two_sigma2 * sum_e (scale_e * wrap_e(x_je - y_e))^2),
 //     y_e += sum_j k_j(y) wrap_e(x_je - y_e) / sum_j k_j(y)                          (one iteration; a heading is wrapped back),
 // until the shift is at most `tol` sigmas or `max_iters` shifts were applied, and the converged points are merged into modes.
-// Xt is the COLUMN-major float32 device matrix [x_rows][n] (the walk's St, the layout of sample_mmd.hip and
-// sample_summary.hip); an entry e names a row cols[e] of Xt and a block is a run of entries (nfisam_mmd_block).
+// Xt is the COLUMN-major float32 device matrix [x_rows][n] (the walk's St, the layout of sample_common.h); an entry e names
+// a row cols[e] of Xt and a block is a run of entries (nfisam_mmd_block).
 //
-// Numerics: float32 points in; every difference, exponent, sum and division is float64 (the contract of sample_mmd.hip).
+// Numerics: float32 points in; every difference, exponent, sum and division is float64 (the contract of sample_common.h).
 // Direct differences, never the Gram identity.  The SHIFT form -- a weighted mean of wrapped differences, not of
 // coordinates -- is right across the +-pi seam and leaves a constant column exactly where it is (every difference is exactly
 // 0, whatever its scale).  A column with scale 0 does not enter the exponent: it is carried along by the others' weights.
@@ -32,10 +32,11 @@
 #include <stdint.h>
 
 #include "../../include/nfisam_hip.h"
-
-extern thread_local int nfisam_g_last_hip_error;      // defined in the common unit
+#include "sample_common.h"
 
 namespace {
+
+using namespace sample_common;
 
 constexpr int MAX_D = NFISAM_MODES_MAX_D;
 constexpr int MAX_MODES = NFISAM_MODES_MAX_MODES;
@@ -43,27 +44,8 @@ constexpr int SPG = 64;           // starts per group: one per lane, the same 64
 constexpr int JT = 128;           // points j per staged chunk
 constexpr int JPW = JT / 4;       // ... of which a wave takes 32
 constexpr int ROWS = MAX_D + 1;   // staged rows: the columns and the weights | partial sums: the numerators and the denominator
-constexpr double TWO_PI = 6.283185307179586476925286766559;
-constexpr double PI = 3.141592653589793238462643383279;
 
-// (t + pi) mod 2 pi - pi with the sign of Python's `%`: [-pi, pi)  (wrap_pi of sample_mmd.hip; where 0 <= t + pi < 2 pi the
-// remainder is t + pi itself, bit for bit, and fmod is not called)
-__device__ __forceinline__ double wrap_pi(double t) {
-    double m = t + PI;
-    if (!(m >= 0.0 && m < TWO_PI)) {
-        m = fmod(m, TWO_PI);
-        if (m < 0.0) m += TWO_PI;
-    }
-    return m - PI;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {           // a fixed tree: the same order in every wave of every call
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;                                                      // (lane 0 holds the sum)
-}
-
-// sum of w over all points (n for NULL weights): thread t adds t, t + 256, ... in order, the tree, the four waves in order.
+// sum of w over all points (n for NULL weights): thread t adds t, t + 256, ... in order, wave_sum, the four waves in order.
 // Every thread of the group returns the same bits.  `part` is 4 doubles of LDS; two barriers.
 __device__ __forceinline__ double group_weight_sum(const double* __restrict__ weights, int n, double* part) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -72,7 +54,7 @@ __device__ __forceinline__ double group_weight_sum(const double* __restrict__ we
     s = wave_sum(s);
     if (lane == 0) part[w] = s;
     __syncthreads();
-    const double W = ((part[0] + part[1]) + part[2]) + part[3];
+    const double W = waves_in_order(part);
     __syncthreads();
     return W;
 }
@@ -153,7 +135,7 @@ __device__ __forceinline__ void ascend(const BlockHead h, const float* __restric
                     diff[c] = 0.0;
                     if (c < d) {
                         double t = xs[c][jl] - y[c];
-                        if ((wrap_mask >> c) & 1u) t = wrap_pi(t);
+                        if ((wrap_mask >> c) & 1u) t = wrap_pi_near(t);
                         diff[c] = t;
                         const double u = sc[c] * t;
                         q = fma(u, u, q);
@@ -190,7 +172,7 @@ __device__ __forceinline__ void ascend(const BlockHead h, const float* __restric
                     if (c < d) {
                         const double delta = acc[c] / den;
                         double v = y[c] + delta;
-                        if ((wrap_mask >> c) & 1u) v = wrap_pi(v);
+                        if ((wrap_mask >> c) & 1u) v = wrap_pi_near(v);
                         y[c] = v;
                         const double s = sc[c] * delta;
                         crit = fma(s, s, crit);
@@ -324,7 +306,7 @@ __global__ void __launch_bounds__(256) modes_merge_kernel(const nfisam_mmd_block
             double q = 0.0;
             for (int c = 0; c < d; ++c) {
                 double t = p0[(size_t)c * (size_t)n + (size_t)i] - tab[m][c];
-                if (wrap_s[c]) t = wrap_pi(t);
+                if (wrap_s[c]) t = wrap_pi_near(t);
                 const double u = sc_s[c] * t;
                 q = fma(u, u, q);
             }
@@ -336,7 +318,7 @@ __global__ void __launch_bounds__(256) modes_merge_kernel(const nfisam_mmd_block
         mass = wave_sum(mass);
         if (lane == 0) wm[w] = mass;
         __syncthreads();
-        if (tid == 0) tab_mass[m] = (((wm[0] + wm[1]) + wm[2]) + wm[3]) / W;
+        if (tid == 0) tab_mass[m] = waves_in_order(wm) / W;
     }
     __syncthreads();
     int left = 0;
@@ -404,11 +386,7 @@ extern "C" int nfisam_sample_modes(const float* Xt, int x_rows, int n, const nfi
     if (e == hipSuccess)
         e = launch_merge(blocks_dev, n_blocks, x_rows, n, cols, n_entries, scale, wrap, weights, merge, max_modes, pos, dens, labels,
                          n_modes, mode_pos, mode_dens, mode_mass, unlabelled, s);
-    if (e != hipSuccess) {
-        nfisam_g_last_hip_error = (int)e;
-        return NFISAM_ERR_LAUNCH;
-    }
-    return NFISAM_OK;
+    return launch_status(e);
 }
 
 // the second launch alone: converged points and densities of an earlier nfisam_sample_modes call merged again, with another
@@ -426,9 +404,5 @@ extern "C" int nfisam_sample_modes_merge(int x_rows, int n, const nfisam_mmd_blo
     if (n == 0) return NFISAM_OK;
     const hipError_t e = launch_merge(blocks_dev, n_blocks, x_rows, n, cols, n_entries, scale, wrap, weights, merge, max_modes, pos,
                                       dens, labels, n_modes, mode_pos, mode_dens, mode_mass, unlabelled, (hipStream_t)stream);
-    if (e != hipSuccess) {
-        nfisam_g_last_hip_error = (int)e;
-        return NFISAM_ERR_LAUNCH;
-    }
-    return NFISAM_OK;
+    return launch_status(e);
 }

@@ -3,19 +3,19 @@
 // The reference summarises a posterior draw on the host (src/utils/Statistics.py:142-214: `sample_mean` with scipy's circmean
 // for headings, `rmse`, `translation_distance`, `geodesic_distance`); its run scripts copy the whole [n, total_dim] matrix
 // out and loop over the variables in numpy after every update.  Here the matrix is summarised where the tree walk wrote it:
-// Xt is the COLUMN-major float32 device matrix [x_rows][n] (the walk's St, the layout of sample_mmd.hip and
-// factor_density.hip); an entry e names a row cols[e] of Xt (one coordinate of one variable) and a block is a run of entries.
+// Xt is the COLUMN-major float32 device matrix [x_rows][n] (the walk's St, the layout of sample_common.h); an entry e names
+// a row cols[e] of Xt (one coordinate of one variable) and a block is a run of entries.
 //
 // Numerics: float32 points in; every difference, product, transcendental and sum is float64 (the contract of
-// factor_density.hip and sample_mmd.hip).  TWO PASSES: the means first, then residuals about the float64 mean -- never
+// sample_common.h).  TWO PASSES: the means first, then residuals about the float64 mean -- never
 // sum x^2 - (sum x)^2, which cancels at coordinates of 100 m and spreads of centimetres.  Both means are taken about the
 // column's first point: x_0 + sum w (x - x_0) / W, and x_0 + atan2(sum w sin(x - x_0), sum w cos(x - x_0)) for an angle (the
 // same direction and the same resultant length as atan2(S, C) of the unshifted sums).  The differences of float32 values are
 // exact in float64, so a constant column -- or a single point -- has mean x_0 and variance 0 exactly, whatever the weights.
 //
 // Three kernels, no float atomics, everything a workgroup brings decided by blockIdx alone (wave-uniform):
-//   (1) moments_mean_kernel: one 256-thread group per ENTRY.  Thread t adds points t, t + 256, ... in order, then the fixed
-//       shuffle tree of sample_mmd.hip, then the four waves in order.
+//   (1) moments_mean_kernel: one 256-thread group per ENTRY.  Thread t adds points t, t + 256, ... in order, then wave_sum, then
+//       the four waves in order.
 //   (2) moments_cov_kernel: one 256-thread group per BLOCK.  The d (d + 1) / 2 <= 136 products of the upper triangle are
 //       numbered column by column (p = f (f + 1) / 2 + e, e <= f) and wave w owns p = w, w + 4, ...: at most 34 float64
 //       accumulators per lane, indexed at compile time (the wave number is a template argument).  Every wave walks all
@@ -31,33 +31,15 @@
 #include <stdint.h>
 
 #include "../../include/nfisam_hip.h"
-
-extern thread_local int nfisam_g_last_hip_error;      // defined in the common unit
+#include "sample_common.h"
 
 namespace {
+
+using namespace sample_common;
 
 constexpr int MAX_D = NFISAM_MOMENTS_MAX_D;
 constexpr int MAX_P = MAX_D * (MAX_D + 1) / 2;        // 136 products of the upper triangle
 constexpr int PPW = (MAX_P + 3) / 4;                  // 34 per wave
-constexpr double TWO_PI = 6.283185307179586476925286766559;
-constexpr double PI = 3.141592653589793238462643383279;
-
-// (t + pi) mod 2 pi - pi with the sign of Python's `%`: [-pi, pi)  (wrap_pi of factor_density.hip and sample_mmd.hip)
-__device__ __forceinline__ double wrap_pi(double t) {
-    double m = fmod(t + PI, TWO_PI);
-    if (m < 0.0) m += TWO_PI;
-    return m - PI;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {           // a fixed tree: the same order in every wave of every call
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;                                                      // (lane 0 holds the sum)
-}
-
-__device__ __forceinline__ double wave_total(double v) {         // the same tree, the sum in every lane
-    return __shfl(wave_sum(v), 0, 64);
-}
 
 // grid (n_entries); 256 threads
 __global__ void __launch_bounds__(256) moments_mean_kernel(const float* __restrict__ Xt, int x_rows, int n,
@@ -93,9 +75,7 @@ __global__ void __launch_bounds__(256) moments_mean_kernel(const float* __restri
     if (lane == 0) part[0][w] = sw, part[1][w] = sa, part[2][w] = sb;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double W = ((part[0][0] + part[0][1]) + part[0][2]) + part[0][3];
-        const double A = ((part[1][0] + part[1][1]) + part[1][2]) + part[1][3];
-        const double B = ((part[2][0] + part[2][1]) + part[2][2]) + part[2][3];
+        const double W = waves_in_order(part[0]), A = waves_in_order(part[1]), B = waves_in_order(part[2]);
         double m, r = (double)NAN;
         if (circ) {
             const double C = A / W, S = B / W;
@@ -285,11 +265,7 @@ extern "C" int nfisam_sample_moments(const float* Xt, int x_rows, int n, const n
                            circular, weights, mean, cov_count, cov);
         e = hipGetLastError();
     }
-    if (e != hipSuccess) {
-        nfisam_g_last_hip_error = (int)e;
-        return NFISAM_ERR_LAUNCH;
-    }
-    return NFISAM_OK;
+    return launch_status(e);
 }
 
 extern "C" int nfisam_sample_quantiles(const float* Xt, int x_rows, int n, const int32_t* cols, int n_entries,
@@ -311,9 +287,5 @@ extern "C" int nfisam_sample_quantiles(const float* Xt, int x_rows, int n, const
                            circular, center, probs_dev, n_probs, out);
         e = hipGetLastError();
     }
-    if (e != hipSuccess) {
-        nfisam_g_last_hip_error = (int)e;
-        return NFISAM_ERR_LAUNCH;
-    }
-    return NFISAM_OK;
+    return launch_status(e);
 }

@@ -863,6 +863,127 @@ def factor_graph_log_density_t(terms: np.ndarray, St, device, per_factor=False, 
     return log_p
 
 
+# ---- the front of the sample bindings: what every evaluator over the walk's sample matrix checks and stages ---------------------
+# Every binding below comes as NAME(X [n, cols], ..., device), which makes every check on a row-major tensor or array before
+# the device is touched and hands the transposed copy on, and as NAME_t(Xt [rows, n], ..., checked=True), which works on the
+# column-major device matrix in place.  A new evaluator is written from these helpers (csrc/sample_common.h on the device
+# side): the two fronts, the block-table checks, `_f64` for the weights, which go the plain way, and `_upload_named` for
+# everything small -- ONE `upload` per call for whatever is on the host, every result taken by name, whatever form it came in.
+def _row_major_front(what, device, **mats):
+    """The head of the row-major binding `what`: -> the device (default: the first matrix's own, or "cuda").  RuntimeError
+    unless that is a ROCm device, ValueError unless every matrix is a 2-D tensor or array.  Nothing is copied yet: `_columns`
+    does that once the caller's tables have passed their checks."""
+    first = next(iter(mats.values()))
+    if device is None:
+        device = first.device if torch.is_tensor(first) else "cuda"
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("%s needs a ROCm device (no CPU path exists)" % what)
+    if not all((torch.is_tensor(A) or isinstance(A, np.ndarray)) and A.ndim == 2 for A in mats.values()):
+        raise ValueError("%s must be %s" % (" and ".join(mats), "a [rows, cols] tensor or array" if len(mats) == 1 else
+                                            "[rows, cols] tensors or arrays"))
+    return device
+
+
+def _columns(A, device):
+    """A [n, cols] (tensor or numpy) -> the column-major float32 matrix [cols, n] on `device`."""
+    if torch.is_tensor(A):
+        return A.to(device=device, dtype=torch.float32).t().contiguous()
+    return torch.from_numpy(np.ascontiguousarray(A.T, dtype=np.float32)).to(device)
+
+
+def _column_major_front(name, t):
+    """The head of a column-major binding: `t` must be a contiguous float32 [rows, points] tensor on a ROCm device
+    -> (rows, points)."""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError("%s must be a tensor on a ROCm device (no CPU path exists)" % name)
+    if t.ndim != 2 or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous float32 [rows, points] tensor" % name)
+    return int(t.shape[0]), int(t.shape[1])
+
+
+def _f64(a, device):
+    """None, a tensor or anything numpy takes -> None or a contiguous float64 tensor on `device` (the plain way: one `.to`)."""
+    if a is None:
+        return None
+    if torch.is_tensor(a):
+        return a.to(device=device, dtype=torch.float64).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(device)
+
+
+def _entry_f64(a):
+    """An optional float64 per-entry array in the form `_upload_named` takes: None, a device tensor cast to float64 (it stays
+    where it is), or -- a list, numpy, a CPU tensor -- the float64 numpy array to stage."""
+    if a is None:
+        return None
+    if torch.is_tensor(a) and a.is_cuda:
+        return a.to(dtype=torch.float64)
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _flags(a):
+    """Optional per-entry flags -> None or the uint8 numpy array the kernels read."""
+    return None if a is None else np.asarray(a).astype(np.uint8)
+
+
+def _table_bytes(blocks):
+    return blocks.view(np.uint8).reshape(-1)
+
+
+def _upload_named(device, **arrays):
+    """`upload` by name: ONE staged copy for the numpy arrays among `arrays` (none at all if there is none); a value that is
+    a tensor already is not staged but brought to `device`, contiguous; None stays None.
+    -> {name: tensor on `device`, None for an absent array}: what a name maps to never depends on the form of another."""
+    host = {k: a for k, a in arrays.items() if a is not None and not torch.is_tensor(a)}
+    out = {k: a.to(device).contiguous() if torch.is_tensor(a) else None for k, a in arrays.items()}
+    if host:
+        out.update(zip(host, upload(*host.values(), device=device)))
+    return out
+
+
+def _check_table_layout(blocks, dtype, dtype_name, cols, per_entry, max_d=None):
+    """What the block-table checks share, in this order (a checker goes on with what is its own, then `_check_bandwidths`
+    and `_check_rows`): the table's dtype, the column lists `cols` ({name: (list, rows of
+    its matrix)}: 1-D, one length >= 1), the optional per-entry arrays `per_entry` ({name: array or None}: that length),
+    1..65535 blocks, widths in 1..max_d (if given), entries inside [0, n_entries).  -> (col_off, d) as int64."""
+    if not isinstance(blocks, np.ndarray) or blocks.dtype != dtype or blocks.ndim != 1:
+        raise ValueError("blocks must be a 1-D numpy array of %s" % dtype_name)
+    lists = [np.asarray(c) for c, _ in cols.values()]
+    ne, single = int(lists[0].size), len(lists) == 1
+    if ne < 1 or any(c.ndim != 1 or c.size != ne for c in lists):
+        raise ValueError("cols must be a 1-D list of at least one row" if single else
+                         "%s must be 1-D lists of the same length >= 1" % " and ".join(cols))
+    for name, a in per_entry.items():
+        if a is not None and (tuple(a.shape) if torch.is_tensor(a) else np.shape(a)) != (ne,):
+            raise ValueError("%s must have one %s per entry (%d)" % (name, "flag" if name == "circular" else "value", ne))
+    if not 1 <= blocks.size <= 65535:
+        raise ValueError("1..65535 blocks are supported, got %d" % blocks.size)
+    off, d = blocks["col_off"].astype(np.int64), blocks["d"].astype(np.int64)
+    if max_d is not None and np.any((d < 1) | (d > max_d)):
+        b = int(np.argmax((d < 1) | (d > max_d)))
+        raise ValueError("block %d: width %d is outside 1..%d" % (b, int(d[b]), max_d))
+    bad = (d < 1) | (off < 0) | (off + d > ne)
+    if np.any(bad):
+        b = int(np.argmax(bad))
+        raise ValueError("block %d: entries %d..%d leave the %d entries of the column list%s"
+                         % (b, int(off[b]), int((off + d)[b]), ne, "" if single else "s (d >= 1 is required)"))
+    return off, d
+
+
+def _check_bandwidths(blocks):
+    ok = np.isfinite(blocks["inv_two_sigma2"]) & (blocks["inv_two_sigma2"] > 0)
+    if not np.all(ok):
+        raise ValueError("block %d: inv_two_sigma2 must be positive and finite" % int(np.argmin(ok)))
+
+
+def _check_rows(cols):
+    """Every row of the column lists `cols` ({name: (list, rows of its matrix)}) inside its matrix."""
+    for name, (c, rows) in cols.items():
+        c = np.asarray(c)
+        if not 0 <= int(c.min()) <= int(c.max()) < int(rows):
+            raise ValueError("%s: a row is out of range of the %d rows of %s matrix"
+                             % (name, int(rows), "the" if len(cols) == 1 else "its"))
+
+
 # ---- two-sample MMD: the kernel sums of many column blocks in one launch (nfisam_sample_mmd) ------------------------------------
 MMD_BLOCK_DTYPE = np.dtype([("col_off", np.int32), ("d", np.int32), ("inv_two_sigma2", np.float64)])
 assert MMD_BLOCK_DTYPE.itemsize == C.sizeof(MmdBlock)
@@ -881,38 +1002,12 @@ def pack_mmd_blocks(dims, sigmas) -> np.ndarray:
 def check_mmd_blocks(blocks: np.ndarray, xcols, ycols, x_rows: int, y_rows: int, scale=None, wrap=None) -> None:
     """ValueError for tables the kernel must not see: no block or more than 65535, d < 1, a bandwidth term that is not positive
     and finite, entries outside [0, n_entries), a row outside [0, x_rows) / [0, y_rows), per-entry arrays of another length."""
-    if not isinstance(blocks, np.ndarray) or blocks.dtype != MMD_BLOCK_DTYPE or blocks.ndim != 1:
-        raise ValueError("blocks must be a 1-D numpy array of MMD_BLOCK_DTYPE")
-    xcols, ycols = np.asarray(xcols), np.asarray(ycols)
-    if xcols.ndim != 1 or ycols.ndim != 1 or xcols.size != ycols.size or xcols.size < 1:
-        raise ValueError("xcols and ycols must be 1-D lists of the same length >= 1")
-    ne = int(xcols.size)
-    for name, a in (("scale", scale), ("wrap", wrap)):
-        if a is not None and (np.ndim(a) != 1 or np.size(a) != ne):
-            raise ValueError("%s must have one value per entry (%d)" % (name, ne))
-    if not 1 <= blocks.size <= 65535:
-        raise ValueError("1..65535 blocks are supported, got %d" % blocks.size)
-    off, d = blocks["col_off"].astype(np.int64), blocks["d"].astype(np.int64)
-    bad = (d < 1) | (off < 0) | (off + d > ne)
-    if np.any(bad):
-        raise ValueError("block %d: entries %d..%d leave the %d entries of the column lists (d >= 1 is required)"
-                         % (int(np.argmax(bad)), int(off[np.argmax(bad)]), int((off + d)[np.argmax(bad)]), ne))
-    v = blocks["inv_two_sigma2"]
-    if not np.all(np.isfinite(v) & (v > 0)):
-        raise ValueError("block %d: inv_two_sigma2 must be positive and finite" % int(np.argmin(np.isfinite(v) & (v > 0))))
-    for name, cols, rows in (("xcols", xcols, int(x_rows)), ("ycols", ycols, int(y_rows))):
-        if not 0 <= int(cols.min()) <= int(cols.max()) < rows:
-            raise ValueError("%s: a row is out of range of the %d rows of its matrix" % (name, rows))
+    cols = {"xcols": (xcols, x_rows), "ycols": (ycols, y_rows)}
+    _check_table_layout(blocks, MMD_BLOCK_DTYPE, "MMD_BLOCK_DTYPE", cols, dict(scale=scale, wrap=wrap))
+    _check_bandwidths(blocks)
+    _check_rows(cols)
     if scale is not None and not np.all(np.isfinite(np.asarray(scale, dtype=np.float64))):
         raise ValueError("scale must be finite")
-
-
-def _mmd_matrix(A, name, device):
-    if not (torch.is_tensor(A) or isinstance(A, np.ndarray)) or A.ndim != 2:
-        raise ValueError("%s must be a [rows, cols] tensor or array" % name)
-    if torch.is_tensor(A):
-        return A.to(device=device, dtype=torch.float32).t().contiguous()
-    return torch.from_numpy(np.ascontiguousarray(A.T, dtype=np.float32)).to(device)
 
 
 def mmd_sums(X, Y, blocks: np.ndarray, xcols, ycols, scale=None, wrap=None, device=None):
@@ -921,55 +1016,37 @@ def mmd_sums(X, Y, blocks: np.ndarray, xcols, ycols, scale=None, wrap=None, devi
     stream.  `blocks`: numpy MMD_BLOCK_DTYPE (`pack_mmd_blocks`); entry e of a block pairs column xcols[e] of X with column
     ycols[e] of Y; scale [n_entries] multiplies an entry's differences, wrap [n_entries] marks angles (differences brought
     into [-pi, pi)).  -> [n_blocks, 3] float64 device tensor."""
-    if device is None:
-        device = X.device if torch.is_tensor(X) else "cuda"
-    if torch.device(device).type != "cuda":
-        raise RuntimeError("mmd_sums needs a ROCm device (no CPU path exists)")
-    if not (torch.is_tensor(X) or isinstance(X, np.ndarray)) or X.ndim != 2 or \
-            not (torch.is_tensor(Y) or isinstance(Y, np.ndarray)) or Y.ndim != 2:
-        raise ValueError("X and Y must be [rows, cols] tensors or arrays")
+    device = _row_major_front("mmd_sums", device, X=X, Y=Y)
     check_mmd_blocks(blocks, xcols, ycols, int(X.shape[1]), int(Y.shape[1]), scale, wrap)
-    return mmd_sums_t(_mmd_matrix(X, "X", device), _mmd_matrix(Y, "Y", device), blocks, xcols, ycols, scale, wrap, checked=True)
+    return mmd_sums_t(_columns(X, device), _columns(Y, device), blocks, xcols, ycols, scale, wrap, checked=True)
 
 
 def mmd_sums_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, scale=None, wrap=None, checked=False):
     """`mmd_sums` on the COLUMN-major matrices Xt [x_rows, m], Yt [y_rows, n] (contiguous float32 device tensors, used in
     place): what the tree walk wrote."""
-    for name, t in (("Xt", Xt), ("Yt", Yt)):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise RuntimeError("%s must be a tensor on a ROCm device (no CPU path exists)" % name)
-        if t.ndim != 2 or t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous float32 [rows, points] tensor" % name)
+    (x_rows, m), (y_rows, n) = _column_major_front("Xt", Xt), _column_major_front("Yt", Yt)
     if Xt.device != Yt.device:
         raise ValueError("Xt and Yt must be on the same device")
     device = Xt.device
-    x_rows, m, y_rows, n = int(Xt.shape[0]), int(Xt.shape[1]), int(Yt.shape[0]), int(Yt.shape[1])
     if m < 1 or n < 1:
         raise ValueError("both sample sets need at least one point")
     if not checked:
         check_mmd_blocks(blocks, xcols, ycols, x_rows, y_rows, scale, wrap)
     nb = int(blocks.shape[0])
+    blocks = np.ascontiguousarray(blocks)
     xc, yc = np.asarray(xcols, dtype=np.int32), np.asarray(ycols, dtype=np.int32)
-    host = [blocks.view(np.uint8).reshape(-1), xc, yc]
-    if scale is not None:
-        host.append(np.asarray(scale, dtype=np.float64))
-    if wrap is not None:
-        host.append(np.asarray(wrap).astype(np.uint8))
     with torch.cuda.device(device):
-        dev = upload(*host, device=device)
-        blk_d, xc_d, yc_d = dev[:3]
-        sc_d = dev[3] if scale is not None else None
-        wr_d = dev[-1] if wrap is not None else None
+        dev = _upload_named(device, blocks=_table_bytes(blocks), xcols=xc, ycols=yc, scale=_entry_f64(scale), wrap=_flags(wrap))
         count = int(lib().nfisam_sample_mmd_scratch_count(m, n, nb))
         if count < 1:
             raise ValueError("mmd_sums: %d x %d points in %d blocks exceed the grid" % (m, n, nb))
         # the per-tile partials come from torch's allocator, like the per-factor rows of factor_graph_log_density_t
         scratch = torch.empty(count, dtype=torch.float64, device=device)
         sums = torch.empty(nb, 3, dtype=torch.float64, device=device)
-        blocks = np.ascontiguousarray(blocks)
         _check(lib().nfisam_sample_mmd(_ptr(Xt), x_rows, m, _ptr(Yt), y_rows, n, blocks.ctypes.data_as(C.c_void_p),
-                                       C.c_void_p(blk_d.data_ptr()), nb, _ptr(xc_d), _ptr(yc_d), int(xc.size), _ptr(sc_d),
-                                       _ptr(wr_d), _ptr(sums), _ptr(scratch), _stream()), "nfisam_sample_mmd")
+                                       _ptr(dev["blocks"]), nb, _ptr(dev["xcols"]), _ptr(dev["ycols"]), int(xc.size),
+                                       _ptr(dev["scale"]), _ptr(dev["wrap"]), _ptr(sums), _ptr(scratch), _stream()),
+               "nfisam_sample_mmd")
     return sums
 
 
@@ -993,30 +1070,14 @@ def check_moment_blocks(blocks: np.ndarray, cols, x_rows: int, circular=None, co
     """ValueError for tables the kernel must not see: no block or more than 65535, d outside 1..16, entries outside
     [0, n_entries), a matrix outside [0, cov_count) (default: the end of the last matrix), a row outside [0, x_rows), flags of
     another length."""
-    if not isinstance(blocks, np.ndarray) or blocks.dtype != MOMENT_BLOCK_DTYPE or blocks.ndim != 1:
-        raise ValueError("blocks must be a 1-D numpy array of MOMENT_BLOCK_DTYPE")
-    cols = np.asarray(cols)
-    if cols.ndim != 1 or cols.size < 1:
-        raise ValueError("cols must be a 1-D list of at least one row")
-    ne = int(cols.size)
-    if circular is not None and (np.ndim(circular) != 1 or np.size(circular) != ne):
-        raise ValueError("circular must have one flag per entry (%d)" % ne)
-    if not 1 <= blocks.size <= 65535:
-        raise ValueError("1..65535 blocks are supported, got %d" % blocks.size)
-    off, d, coff = blocks["col_off"].astype(np.int64), blocks["d"].astype(np.int64), blocks["cov_off"].astype(np.int64)
-    bad = (d < 1) | (d > MOMENTS_MAX_D)
-    if np.any(bad):
-        raise ValueError("block %d: width %d is outside 1..%d" % (int(np.argmax(bad)), int(d[np.argmax(bad)]), MOMENTS_MAX_D))
-    bad = (off < 0) | (off + d > ne)
-    if np.any(bad):
-        raise ValueError("block %d: entries %d..%d leave the %d entries of the column list"
-                         % (int(np.argmax(bad)), int(off[np.argmax(bad)]), int((off + d)[np.argmax(bad)]), ne))
+    cols = {"cols": (cols, x_rows)}
+    off, d = _check_table_layout(blocks, MOMENT_BLOCK_DTYPE, "MOMENT_BLOCK_DTYPE", cols, dict(circular=circular), MOMENTS_MAX_D)
+    coff = blocks["cov_off"].astype(np.int64)
     count = int((coff + d * d).max()) if cov_count is None else int(cov_count)
     bad = (coff < 0) | (coff + d * d > count)
     if np.any(bad):
         raise ValueError("block %d: its matrix at %d leaves the %d values of cov" % (int(np.argmax(bad)), int(coff[np.argmax(bad)]), count))
-    if not 0 <= int(cols.min()) <= int(cols.max()) < int(x_rows):
-        raise ValueError("cols: a row is out of range of the %d rows of the matrix" % int(x_rows))
+    _check_rows(cols)
 
 
 def _check_weights(weights, n):
@@ -1044,28 +1105,19 @@ def sample_moments(X, blocks: np.ndarray, cols, circular=None, weights=None, dev
     in [-pi, pi), residuals wrapped); weights [n] float64 (None: all ones).
     -> (mean [n_entries], resultant [n_entries] (NaN for a Euclidean entry), cov [sum d^2], block b's row-major d x d matrix
     at blocks["cov_off"][b]): float64 device tensors."""
-    if device is None:
-        device = X.device if torch.is_tensor(X) else "cuda"
-    if torch.device(device).type != "cuda":
-        raise RuntimeError("sample_moments needs a ROCm device (no CPU path exists)")
-    if not (torch.is_tensor(X) or isinstance(X, np.ndarray)) or X.ndim != 2:
-        raise ValueError("X must be a [rows, cols] tensor or array")
+    device = _row_major_front("sample_moments", device, X=X)
     if int(X.shape[0]) < 1:
         raise ValueError("sample_moments: no points")
     check_moment_blocks(blocks, cols, int(X.shape[1]), circular)
     weights = _check_weights(weights, int(X.shape[0]))
-    return sample_moments_t(_mmd_matrix(X, "X", device), blocks, cols, circular, weights, checked=True)
+    return sample_moments_t(_columns(X, device), blocks, cols, circular, weights, checked=True)
 
 
 def sample_moments_t(Xt, blocks: np.ndarray, cols, circular=None, weights=None, checked=False):
     """`sample_moments` on the COLUMN-major matrix Xt [x_rows, n] (a contiguous float32 device tensor, used in place): what
     the tree walk wrote.  `checked` skips the table check (the caller has made it)."""
-    if not torch.is_tensor(Xt) or not Xt.is_cuda:
-        raise RuntimeError("Xt must be a tensor on a ROCm device (no CPU path exists)")
-    if Xt.ndim != 2 or Xt.dtype != torch.float32 or not Xt.is_contiguous():
-        raise ValueError("Xt must be a contiguous float32 [rows, points] tensor")
+    x_rows, n = _column_major_front("Xt", Xt)
     device = Xt.device
-    x_rows, n = int(Xt.shape[0]), int(Xt.shape[1])
     if n < 1:
         raise ValueError("sample_moments: no points")
     if not checked:
@@ -1077,22 +1129,15 @@ def sample_moments_t(Xt, blocks: np.ndarray, cols, circular=None, weights=None, 
     d = blocks["d"].astype(np.int64)
     cov_count = max(int((blocks["cov_off"].astype(np.int64) + d * d).max()), 1)
     blocks = np.ascontiguousarray(blocks)
-    host = [blocks.view(np.uint8).reshape(-1), cc]
-    if circular is not None:
-        host.append(np.asarray(circular).astype(np.uint8))
     with torch.cuda.device(device):
-        dev = upload(*host, device=device)
-        ci_d = dev[2] if circular is not None else None
-        w_d = None
-        if weights is not None:
-            w_d = weights.to(device=device, dtype=torch.float64).contiguous() if torch.is_tensor(weights) else \
-                torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float64)).to(device)
+        dev = _upload_named(device, blocks=_table_bytes(blocks), cols=cc, circular=_flags(circular))
+        w_d = _f64(weights, device)
         mean = torch.empty(ne, dtype=torch.float64, device=device)
         res = torch.empty(ne, dtype=torch.float64, device=device)
         cov = torch.full((cov_count,), float("nan"), dtype=torch.float64, device=device)
-        _check(lib().nfisam_sample_moments(_ptr(Xt), x_rows, n, blocks.ctypes.data_as(C.c_void_p), C.c_void_p(dev[0].data_ptr()), nb,
-                                           _ptr(dev[1]), ne, _ptr(ci_d), _ptr(w_d), _ptr(mean), _ptr(res), _ptr(cov),
-                                           C.c_longlong(cov_count), _stream()), "nfisam_sample_moments")
+        _check(lib().nfisam_sample_moments(_ptr(Xt), x_rows, n, blocks.ctypes.data_as(C.c_void_p), _ptr(dev["blocks"]), nb,
+                                           _ptr(dev["cols"]), ne, _ptr(dev["circular"]), _ptr(w_d), _ptr(mean), _ptr(res),
+                                           _ptr(cov), C.c_longlong(cov_count), _stream()), "nfisam_sample_moments")
     return mean, res, cov
 
 
@@ -1111,15 +1156,10 @@ def sample_quantiles(X, cols, probs, circular=None, center=None, device=None):
     angles: their keys are wrap_pi(x - center[e]) (center [n_entries] float64, tensor or numpy: the circular means; None: 0)
     and center + quantile is returned UNWRAPPED -- wrap it for display.  n <= 16384.  -> [n_entries, n_probs] float64 device
     tensor."""
-    if device is None:
-        device = X.device if torch.is_tensor(X) else "cuda"
-    if torch.device(device).type != "cuda":
-        raise RuntimeError("sample_quantiles needs a ROCm device (no CPU path exists)")
-    if not (torch.is_tensor(X) or isinstance(X, np.ndarray)) or X.ndim != 2:
-        raise ValueError("X must be a [rows, cols] tensor or array")
+    device = _row_major_front("sample_quantiles", device, X=X)
     circular, center = _entry_arrays(circular, center)
     _check_quantile_args(int(X.shape[0]), int(X.shape[1]), cols, probs, circular, center)
-    return sample_quantiles_t(_mmd_matrix(X, "X", device), cols, probs, circular, center, checked=True)
+    return sample_quantiles_t(_columns(X, device), cols, probs, circular, center, checked=True)
 
 
 def _entry_arrays(circular, center):
@@ -1134,8 +1174,7 @@ def _check_quantile_args(n, x_rows, cols, probs, circular, center):
     cols = np.asarray(cols)
     if cols.ndim != 1 or cols.size < 1:
         raise ValueError("cols must be a 1-D list of at least one row")
-    if not 0 <= int(cols.min()) <= int(cols.max()) < int(x_rows):
-        raise ValueError("cols: a row is out of range of the %d rows of the matrix" % int(x_rows))
+    _check_rows({"cols": (cols, x_rows)})
     _check_probs(probs)
     if not 1 <= n <= QUANTILE_MAX_N:
         raise ValueError("sample_quantiles takes 1..%d points, got %d" % (QUANTILE_MAX_N, n))
@@ -1146,32 +1185,19 @@ def _check_quantile_args(n, x_rows, cols, probs, circular, center):
 
 def sample_quantiles_t(Xt, cols, probs, circular=None, center=None, checked=False):
     """`sample_quantiles` on the COLUMN-major matrix Xt [x_rows, n] (a contiguous float32 device tensor, used in place)."""
-    if not torch.is_tensor(Xt) or not Xt.is_cuda:
-        raise RuntimeError("Xt must be a tensor on a ROCm device (no CPU path exists)")
-    if Xt.ndim != 2 or Xt.dtype != torch.float32 or not Xt.is_contiguous():
-        raise ValueError("Xt must be a contiguous float32 [rows, points] tensor")
+    x_rows, n = _column_major_front("Xt", Xt)
     device = Xt.device
-    x_rows, n = int(Xt.shape[0]), int(Xt.shape[1])
     circular, center = _entry_arrays(circular, center)
     if not checked:
         _check_quantile_args(n, x_rows, cols, probs, circular, center)
     p = _check_probs(probs)
     cc = np.asarray(cols, dtype=np.int32)
-    host = [cc, p]
-    if circular is not None:
-        host.append(np.asarray(circular).astype(np.uint8))
-    if center is not None and not torch.is_tensor(center):
-        host.append(np.ascontiguousarray(center, dtype=np.float64))
     with torch.cuda.device(device):
-        dev = upload(*host, device=device)
-        ci_d = dev[2] if circular is not None else None
-        ce_d = None
-        if center is not None:
-            ce_d = center.to(device=device, dtype=torch.float64).contiguous() if torch.is_tensor(center) else dev[-1]
+        dev = _upload_named(device, cols=cc, probs=p, circular=_flags(circular), center=_entry_f64(center))
         out = torch.empty(int(cc.size), int(p.size), dtype=torch.float64, device=device)
-        _check(lib().nfisam_sample_quantiles(_ptr(Xt), x_rows, n, _ptr(dev[0]), int(cc.size), _ptr(ci_d), _ptr(ce_d),
-                                             p.ctypes.data_as(C.c_void_p), _ptr(dev[1]), int(p.size), _ptr(out), _stream()),
-               "nfisam_sample_quantiles")
+        _check(lib().nfisam_sample_quantiles(_ptr(Xt), x_rows, n, _ptr(dev["cols"]), int(cc.size), _ptr(dev["circular"]),
+                                             _ptr(dev["center"]), p.ctypes.data_as(C.c_void_p), _ptr(dev["probs"]), int(p.size),
+                                             _ptr(out), _stream()), "nfisam_sample_quantiles")
     return out
 
 
@@ -1184,35 +1210,15 @@ def check_mode_blocks(blocks: np.ndarray, cols, x_rows: int, scale=None, wrap=No
     not positive and finite, entries outside [0, n_entries), two blocks that share an entry (the converged points are stored
     by entry: list a column twice instead), a row outside [0, x_rows), per-entry arrays of another length, a scale that is
     negative or not finite (a device tensor's length alone is checked: checking its values would read it back)."""
-    if not isinstance(blocks, np.ndarray) or blocks.dtype != MMD_BLOCK_DTYPE or blocks.ndim != 1:
-        raise ValueError("blocks must be a 1-D numpy array of MMD_BLOCK_DTYPE")
-    cols = np.asarray(cols)
-    if cols.ndim != 1 or cols.size < 1:
-        raise ValueError("cols must be a 1-D list of at least one row")
-    ne = int(cols.size)
-    for name, a in (("scale", scale), ("wrap", wrap)):
-        if a is not None and (tuple(a.shape) if torch.is_tensor(a) else np.shape(a)) != (ne,):
-            raise ValueError("%s must have one value per entry (%d)" % (name, ne))
-    if not 1 <= blocks.size <= 65535:
-        raise ValueError("1..65535 blocks are supported, got %d" % blocks.size)
-    off, d = blocks["col_off"].astype(np.int64), blocks["d"].astype(np.int64)
-    bad = (d < 1) | (d > MODES_MAX_D)
-    if np.any(bad):
-        raise ValueError("block %d: width %d is outside 1..%d" % (int(np.argmax(bad)), int(d[np.argmax(bad)]), MODES_MAX_D))
-    bad = (off < 0) | (off + d > ne)
-    if np.any(bad):
-        raise ValueError("block %d: entries %d..%d leave the %d entries of the column list"
-                         % (int(np.argmax(bad)), int(off[np.argmax(bad)]), int((off + d)[np.argmax(bad)]), ne))
+    cols = {"cols": (cols, x_rows)}
+    off, d = _check_table_layout(blocks, MMD_BLOCK_DTYPE, "MMD_BLOCK_DTYPE", cols, dict(scale=scale, wrap=wrap), MODES_MAX_D)
     order = np.argsort(off, kind="stable")
     clash = (off[order][1:] < (off + d)[order][:-1])
     if np.any(clash):
         raise ValueError("blocks %d and %d share an entry: the converged points are stored by entry (list the column twice)"
                          % (int(order[:-1][np.argmax(clash)]), int(order[1:][np.argmax(clash)])))
-    v = blocks["inv_two_sigma2"]
-    if not np.all(np.isfinite(v) & (v > 0)):
-        raise ValueError("block %d: inv_two_sigma2 must be positive and finite" % int(np.argmin(np.isfinite(v) & (v > 0))))
-    if not 0 <= int(cols.min()) <= int(cols.max()) < int(x_rows):
-        raise ValueError("cols: a row is out of range of the %d rows of the matrix" % int(x_rows))
+    _check_bandwidths(blocks)
+    _check_rows(cols)
     if scale is not None and not (torch.is_tensor(scale) and scale.is_cuda):     # (a device tensor is taken as it is)
         sc = np.asarray(scale, dtype=np.float64)
         if not np.all(np.isfinite(sc)) or np.any(sc < 0):
@@ -1244,19 +1250,32 @@ def sample_modes(X, blocks: np.ndarray, cols, scale=None, wrap=None, weights=Non
     -> dict of device tensors: pos [n_entries, n] (converged points), dens [n_blocks, n], iters [n_blocks, n] int32 (negative:
     stopped on max_iters), labels [n_blocks, n] int32 (-1: left over), n_modes [n_blocks], mode_pos [n_blocks, max_modes, 16],
     mode_dens, mode_mass [n_blocks, max_modes] (NaN past n_modes), unlabelled [n_blocks]."""
-    if device is None:
-        device = X.device if torch.is_tensor(X) else "cuda"
-    if torch.device(device).type != "cuda":
-        raise RuntimeError("sample_modes needs a ROCm device (no CPU path exists)")
-    if not (torch.is_tensor(X) or isinstance(X, np.ndarray)) or X.ndim != 2:
-        raise ValueError("X must be a [rows, cols] tensor or array")
+    device = _row_major_front("sample_modes", device, X=X)
     if int(X.shape[0]) < 1:
         raise ValueError("sample_modes: no points")
     check_mode_blocks(blocks, cols, int(X.shape[1]), scale, wrap)
     check_mode_args(max_iters, tol, merge, max_modes)
     weights = _check_weights(weights, int(X.shape[0]))
-    return sample_modes_t(_mmd_matrix(X, "X", device), blocks, cols, scale, wrap, weights, tol, merge, max_iters, max_modes,
-                          checked=True)
+    return sample_modes_t(_columns(X, device), blocks, cols, scale, wrap, weights, tol, merge, max_iters, max_modes, checked=True)
+
+
+def _mode_shapes(blocks, cols, n, max_modes):
+    """{key of MODE_KEYS: (shape, dtype)} of the tensors of a modes call."""
+    nb, ne, mm = int(blocks.shape[0]), int(np.size(cols)), max(int(max_modes), 1)
+    return dict(pos=((ne, n), torch.float64), dens=((nb, n), torch.float64), iters=((nb, n), torch.int32),
+                labels=((nb, n), torch.int32), n_modes=((nb,), torch.int32), mode_pos=((nb, mm, MODES_MAX_D), torch.float64),
+                mode_dens=((nb, mm), torch.float64), mode_mass=((nb, mm), torch.float64), unlabelled=((nb,), torch.int32))
+
+
+def _modes_inputs(device, blocks, cols, scale, wrap, weights, shapes, given):
+    """What sample_modes_t and sample_modes_merge_t share once their arguments are checked
+    -> (the contiguous host table, the tables and per-entry arrays on the device by name (one upload), the weights on the
+    device or None, the result dict: the tensors `given` as they are, the others of `shapes` fresh)."""
+    blocks = np.ascontiguousarray(blocks)
+    dev = _upload_named(device, blocks=_table_bytes(blocks), cols=np.asarray(cols, dtype=np.int32), scale=_entry_f64(scale),
+                        wrap=_flags(wrap))
+    res = {k: given[k] if k in given else torch.empty(shape, dtype=dt, device=device) for k, (shape, dt) in shapes.items()}
+    return blocks, dev, _f64(weights, device), res
 
 
 def sample_modes_t(Xt, blocks: np.ndarray, cols, scale=None, wrap=None, weights=None, tol=1e-7, merge=1e-2, max_iters=500,
@@ -1264,53 +1283,27 @@ def sample_modes_t(Xt, blocks: np.ndarray, cols, scale=None, wrap=None, weights=
     """`sample_modes` on the COLUMN-major matrix Xt [x_rows, n] (a contiguous float32 device tensor, used in place): what the
     tree walk wrote.  `checked` skips the table and argument checks (the caller has made them); `out`: the dict of an earlier
     call with the same shapes, written in place."""
-    if not torch.is_tensor(Xt) or not Xt.is_cuda:
-        raise RuntimeError("Xt must be a tensor on a ROCm device (no CPU path exists)")
-    if Xt.ndim != 2 or Xt.dtype != torch.float32 or not Xt.is_contiguous():
-        raise ValueError("Xt must be a contiguous float32 [rows, points] tensor")
-    device = Xt.device
-    x_rows, n = int(Xt.shape[0]), int(Xt.shape[1])
+    x_rows, n = _column_major_front("Xt", Xt)
     if n < 1:
         raise ValueError("sample_modes: no points")
     if not checked:
         check_mode_blocks(blocks, cols, x_rows, scale, wrap)
         check_mode_args(max_iters, tol, merge, max_modes)
         weights = _check_weights(weights, n)
-    nb = int(blocks.shape[0])
-    cc = np.asarray(cols, dtype=np.int32)
-    ne = int(cc.size)
-    blocks = np.ascontiguousarray(blocks)
-    host = [blocks.view(np.uint8).reshape(-1), cc]
-    if scale is not None and not torch.is_tensor(scale):
-        host.append(np.ascontiguousarray(scale, dtype=np.float64))
-    if wrap is not None:
-        host.append(np.asarray(wrap).astype(np.uint8))
-    mm = max(int(max_modes), 1)
-    shapes = dict(pos=((ne, n), torch.float64), dens=((nb, n), torch.float64), iters=((nb, n), torch.int32),
-                  labels=((nb, n), torch.int32), n_modes=((nb,), torch.int32), mode_pos=((nb, mm, MODES_MAX_D), torch.float64),
-                  mode_dens=((nb, mm), torch.float64), mode_mass=((nb, mm), torch.float64), unlabelled=((nb,), torch.int32))
+    device, shapes = Xt.device, _mode_shapes(blocks, cols, n, max_modes)
+    if out is not None:
+        for k, (shape, dt) in shapes.items():
+            t = out.get(k)
+            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or t.device != device or not t.is_contiguous():
+                raise ValueError("out[%r] must be a contiguous %s tensor of shape %s on %s" % (k, dt, shape, device))
     with torch.cuda.device(device):
-        dev = upload(*host, device=device)
-        sc_d = None
-        if scale is not None:
-            sc_d = scale.to(device=device, dtype=torch.float64).contiguous() if torch.is_tensor(scale) else dev[2]
-        wr_d = dev[-1] if wrap is not None else None
-        w_d = None
-        if weights is not None:
-            w_d = weights.to(device=device, dtype=torch.float64).contiguous() if torch.is_tensor(weights) else \
-                torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float64)).to(device)
-        if out is None:
-            out = {k: torch.empty(shape, dtype=dt, device=device) for k, (shape, dt) in shapes.items()}
-        else:
-            for k, (shape, dt) in shapes.items():
-                t = out.get(k)
-                if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or t.device != device or not t.is_contiguous():
-                    raise ValueError("out[%r] must be a contiguous %s tensor of shape %s on %s" % (k, dt, shape, device))
-        _check(lib().nfisam_sample_modes(_ptr(Xt), x_rows, n, blocks.ctypes.data_as(C.c_void_p), C.c_void_p(dev[0].data_ptr()), nb,
-                                         _ptr(dev[1]), ne, _ptr(sc_d), _ptr(wr_d), _ptr(w_d), C.c_int(int(max_iters)),
-                                         C.c_double(float(tol)), C.c_double(float(merge)), C.c_int(int(max_modes)),
-                                         *[_ptr(out[k]) for k in MODE_KEYS], _stream()), "nfisam_sample_modes")
-    return out
+        blocks, dev, w_d, res = _modes_inputs(device, blocks, cols, scale, wrap, weights, shapes, out or {})
+        _check(lib().nfisam_sample_modes(_ptr(Xt), x_rows, n, blocks.ctypes.data_as(C.c_void_p), _ptr(dev["blocks"]),
+                                         int(blocks.shape[0]), _ptr(dev["cols"]), shapes["pos"][0][0], _ptr(dev["scale"]),
+                                         _ptr(dev["wrap"]), _ptr(w_d), C.c_int(int(max_iters)), C.c_double(float(tol)),
+                                         C.c_double(float(merge)), C.c_int(int(max_modes)), *[_ptr(res[k]) for k in MODE_KEYS],
+                                         _stream()), "nfisam_sample_modes")
+    return res if out is None else out
 
 
 def sample_modes_merge_t(out, x_rows: int, blocks: np.ndarray, cols, scale=None, wrap=None, weights=None, merge=1e-2, max_modes=16,
@@ -1319,46 +1312,26 @@ def sample_modes_merge_t(out, x_rows: int, blocks: np.ndarray, cols, scale=None,
     `sample_modes` / `sample_modes_t` call -- same table, cols, scale, wrap, weights -- merged again with another radius or
     max_modes, without climbing again.  x_rows: the rows of the matrix the call was made on.  -> a new dict that shares pos,
     dens and iters with `out`; the same bits as a full call with these arguments."""
-    for k in ("pos", "dens", "iters"):
+    for k in MODE_KEYS[:3]:
         t = out.get(k) if isinstance(out, dict) else None
         if not torch.is_tensor(t) or not t.is_cuda or t.ndim != 2 or not t.is_contiguous():
             raise ValueError("out[%r] must be the contiguous device tensor of an earlier sample_modes call" % k)
     pos, dens = out["pos"], out["dens"]
-    device, n = pos.device, int(pos.shape[1])
+    n = int(pos.shape[1])
     if not checked:
         check_mode_blocks(blocks, cols, x_rows, scale, wrap)
         check_mode_args(1, 0.0, merge, max_modes)
         weights = _check_weights(weights, n)
-    nb, cc = int(blocks.shape[0]), np.asarray(cols, dtype=np.int32)
-    ne = int(cc.size)
-    if pos.dtype != torch.float64 or dens.dtype != torch.float64 or tuple(pos.shape) != (ne, n) or tuple(dens.shape) != (nb, n) or n < 1:
+    shapes = _mode_shapes(blocks, cols, n, max_modes)
+    if n < 1 or any((tuple(t.shape), t.dtype) != shapes[k] for k, t in (("pos", pos), ("dens", dens))):
         raise ValueError("out does not belong to this table: pos %s, dens %s for %d entries, %d blocks" %
-                         (tuple(pos.shape), tuple(dens.shape), ne, nb))
-    blocks = np.ascontiguousarray(blocks)
-    host = [blocks.view(np.uint8).reshape(-1), cc]
-    if scale is not None and not torch.is_tensor(scale):
-        host.append(np.ascontiguousarray(scale, dtype=np.float64))
-    if wrap is not None:
-        host.append(np.asarray(wrap).astype(np.uint8))
-    mm = max(int(max_modes), 1)
-    with torch.cuda.device(device):
-        dev = upload(*host, device=device)
-        sc_d = None
-        if scale is not None:
-            sc_d = scale.to(device=device, dtype=torch.float64).contiguous() if torch.is_tensor(scale) else dev[2]
-        wr_d = dev[-1] if wrap is not None else None
-        w_d = None
-        if weights is not None:
-            w_d = weights.to(device=device, dtype=torch.float64).contiguous() if torch.is_tensor(weights) else \
-                torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float64)).to(device)
-        res = dict(pos=pos, dens=dens, iters=out["iters"], labels=torch.empty(nb, n, dtype=torch.int32, device=device),
-                   n_modes=torch.empty(nb, dtype=torch.int32, device=device),
-                   mode_pos=torch.empty(nb, mm, MODES_MAX_D, dtype=torch.float64, device=device),
-                   mode_dens=torch.empty(nb, mm, dtype=torch.float64, device=device),
-                   mode_mass=torch.empty(nb, mm, dtype=torch.float64, device=device),
-                   unlabelled=torch.empty(nb, dtype=torch.int32, device=device))
-        _check(lib().nfisam_sample_modes_merge(int(x_rows), n, blocks.ctypes.data_as(C.c_void_p), C.c_void_p(dev[0].data_ptr()), nb,
-                                               _ptr(dev[1]), ne, _ptr(sc_d), _ptr(wr_d), _ptr(w_d), C.c_double(float(merge)),
-                                               C.c_int(int(max_modes)), _ptr(pos), _ptr(dens),
-                                               *[_ptr(res[k]) for k in MODE_KEYS[3:]], _stream()), "nfisam_sample_modes_merge")
+                         (tuple(pos.shape), tuple(dens.shape), shapes["pos"][0][0], shapes["dens"][0][0]))
+    with torch.cuda.device(pos.device):
+        blocks, dev, w_d, res = _modes_inputs(pos.device, blocks, cols, scale, wrap, weights, shapes,
+                                              {k: out[k] for k in MODE_KEYS[:3]})
+        _check(lib().nfisam_sample_modes_merge(int(x_rows), n, blocks.ctypes.data_as(C.c_void_p), _ptr(dev["blocks"]),
+                                               int(blocks.shape[0]), _ptr(dev["cols"]), shapes["pos"][0][0], _ptr(dev["scale"]),
+                                               _ptr(dev["wrap"]), _ptr(w_d), C.c_double(float(merge)), C.c_int(int(max_modes)),
+                                               _ptr(pos), _ptr(dens), *[_ptr(res[k]) for k in MODE_KEYS[3:]], _stream()),
+               "nfisam_sample_modes_merge")
     return res

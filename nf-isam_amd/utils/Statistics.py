@@ -337,7 +337,7 @@ def sample_modes(x, blocks, circular=None, weights=None, sigma=None, scale=None,
     on_device = hasattr(x, "is_cuda") and x.is_cuda
     if device is None:
         device = x.device if on_device else "cuda"
-    out = sample_modes_t(_nh._mmd_matrix(x, "x", device), cols, flags, weights, sigma, scale, tol, merge, max_iters, max_modes,
+    out = sample_modes_t(_nh._columns(x, device), cols, flags, weights, sigma, scale, tol, merge, max_iters, max_modes,
                          checked=True)
     if not on_device:
         out["labels"] = out["labels"].cpu().numpy()
