@@ -213,7 +213,11 @@ typedef struct nfisam_sim_op {
 
 /* Simulate the n joint samples of a clique: every thread interprets `ops` (HOST array, copied into the launch) for its
  * own sample with a counter-based generator keyed by `seed`; x_out[n, D_out] row-major receives the first D_out
- * columns (D_total - D_out scratch columns may hold variables that are not part of the batch).                */
+ * columns (D_total - D_out scratch columns may hold variables that are not part of the batch).
+ * Generator: Philox4x32-10, counter (sample, op index, 0x9E3779B9, 0x243F6A88), key (seed low, seed high);
+ * float32 uniforms on (0, 1]; z0 z1 from (u0, u1), z2 from (u2, u3), bearings and the ADA_OBS / NH_OBS picks from u2, the
+ * NH_RING pick from u3.  NFISAM_ERR_ARG, before any launch: n_ops outside 1..NFISAM_SIM_MAX_OPS, D_total > 150, an op whose
+ * a, b, cand[j < k] or c leaves the D_total columns, a COPY with b < 0 or b + k > a, k out of range.              */
 int nfisam_simulate_clique(const nfisam_sim_op* ops, int n_ops, int n, int D_out, int D_total, uint64_t seed,
                            float* x_out, nfisam_stream_t stream);
 

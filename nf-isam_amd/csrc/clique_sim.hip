@@ -32,7 +32,8 @@ __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint
     c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
 }
 
-// four uniforms in (0,1) for (sample, op) under `seed`
+// four uniforms in (0,1] for (sample, op) under `seed`: x + 0.5f is not representable for x >= 2^23 and rounds to even, so
+// the largest value is exactly 1.0f (harmless: log 1 = 0, and the bearing (2 u - 1) pi is then pi)
 __device__ __forceinline__ void philox4(unsigned long long seed, uint32_t sample, uint32_t op, float (&u)[4]) {
     uint32_t c[4] = {sample, op, 0x9E3779B9u, 0x243F6A88u};
     uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
@@ -69,8 +70,13 @@ __device__ __forceinline__ float wrap_angle(float t) {
     return r - pi;
 }
 __device__ __forceinline__ Pose se2_exp(float vx, float vy, float w) {
+    // b = (1 - cos w) / w as 2 sin^2(w/2) / w: cosf(w) is exactly 1 up to |w| ~ 2.4e-4, so the difference form loses all of b
+    // there.  Below 1e-6 the series a = 1, b = w/2 is exact in float32 (the next terms are w^2/6 and w^2/12 < 2^-25).
     float a, b;
-    if (fabsf(w) < 1e-6f) { a = 1.0f; b = 0.5f * w; } else { a = sinf(w) / w; b = (1.0f - cosf(w)) / w; }
+    if (fabsf(w) < 1e-6f) { a = 1.0f; b = 0.5f * w; } else {
+        const float h = sinf(0.5f * w);
+        a = sinf(w) / w; b = 2.0f * h * h / w;
+    }
     return Pose{a * vx - b * vy, b * vx + a * vy, wrap_angle(w)};
 }
 __device__ __forceinline__ Pose compose(const Pose& A, const Pose& B) {
@@ -203,6 +209,21 @@ __global__ void __launch_bounds__(SIM_BLOCK) nsf_clique_sim_kernel(SimArgs a) {
     }
 }
 
+// the columns [first, first + width) lie inside the D_total columns of the launch
+bool cols_ok(int first, int width, int D_total) { return first >= 0 && first <= D_total - width; }
+
+// what an op reads: the width of the variable at a, at b and (ADA_OBS) at every cand[j < k]; 0 = the field is not read
+void read_widths(int code, int& wa, int& wb) {
+    switch (code) {
+    case NFISAM_SIM_REL_FWD: case NFISAM_SIM_REL_BWD: wa = 3; wb = 0; break;
+    case NFISAM_SIM_REL_OBS: wa = 3; wb = 3; break;
+    case NFISAM_SIM_RING: case NFISAM_SIM_NH_RING: case NFISAM_SIM_ADA_OBS:
+    case NFISAM_SIM_REL_R2_FWD: case NFISAM_SIM_REL_R2_BWD: wa = 2; wb = 0; break;
+    case NFISAM_SIM_RANGE_OBS: case NFISAM_SIM_NH_OBS: case NFISAM_SIM_REL_R2_OBS: wa = 2; wb = 2; break;
+    default: wa = 0; wb = 0; break;            // COPY (a, b index the source array) and the priors
+    }
+}
+
 }  // namespace
 
 extern "C" int nfisam_simulate_clique(const nfisam_sim_op* ops, int n_ops, int n, int D_out, int D_total,
@@ -212,12 +233,21 @@ extern "C" int nfisam_simulate_clique(const nfisam_sim_op* ops, int n_ops, int n
         return NFISAM_ERR_ARG;
     for (int o = 0; o < n_ops; ++o) {
         const nfisam_sim_op& op = ops[o];
+        if (op.code < NFISAM_SIM_COPY || op.code > NFISAM_SIM_REL_R2_OBS) return NFISAM_ERR_ARG;
+        // a COPY reads columns [b, b + k) of rows of a columns
+        if (op.code == NFISAM_SIM_COPY && (op.src == 0 || op.k < 1 || op.a < 1 || op.b < 0 || op.b > op.a - op.k))
+            return NFISAM_ERR_ARG;
+        if (op.code == NFISAM_SIM_ADA_OBS && (op.k < 1 || op.k > 4)) return NFISAM_ERR_ARG;
         const int w = (op.code == NFISAM_SIM_COPY) ? op.k : ((op.code == NFISAM_SIM_RING || op.code == NFISAM_SIM_NH_RING ||
                                                               op.code >= NFISAM_SIM_PRIOR_R2) ? 2 :
                       ((op.code == NFISAM_SIM_RANGE_OBS || op.code == NFISAM_SIM_ADA_OBS || op.code == NFISAM_SIM_NH_OBS) ? 1 : 3));
-        if (op.code < NFISAM_SIM_COPY || op.code > NFISAM_SIM_REL_R2_OBS || op.c < 0 || op.c + w > D_total) return NFISAM_ERR_ARG;
-        if (op.code == NFISAM_SIM_COPY && (op.src == 0 || op.k < 1)) return NFISAM_ERR_ARG;
-        if (op.code == NFISAM_SIM_ADA_OBS && (op.k < 1 || op.k > 4)) return NFISAM_ERR_ARG;
+        if (!cols_ok(op.c, w, D_total)) return NFISAM_ERR_ARG;
+        // every column an op reads lies inside the launch's LDS image
+        int wa, wb;
+        read_widths(op.code, wa, wb);
+        if ((wa && !cols_ok(op.a, wa, D_total)) || (wb && !cols_ok(op.b, wb, D_total))) return NFISAM_ERR_ARG;
+        if (op.code == NFISAM_SIM_ADA_OBS)
+            for (int j = 0; j < op.k; ++j) if (!cols_ok(op.cand[j], 2, D_total)) return NFISAM_ERR_ARG;
     }
     SimArgs a;
     memset(&a, 0, sizeof(a));

@@ -15,8 +15,9 @@ batch is simulated, normalised (`nfisam_normalize_columns`) and trained without 
   UnaryR2GaussianPriorFactor, UnaryR2RangeGaussianPriorFactor, R2RelativeGaussianLikelihoodFactor,
   R2RangeGaussianLikelihoodFactor           the R2 family of the toy examples             (reference :362, :451, :912, :2026)
 
-Random numbers: Philox4x32-10 keyed per clique from numpy's global RNG.  A factor type the backend does not know
-raises `DeviceSimulationUnsupported`; the solver then simulates that clique on the host.
+Random numbers: Philox4x32-10 keyed per clique from numpy's global RNG.  A factor type the backend does not know, a
+schedule of more than 40 ops or a column plan beyond the kernel's 150 columns raises `DeviceSimulationUnsupported`; the
+solver then simulates that clique on the host.
 """
 from typing import List
 
@@ -31,6 +32,10 @@ from factors.Factors import (AmbiguousDataAssociationFactor, BinaryFactorWithNul
 
 class DeviceSimulationUnsupported(NotImplementedError):
     pass
+
+
+# `nfisam_simulate_clique` keeps every column of a block's 256 samples in LDS and accepts up to 150 KB of it
+MAX_COLUMNS = 150
 
 
 class FusedSimulationBackend(object):
@@ -68,6 +73,8 @@ class FusedSimulationBackend(object):
             col[v] = off
             off += v.dim
         D_out = off
+        if D_out > MAX_COLUMNS:               # (before any child's message is sampled for nothing)
+            raise DeviceSimulationUnsupported("batch of %d columns" % D_out)
 
         def column(v):
             nonlocal off
@@ -154,6 +161,8 @@ class FusedSimulationBackend(object):
                 raise DeviceSimulationUnsupported("association factor drawing its observer")
         if len(ops) > nh.SIM_MAX_OPS or not ops:
             raise DeviceSimulationUnsupported("schedule of %d ops" % len(ops))
+        if off > MAX_COLUMNS:                 # with the scratch columns
+            raise DeviceSimulationUnsupported("column plan of %d columns" % off)
         seed = int(np.random.randint(0, 2 ** 62))
         x = nh.simulate_clique(ops, n, D_out, off, seed, self.device)
         self._keep = keep                      # the messages are read by the enqueued kernel (same stream)
