@@ -264,6 +264,29 @@ typedef struct nfisam_factor_term {
 int nfisam_factor_graph_log_density(const nfisam_factor_term* terms, int n_terms, const float* St, int total_dim, int n,
                                     double* log_p, double* per_factor, nfisam_stream_t stream);
 
+/* ---- the score of the joint density (factor_score.hip) -----------------------------------------------------------------
+ * Gt[r][p] = d/dx_r log p(X, Z) at point p: the reference's JointFactor.grad_x_log_pdf (src/sampler/sampler_utils.py:100-113)
+ * over its factors' `grad_x_log_pdf` (src/factors/Factors.py:829-850, :1450-1478, :2203-2223, :2732-2751, :3135-3156), for the
+ * table and the sample matrix of nfisam_factor_graph_log_density.  Float32 points in, float64 arithmetic, float64 out: the
+ * derivative of the float64 formula of the value entry at the float32 point -- of the smooth formula everywhere (small-angle
+ * series of the log map and of its Jacobian below |w| = 0.2; the value's |w| < 1e-10 / 1e-5 branches get no plateaus), the
+ * zero vector at a range of exactly 0, softmax weights with the value's max shift for mixtures (finite far from every
+ * component).
+ *   Factor f owns the slots slot_off[f] .. + {3, 6, 4, 2 + 2k, 2, 2, 4}[code] of scratch[n_slots][n], one per row it touches,
+ *   in the order a's rows, then b's or the candidates'; row r of Gt is the sum of the slots row_slot[row_off[r] ..
+ *   row_off[r + 1]), strictly in that order (the host lists a row's slots in table order); a row without a slot is 0.
+ *   terms[n_terms], slot_off[n_terms], row_off[total_dim + 1], row_slot[n_slots]: DEVICE arrays; Gt[total_dim][n] double;
+ *   scratch: nfisam_factor_graph_score_scratch_count(n_slots, n) doubles on the device.
+ * Two launches, no float atomics: two calls give the same bits, and a point's column does not depend on n or on its tile.
+ * NFISAM_ERR_ARG: a NULL pointer, a negative count, total_dim < 1 or > 65535, more than 524280 factors, n_slots > 10 n_terms.
+ * The device tables are not read on the host: a record with an unknown code, k outside 1..4 or a row outside [0, total_dim)
+ * yields NaN in its slots, a slot index or list outside the scratch yields NaN for its row (nothing is read or written out of
+ * bounds); the Python binding refuses such tables before upload.  (Additive: ABI 1600.)                               */
+size_t nfisam_factor_graph_score_scratch_count(int n_slots, int n);
+int nfisam_factor_graph_score(const nfisam_factor_term* terms, int n_terms, const float* St, int total_dim, int n,
+                              const int32_t* slot_off, int n_slots, const int32_t* row_off, const int32_t* row_slot, double* Gt,
+                              double* scratch, nfisam_stream_t stream);
+
 /* ---- two-sample MMD: the kernel sums of many column blocks in one launch (sample_mmd.hip) ---------------------------------
  * The reference grades a posterior against a reference sample set with an RBF-kernel MMD (src/utils/Statistics.py:13-84).
  * Block b of the table compares the entries col_off .. col_off + d of the row lists: entry e pairs row xcols[e] of Xt with
@@ -294,6 +317,24 @@ size_t nfisam_sample_mmd_scratch_count(int m, int n, int n_blocks);     /* 0 for
 int nfisam_sample_mmd(const float* Xt, int x_rows, int m, const float* Yt, int y_rows, int n, const nfisam_mmd_block* blocks,
                       const nfisam_mmd_block* blocks_dev, int n_blocks, const int32_t* xcols, const int32_t* ycols, int n_entries,
                       const double* scale, const uint8_t* wrap, double* sums, double* scratch, nfisam_stream_t stream);
+
+/* ---- kernel Stein discrepancy: the pairwise Stein sums of a sample set and its scores (sample_ksd.hip) -----------------------
+ * The reference's Gaussian_kernel_stein_discrepancy (src/utils/Statistics.py:216-245) for a DIAGONAL kernel precision p[rows],
+ * p_c >= 0.  With d = x_i - x_j, brought into [-pi, pi] as sign(d) wrap(|d|) where wrap[c] is set, and s = the scores:
+ *     k_ij = exp(-1/2 sum_c p_c d_c^2),   h_ij = k_ij [ s_i.s_j + sum_c (s_ic - s_jc) p_c d_c - sum_c p_c^2 d_c^2 + sum_c p_c ]
+ *     row[i] = sum over ALL j of h_ij,  diag[i] = h_ii = |s_i|^2 + sum_c p_c,  H[i][j] = h_ij (nullable; n <= 4096: 128 MiB).
+ *   Xt[rows][n]: COLUMN-major float32 device matrix; Gt[rows][n]: COLUMN-major float64 device matrix (what
+ *   nfisam_factor_graph_score writes); precision[rows] double, wrap[rows] uint8 (nullable): DEVICE arrays;
+ *   row[n], diag[n], H[n][n] double; scratch: nfisam_sample_ksd_scratch_count(n) doubles on the device.
+ * Float32 points in; float64 differences, products, exp and sums; direct differences.  Two launches, no float atomics: a
+ * 256-thread group per 64 x 64 tile of the full grid of pairs writes one partial per (tile, i), then row[i] adds them in tile
+ * order: two calls give the same bits, `row` is the same bits with and without H, and H is symmetric to the bit.
+ * NFISAM_ERR_ARG: a NULL pointer (wrap and H excepted), rows or n < 1, n > 65535 * 64, H with n > 4096.  The precision is not
+ * read on the host: the Python binding refuses negative or non-finite entries before upload.  (Additive: ABI 1600.)   */
+#define NFISAM_KSD_MATRIX_MAX_N 4096
+size_t nfisam_sample_ksd_scratch_count(int n);                          /* 0 for an n the entry refuses */
+int nfisam_sample_ksd(const float* Xt, const double* Gt, int rows, int n, const double* precision, const uint8_t* wrap,
+                      double* row, double* diag, double* H, double* scratch, nfisam_stream_t stream);
 
 /* ---- sample summaries: means, resultant lengths, covariances and quantiles of many column blocks (sample_summary.hip) -------
  * The reference summarises a draw on the host: `sample_mean` (src/utils/Statistics.py:151-171: np.mean, and scipy's

@@ -29,7 +29,11 @@ Density evaluation: every class has `log_pdf(x)` / `pdf(x)` (x: [n, sum of the v
 One deliberate difference: the reference's mixture takes `np.log` of a sum of `exp`s, which is -inf far from every
 component; here mixtures use log-sum-exp and stay finite (equal wherever the reference is finite).  The log map uses the
 half-angle form (th/2) cot(th/2), which does not cancel for small th.  `density_record()` returns the factor's row of the
-device table of `nfisam_factor_graph_log_density` (include/nfisam_hip.h); gradients are not provided.
+device table of `nfisam_factor_graph_log_density` (include/nfisam_hip.h).
+
+Scores: the seven classes with a `density_record` have `grad_x_log_pdf(x)` -> [n, dim] float64, the derivative of the
+class's own `log_pdf` (of its smooth formula: small-angle series of the log map below |w| = 0.2), with the conventions of the
+device entry `nfisam_factor_graph_score`: the zero vector at a range of exactly 0, softmax weights for mixtures.
 """
 from typing import Iterable, List, Union
 
@@ -158,6 +162,53 @@ def _se2_tangent_log_pdf(tx, ty, w, precision, log_norm) -> np.ndarray:
     return log_norm - 0.5 * _quad_form(v, precision) + log_det
 
 
+_SERIES_H = 0.1
+
+
+def _log_map_terms(w):
+    """a = h cot h (h = w / 2), da / dw = (cot h - h / sin^2 h) / 2 and d/dw of the log-det term 2 log|h / sin h|,
+    1 / h - cot h.  The two derivatives are differences of terms of size 1 / h that leave h / 3: the plain forms lose
+    1.5 eps / h^2 relative.  Below |h| = 0.1 the Taylor series through h^9 replace them: there the plain forms have lost
+    two digits (1.7e-14) and the first dropped series terms are 3.9e-15 and 6.5e-16 relative, so neither side of the switch
+    is more than about two digits worse than the other (the same switch as csrc/factor_score.hip)."""
+    h = 0.5 * np.asarray(w, dtype=np.float64)
+    ser = np.abs(h) < _SERIES_H
+    h2 = np.where(ser, h * h, 0.0)
+    a_s = 1.0 - h2 * (1.0 / 3.0 + h2 * (1.0 / 45.0 + h2 * (2.0 / 945.0 + h2 * (1.0 / 4725.0 + h2 * (2.0 / 93555.0)))))
+    da_s = -h * (1.0 / 3.0 + h2 * (2.0 / 45.0 + h2 * (2.0 / 315.0 + h2 * (4.0 / 4725.0 + h2 * (2.0 / 18711.0)))))
+    dl_s = h * (1.0 / 3.0 + h2 * (1.0 / 45.0 + h2 * (2.0 / 945.0 + h2 * (1.0 / 4725.0 + h2 * (2.0 / 93555.0)))))
+    hp = np.where(ser, 1.0, h)
+    sh, ch = np.sin(hp), np.cos(hp)
+    cot = ch / sh
+    return (np.where(ser, a_s, hp * cot), np.where(ser, da_s, 0.5 * (cot - hp / (sh * sh))),
+            np.where(ser, dl_s, 1.0 / hp - cot))
+
+
+def _se2_tangent_score(tx, ty, w, precision):
+    """d/d(tx, ty, w) of `_se2_tangent_log_pdf`: of its smooth formula everywhere (the value's |w| < 1e-10 and |w| < 1e-5
+    branches are flat spots of that width and get no derivative-zero plateaus)."""
+    a, da, dl = _log_map_terms(w)
+    h = 0.5 * w
+    P = 0.5 * (precision + precision.T)
+    vx, vy = a * tx + h * ty, a * ty - h * tx
+    gvx = -(P[0, 0] * vx + P[0, 1] * vy + P[0, 2] * w)
+    gvy = -(P[0, 1] * vx + P[1, 1] * vy + P[1, 2] * w)
+    gvw = -(P[0, 2] * vx + P[1, 2] * vy + P[2, 2] * w)
+    return (a * gvx - h * gvy, h * gvx + a * gvy,
+            gvw + gvx * (da * tx + 0.5 * ty) + gvy * (da * ty - 0.5 * tx) + dl)
+
+
+def _range_score(ta, tb, d, sigma):
+    """d/d(ta) of log N(|ta - tb| - d; 0, sigma^2) (d/d(tb) is its negative): -(r - d) / sigma^2 (ta - tb) / r, and the
+    zero vector at r = 0 exactly, where the range has no direction."""
+    diff = ta - tb
+    r = np.sqrt((diff ** 2).sum(1))
+    c = np.zeros_like(r)
+    ok = r > 0
+    c[ok] = -(r[ok] - d) / (sigma ** 2 * r[ok])
+    return c[:, None] * diff
+
+
 def _as_points(x, width: int) -> np.ndarray:
     x = np.asarray(x, dtype=np.float64)
     if x.ndim != 2 or x.shape[1] != width:
@@ -225,6 +276,16 @@ class UnarySE2ApproximateGaussianPriorFactor(ExplicitPriorFactor, UnaryFactor):
         dx, dy = x[:, 0] - px, x[:, 1] - py
         w = wrap_pi(wrap_pi(-pth) + wrap_pi(x[:, 2]))
         return _se2_tangent_log_pdf(c * dx + s * dy, -s * dx + c * dy, w, self._precision, self._log_norm)
+
+    def grad_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """d log_pdf / d(x, y, theta), [n, 3] float64 (reference :829-850); the heading wrap has derivative 1."""
+        x = _as_points(x, 3)
+        px, py, pth = self._prior_pose.array
+        c, s = np.cos(pth), np.sin(pth)
+        dx, dy = x[:, 0] - px, x[:, 1] - py
+        w = wrap_pi(wrap_pi(-pth) + wrap_pi(x[:, 2]))
+        gtx, gty, gw = _se2_tangent_score(c * dx + s * dy, -s * dx + c * dy, w, self._precision)
+        return np.stack([c * gtx - s * gty, s * gtx + c * gty, gw], 1)
 
     def pdf(self, x: np.ndarray) -> np.ndarray:
         return np.exp(self.log_pdf(x))
@@ -333,6 +394,21 @@ class SE2RelativeGaussianLikelihoodFactor(LikelihoodFactor, BinaryFactor, OdomFa
         w = wrap_pi(wrap_pi(-oth) + wrap_pi(wrap_pi(-wrap_pi(x[:, 2])) + wrap_pi(x[:, 5])))
         return _se2_tangent_log_pdf(co * rx + so * ry, -so * rx + co * ry, w, self._precision, self._log_norm)
 
+    def grad_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """d log_pdf / d[T_i | T_j], [n, 6] float64 (reference :1450-1478)."""
+        x = _as_points(x, 6)
+        ox, oy, oth = self.observation
+        ci, si = np.cos(x[:, 2]), np.sin(x[:, 2])
+        dx, dy = x[:, 3] - x[:, 0], x[:, 4] - x[:, 1]
+        ux, uy = ci * dx + si * dy, -si * dx + ci * dy              # the difference in pose i's frame
+        rx, ry = ux - ox, uy - oy
+        co, so = np.cos(oth), np.sin(oth)
+        w = wrap_pi(wrap_pi(-oth) + wrap_pi(wrap_pi(-wrap_pi(x[:, 2])) + wrap_pi(x[:, 5])))
+        gtx, gty, gw = _se2_tangent_score(co * rx + so * ry, -so * rx + co * ry, w, self._precision)
+        grx, gry = co * gtx - so * gty, so * gtx + co * gty
+        gx, gy = ci * grx - si * gry, si * grx + ci * gry           # d/d(x_j, y_j)
+        return np.stack([-gx, -gy, grx * uy - gry * ux - gw, gx, gy, gw], 1)
+
     def pdf(self, x: np.ndarray) -> np.ndarray:
         return np.exp(self.log_pdf(x))
 
@@ -428,6 +504,18 @@ class SE2R2RangeGaussianLikelihoodFactor(LikelihoodFactor, BinaryFactor):
         delta = np.sqrt(((t1 - t2) ** 2).sum(1)) - self._observation[0]
         return _gaussian_log_norm(self._sigma ** 2) - 0.5 * delta * delta * (1.0 / self._sigma ** 2)
 
+    def grad_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """d log_pdf / d[var1 | var2], float64 (reference :2732-2751, :2203-2223): along the line between the two ends,
+        0 in a heading column, and the zero vector at a range of exactly 0 (the reference divides by it)."""
+        x = _as_points(x, self.var1.dim + self.var2.dim)
+        d1 = self.var1.dim
+        i1 = np.asarray(self.var1.t_dim_indices)
+        i2 = d1 + np.asarray(self.var2.t_dim_indices)
+        g = _range_score(x[:, i1], x[:, i2], self._observation[0], self._sigma)
+        out = np.zeros_like(x)
+        out[:, i1], out[:, i2] = g, -g
+        return out
+
     def density_record(self) -> dict:
         return dict(code="RANGE", a=self.var1, b=self.var2, cand=[],
                     p=[float(self._observation[0]), 1.0 / self._sigma ** 2, _gaussian_log_norm(self._sigma ** 2)])
@@ -520,6 +608,19 @@ class BinaryFactorMixture(LikelihoodFactor):
         terms = np.stack([c.log_pdf(x[:, self.comp2idx[c]]) + np.log(w) for c, w in zip(self.components, self.weights)])
         top = terms.max(0)
         return top + np.log(np.exp(terms - top).sum(0))
+
+    def grad_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """d log_pdf / dx = sum_k r_k grad log p_k with r the softmax of the weighted component terms, shifted by their
+        maximum like `log_pdf`: finite far from every component, where the reference (:3135-3156) divides by a sum of pdfs
+        that has underflowed to 0.  A repeated candidate's contributions add into the same columns."""
+        x = _as_points(x, self.dim)
+        terms = np.stack([c.log_pdf(x[:, self.comp2idx[c]]) + np.log(w) for c, w in zip(self.components, self.weights)])
+        e = np.exp(terms - terms.max(0))
+        r = e / e.sum(0)
+        out = np.zeros_like(x)
+        for k, c in enumerate(self.components):
+            out[:, self.comp2idx[c]] += r[k][:, None] * c.grad_x_log_pdf(x[:, self.comp2idx[c]])
+        return out
 
     def density_record(self) -> dict:
         """A k-way range mixture: candidates may repeat (the null hypothesis: one landmark, two sigmas)."""
@@ -661,6 +762,11 @@ class UnaryR2GaussianPriorFactor(ExplicitPriorFactor, UnaryFactor):
         d = _as_points(x, 2) - self._mu
         return _gaussian_log_norm(self._covariance) - 0.5 * _quad_form(d, np.linalg.inv(self._covariance))
 
+    def grad_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """-precision (x - mu), [n, 2] float64."""
+        P = np.linalg.inv(self._covariance)
+        return -(_as_points(x, 2) - self._mu) @ (0.5 * (P + P.T))
+
     def pdf(self, x: np.ndarray) -> np.ndarray:
         return np.exp(self.log_pdf(x))
 
@@ -726,6 +832,11 @@ class UnaryR2RangeGaussianPriorFactor(ExplicitPriorFactor, UnaryFactor):
         x = _as_points(x, 2)
         delta = np.sqrt(((x - self._center) ** 2).sum(1)) - self._mu
         return _gaussian_log_norm(self._sigma ** 2) - 0.5 * delta * delta * (1.0 / self._sigma ** 2)
+
+    def grad_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """d log_pdf / dx, [n, 2] float64: the range term's derivative with one end at the centre; 0 at the centre itself."""
+        x = _as_points(x, 2)
+        return _range_score(x, self._center[None, :], self._mu, self._sigma)
 
     def pdf(self, x: np.ndarray) -> np.ndarray:
         return np.exp(self.log_pdf(x))
@@ -809,6 +920,13 @@ class R2RelativeGaussianLikelihoodFactor(LikelihoodFactor, BinaryFactor, OdomFac
         x = _as_points(x, 4)
         d = x[:, 2:] - x[:, :2] - self._observation
         return _gaussian_log_norm(self._covariance) - 0.5 * _quad_form(d, np.linalg.inv(self._covariance))
+
+    def grad_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """d log_pdf / d[var1 | var2], [n, 4] float64: +-precision (var2 - var1 - observation)."""
+        x = _as_points(x, 4)
+        P = np.linalg.inv(self._covariance)
+        g = -(x[:, 2:] - x[:, :2] - self._observation) @ (0.5 * (P + P.T))
+        return np.concatenate([-g, g], 1)
 
     def pdf(self, x: np.ndarray) -> np.ndarray:
         return np.exp(self.log_pdf(x))

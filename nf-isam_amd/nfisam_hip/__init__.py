@@ -31,6 +31,8 @@ EXPORTS = [
     "nfisam_sample_mmd", "nfisam_sample_mmd_scratch_count",
     "nfisam_sample_moments", "nfisam_sample_quantiles",
     "nfisam_sample_modes", "nfisam_sample_modes_merge",
+    "nfisam_factor_graph_score", "nfisam_factor_graph_score_scratch_count",
+    "nfisam_sample_ksd", "nfisam_sample_ksd_scratch_count",
 ]
 
 
@@ -116,6 +118,8 @@ def lib():
         _lib.nfisam_nsf_train_plan_stream.restype = C.c_void_p
         _lib.nfisam_nsf_train_plan_enqueued.restype = C.c_long
         _lib.nfisam_sample_mmd_scratch_count.restype = C.c_size_t
+        _lib.nfisam_factor_graph_score_scratch_count.restype = C.c_size_t
+        _lib.nfisam_sample_ksd_scratch_count.restype = C.c_size_t
         for name in EXPORTS:
             getattr(_lib, name)   # raises AttributeError if the ABI is incomplete
     return _lib
@@ -1048,6 +1052,144 @@ def mmd_sums_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, scale=None, wrap=None, 
                                        _ptr(dev["scale"]), _ptr(dev["wrap"]), _ptr(sums), _ptr(scratch), _stream()),
                "nfisam_sample_mmd")
     return sums
+
+
+# ---- the score of the joint density (nfisam_factor_graph_score) ------------------------------------------------------------------
+# slots a factor writes, by code: one per row it touches, a's rows first, then b's or the candidates' (csrc/factor_score.hip)
+_FAC_SLOTS = {1: 3, 2: 6, 3: 4, 5: 2, 6: 2, 7: 4}                  # (4, RANGE_MIX: 2 + 2 k)
+
+
+def _slot_rows(terms: np.ndarray):
+    """-> (slot_off [n_terms] int32, rows [n_slots] int64: the row of G every slot adds into), in table order."""
+    slot_off, rows = np.zeros(terms.shape[0], dtype=np.int32), []
+    for i in range(terms.shape[0]):
+        code, a, b, k = int(terms["code"][i]), int(terms["a"][i]), int(terms["b"][i]), int(terms["k"][i])
+        slot_off[i] = len(rows)
+        na, nb = _FAC_ROWS[code]
+        rows += range(a, a + na)
+        if code == FAC_CODES["RANGE_MIX"]:
+            for c in terms["cand"][i, :k]:
+                rows += (int(c), int(c) + 1)
+        else:
+            rows += range(b, b + nb)
+    return slot_off, np.asarray(rows, dtype=np.int64)
+
+
+def pack_score_gather(terms: np.ndarray, total_dim: int) -> dict:
+    """The gather lists of `factor_graph_score` for the table `terms` (checked here: `check_factor_terms`):
+    slot_off [n_terms] int32 (the first scratch slot of every factor), n_slots, and the CSR row_off [total_dim + 1] /
+    row_slot [n_slots] int32: row r of G is the sum of the slots row_slot[row_off[r] : row_off[r + 1]], listed in table
+    order (ascending slot index).  Every slot appears exactly once; a repeated candidate's slots land in the same rows."""
+    check_factor_terms(terms, int(total_dim))
+    slot_off, rows = _slot_rows(terms)
+    order = np.argsort(rows, kind="stable")                            # by row; table order within a row
+    row_off = np.zeros(int(total_dim) + 1, dtype=np.int32)
+    row_off[1:] = np.cumsum(np.bincount(rows, minlength=int(total_dim)))
+    return dict(slot_off=slot_off, n_slots=int(rows.size), row_off=row_off, row_slot=order.astype(np.int32))
+
+
+def factor_graph_score(terms: np.ndarray, S, device, terms_dev=None, gather=None, slots=False):
+    """G = d/dx log p(X, Z) at the n rows of S (nfisam_factor_graph_score): `terms` the numpy FACTOR_DTYPE table
+    (`pack_factor_terms`), S [n, total_dim] in the walk's column layout (tensor or numpy; float32 points, the arithmetic
+    is float64).  Launched on the current stream.  `terms_dev`: an uploaded copy of `terms` to reuse; `gather`: the result of
+    `pack_score_gather(terms, total_dim)` to reuse.
+    -> G [n, total_dim] float64 device tensor (a view of the column-major result); with slots=True: (G, slot values
+    [n_slots, n] float64, the per-factor partial derivatives the rows are added from)."""
+    if not (torch.is_tensor(S) or isinstance(S, np.ndarray)) or S.ndim != 2:
+        raise ValueError("S must be a [n, total_dim] tensor or array")
+    if gather is None:
+        gather = pack_score_gather(terms, int(S.shape[1]))
+    out = factor_graph_score_t(terms, _columns(S, device), device, terms_dev=terms_dev, gather=gather, slots=slots)
+    return (out[0].t(), out[1]) if slots else out.t()
+
+
+def factor_graph_score_t(terms: np.ndarray, St, device, terms_dev=None, gather=None, slots=False):
+    """`factor_graph_score` on the COLUMN-major matrix St [total_dim, n] (contiguous float32 device tensor): what the tree
+    walk wrote, differentiated in place.  -> Gt [total_dim, n] float64 device tensor, the layout `ksd_sums_t` reads."""
+    if not torch.is_tensor(St) or St.ndim != 2 or St.dtype != torch.float32 or not St.is_contiguous():
+        raise ValueError("St must be a contiguous float32 [total_dim, n] tensor")
+    total_dim, n = int(St.shape[0]), int(St.shape[1])
+    if gather is None:
+        gather = pack_score_gather(terms, total_dim)                   # (checks the table)
+    elif gather["row_off"].shape[0] != total_dim + 1 or gather["slot_off"].shape[0] != terms.shape[0]:
+        raise ValueError("gather was packed for another table or another total_dim")
+    if total_dim > 65535:
+        raise ValueError("factor_graph_score: at most 65535 rows are supported, got %d" % total_dim)
+    nt, ns = int(terms.shape[0]), int(gather["n_slots"])
+    Gt = torch.zeros(total_dim, n, dtype=torch.float64, device=device)
+    vals = torch.empty(ns, n, dtype=torch.float64, device=device)     # the scratch: from torch's allocator
+    if nt > 0 and n > 0:
+        with torch.cuda.device(device):
+            dev = _upload_named(device, terms=terms_dev if terms_dev is not None else _table_bytes(np.ascontiguousarray(terms)),
+                                slot_off=gather["slot_off"], row_off=gather["row_off"], row_slot=gather["row_slot"])
+            count = int(lib().nfisam_factor_graph_score_scratch_count(ns, n))
+            assert count == vals.numel()
+            _check(lib().nfisam_factor_graph_score(_ptr(dev["terms"]), nt, _ptr(St), total_dim, n, _ptr(dev["slot_off"]), ns,
+                                                   _ptr(dev["row_off"]), _ptr(dev["row_slot"]), _ptr(Gt), _ptr(vals),
+                                                   _stream()), "nfisam_factor_graph_score")
+    return (Gt, vals) if slots else Gt
+
+
+# ---- kernel Stein discrepancy: the pairwise Stein sums (nfisam_sample_ksd) ----------------------------------------------------------
+KSD_MATRIX_MAX_N = 4096                                               # NFISAM_KSD_MATRIX_MAX_N
+
+
+def check_ksd_args(rows: int, n: int, g_shape, precision, wrap=None, matrix=False) -> None:
+    """ValueError for what the kernel must not see: no point, a score matrix of another shape than the points', a precision
+    that is not one finite value >= 0 per column, flags of another length, the matrix for more than 4096 points."""
+    if n < 1 or rows < 1:
+        raise ValueError("ksd_sums needs at least one point and one column")
+    if tuple(g_shape) != (rows, n):
+        raise ValueError("the score matrix must have the shape of the points: %s, got %s" % ((rows, n), tuple(g_shape)))
+    p = precision.detach().cpu().numpy() if torch.is_tensor(precision) else np.asarray(precision, dtype=np.float64)
+    if p.shape != (rows,):
+        raise ValueError("precision must have one value per column (%d)" % rows)
+    if not np.all(np.isfinite(p)) or np.any(p < 0):
+        raise ValueError("precision must be finite and >= 0")
+    if wrap is not None and np.shape(wrap) != (rows,):
+        raise ValueError("wrap must have one flag per column (%d)" % rows)
+    if matrix and n > KSD_MATRIX_MAX_N:
+        raise ValueError("the matrix H is returned for at most %d points, got %d" % (KSD_MATRIX_MAX_N, n))
+
+
+def ksd_sums(X, G, precision, wrap=None, matrix=False, device=None):
+    """The Stein sums of the points X [n, D] (tensor or numpy; float32 points) with scores G [n, D] (float64) under the
+    Gaussian kernel of DIAGONAL precision `precision` [D] >= 0 (nfisam_sample_ksd, on the current stream); wrap [D] marks
+    angles (differences brought into [-pi, pi]).
+    -> {"row": [n] sum_j h_ij over all j, "diag": [n] h_ii, "H": [n, n] with matrix=True (n <= 4096), else None}, float64
+    device tensors.  `Statistics.ksd_from_sums` forms the U- and V-statistics."""
+    device = _row_major_front("ksd_sums", device, X=X, G=G)
+    check_ksd_args(int(X.shape[1]), int(X.shape[0]), (int(G.shape[1]), int(G.shape[0])), precision, wrap, matrix)
+    Gt = G.to(device=device, dtype=torch.float64).t().contiguous() if torch.is_tensor(G) else \
+        torch.from_numpy(np.ascontiguousarray(np.asarray(G, dtype=np.float64).T)).to(device)
+    return ksd_sums_t(_columns(X, device), Gt, precision, wrap, matrix, checked=True)
+
+
+def ksd_sums_t(Xt, Gt, precision, wrap=None, matrix=False, checked=False):
+    """`ksd_sums` on the COLUMN-major matrices Xt [D, n] (contiguous float32) and Gt [D, n] (contiguous float64) on one
+    ROCm device, used in place: the tree walk's St and `factor_graph_score_t`'s result."""
+    rows, n = _column_major_front("Xt", Xt)
+    if not torch.is_tensor(Gt) or not Gt.is_cuda:
+        raise RuntimeError("Gt must be a tensor on a ROCm device (no CPU path exists)")
+    if Gt.ndim != 2 or Gt.dtype != torch.float64 or not Gt.is_contiguous():
+        raise ValueError("Gt must be a contiguous float64 [rows, points] tensor")
+    if Gt.device != Xt.device:
+        raise ValueError("Xt and Gt must be on the same device")
+    if not checked:
+        check_ksd_args(rows, n, tuple(Gt.shape), precision, wrap, matrix)
+    device = Xt.device
+    with torch.cuda.device(device):
+        dev = _upload_named(device, precision=_entry_f64(precision), wrap=_flags(wrap))
+        count = int(lib().nfisam_sample_ksd_scratch_count(n))
+        if count < 1:
+            raise ValueError("ksd_sums: %d points exceed the grid" % n)
+        scratch = torch.empty(count, dtype=torch.float64, device=device)
+        row = torch.empty(n, dtype=torch.float64, device=device)
+        diag = torch.empty(n, dtype=torch.float64, device=device)
+        H = torch.empty(n, n, dtype=torch.float64, device=device) if matrix else None
+        _check(lib().nfisam_sample_ksd(_ptr(Xt), _ptr(Gt), rows, n, _ptr(dev["precision"]), _ptr(dev["wrap"]), _ptr(row),
+                                       _ptr(diag), _ptr(H), _ptr(scratch), _stream()), "nfisam_sample_ksd")
+    return dict(row=row, diag=diag, H=H)
 
 
 # ---- sample summaries: means, resultant lengths, covariances, quantiles (nfisam_sample_moments, nfisam_sample_quantiles) --------

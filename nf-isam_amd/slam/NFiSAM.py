@@ -969,6 +969,107 @@ class NFiSAM(FactorGraphSolver):
         estimate (FactorGraphSolver.plot2d_MAP_rbt_only, src/slam/FactorGraphSolver.py:660-671).  -> variable -> [dim]."""
         return self.posterior_diagnostics(samples)["map_sample"]
 
+    # ---- the solver graded against the factor graph itself: score and kernel Stein discrepancy -------------------------
+    def _score_launch(self, St, pcol, device):
+        """Gt [total_dim, n] float64 on the device from the column-major points St: the cached table of `_joint_terms`, its
+        gather lists kept next to it."""
+        cache = self._joint_terms(pcol)
+        total_dim = int(St.shape[0])
+        g = cache.get("gather")
+        if g is None or g["row_off"].shape[0] != total_dim + 1:
+            g = cache["gather"] = _nh.pack_score_gather(cache["terms"], total_dim)
+        if device not in cache["dev"] and int(St.shape[1]):
+            cache["dev"][device], = _nh.upload(cache["terms"].view(np.uint8).reshape(-1), device=device, cached=True)
+        return _nh.factor_graph_score_t(cache["terms"], St, device, terms_dev=cache["dev"].get(device), gather=g)
+
+    def joint_score(self, samples) -> np.ndarray:
+        """The score grad_x log p(X, Z) of the measurement factors at n points: the reference's JointFactor.grad_x_log_pdf
+        (src/sampler/sampler_utils.py:101-118) over `physical_factors`, on the device in float64 at the float32 points
+        (nfisam_factor_graph_score: the zero vector at a range of exactly 0, softmax weights for mixtures -- finite where the
+        reference divides by zero).
+
+        samples: as `joint_log_pdf`.  -> np.ndarray [n, total_dim] float64, columns in the walk's permanent layout
+        (`_post_columns`: variable -> first column).  Raises what `joint_log_pdf` raises, before anything is launched."""
+        factors = self.physical_factors
+        if not factors or not self._elimination_ordering:
+            raise RuntimeError("joint_score: no factor graph yet (run an incremental update first)")
+        values, n = self._check_points(samples, "joint_score")
+        pcol, total_dim = self._post_columns()
+        self._joint_terms(pcol)                              # (packs: an unknown factor class raises here)
+        device = _device()
+        S = self._points_matrix(values, n, pcol, total_dim, device)
+        St = S.t().contiguous() if torch.is_tensor(S) else torch.from_numpy(np.ascontiguousarray(S.T)).to(device)
+        return self._score_launch(St, pcol, device).t().cpu().numpy()
+
+    def posterior_ksd(self, samples=None, n: int = None, sigma=None, standardise: bool = True, nboot: int = 0,
+                      seed=None) -> dict:
+        """The solver graded against the factor graph itself, without a second sample set: the Gaussian kernel Stein
+        discrepancy (reference src/utils/Statistics.py:216-245) between posterior samples and the joint density p(X, Z)
+        through its score, both evaluated on the device where the sample matrix lies (nfisam_factor_graph_score,
+        nfisam_sample_ksd).
+
+        samples=None draws `n` (default posterior_sample_num) points through the tree walk; otherwise `samples` is graded (as
+        `joint_log_pdf` accepts it) and nothing is drawn.  standardise: every column's differences are divided by its spread
+        (the circular standard deviation for a heading; a column without spread leaves the kernel: scale 0); sigma: the
+        bandwidth in those units, None = sqrt(total_dim).  Headings are flagged circular from the variables: see
+        `Statistics.kernel_stein_discrepancy` on the antipode.  nboot > 0 adds the reference's multinomial bootstrap, its draws
+        from a generator of its own seeded with `seed`.
+        -> dict: ustat (None for n = 1), vstat, row_mean [n] (sum_j h_ij / n per point: where the draw disagrees with the
+        graph), precision (variable -> [dim]), sigma, n, and p_value / bootstrap with nboot > 0.
+        Nothing of the solver's state or random streams is touched (a draw uses the walk's generator as `sample_posterior`
+        does).  Raises RuntimeError when there is no graph / tree yet, NotImplementedError naming a factor class without a
+        device code, ValueError for bad points or options -- before anything is launched."""
+        from utils import Statistics as ST
+        what = "posterior_ksd"
+        if not self.physical_factors or not self._elimination_ordering:
+            raise RuntimeError("%s: no factor graph yet (run an incremental update first)" % what)
+        if samples is None:
+            tree = self._physical_bayes_tree
+            if tree is None or tree.root is None:
+                raise RuntimeError("%s: no Bayes tree yet (run an incremental update first)" % what)
+            for clique in tree.clique_ordering():
+                if clique not in self._clique_density_model:
+                    raise RuntimeError("%s: clique %s has no trained model yet" % (what, clique))
+        values, rows = self._summary_points(what, samples, n)
+        nboot = int(nboot)
+        if nboot < 0 or (nboot > 0 and (rows < 2 or rows > _nh.KSD_MATRIX_MAX_N)):
+            raise ValueError("%s: the bootstrap needs nboot >= 0 and 2 <= n <= %d" % (what, _nh.KSD_MATRIX_MAX_N))
+        if sigma is not None and not (np.isfinite(sigma) and sigma > 0):
+            raise ValueError("%s: sigma must be positive and finite" % what)
+        pcol, total_dim = self._post_columns()
+        self._joint_terms(pcol)                              # (packs: an unknown factor class raises here)
+        order = list(self._elimination_ordering)
+        flags = np.zeros(total_dim, dtype=bool)
+        used = np.zeros(total_dim, dtype=bool)
+        for v in order:
+            flags[pcol[v]:pcol[v] + v.dim] = [bool(c) for c in v.circular_dim_list]
+            used[pcol[v]:pcol[v] + v.dim] = True
+        St, _, _ = self._summary_matrix(what, samples, values, rows, False, None, pcol, total_dim)
+        device = St.device
+        cols = np.flatnonzero(used)
+        scale = np.zeros(total_dim)
+        if standardise:
+            circ = flags[cols].astype(np.uint8)
+            mean, res, cov = _nh.sample_moments_t(St, _nh.pack_moment_blocks(np.ones(cols.size, dtype=np.int64)), cols,
+                                                  circ if circ.any() else None, None, checked=True)
+            scale[cols] = ST.mode_scale(cov.cpu().numpy(), res.cpu().numpy(), flags[cols])
+        else:
+            scale[cols] = 1.0
+        sig = float(np.sqrt(cols.size)) if sigma is None else float(sigma)
+        precision = scale * scale / (sig * sig)
+        Gt = self._score_launch(St, pcol, device)
+        sums = _nh.ksd_sums_t(St, Gt, precision, wrap=flags.astype(np.uint8) if flags.any() else None, matrix=nboot > 0)
+        row = sums["row"].cpu().numpy()
+        u, vstat = ST.ksd_from_sums(row.sum(), sums["diag"].cpu().numpy().sum(), rows, ustat=rows >= 2)
+        out = dict(ustat=u, vstat=vstat, row_mean=row / rows, n=rows, sigma=sig,
+                   precision={v: precision[pcol[v]:pcol[v] + v.dim].copy() for v in order})
+        if nboot > 0:
+            rng = np.random.RandomState(seed)
+            draws = np.stack([rng.multinomial(rows, np.ones(rows) / rows) for _ in range(nboot)])
+            out["bootstrap"] = ST.ksd_bootstrap(sums["H"], draws)
+            out["p_value"] = float(np.mean(out["bootstrap"] >= u))
+        return out
+
     # ---- the solver graded against a reference sample set --------------------------------------------------------
     def posterior_mmd(self, reference, samples=None, n: int = None, variables=None, blocks=None, columns: str = "xy",
                       estimator: str = "mmd", sigma=None, standardise: bool = False, joint: bool = True) -> dict:

@@ -4,7 +4,8 @@ bandwidth sigma is what the reference's evaluation scripts report,
 example/slam/small_range_gaussian_problem/icra_paper/mmd_rmse_time_da_plot_grid.py:167,245), and the summaries of a
 sample set (reference: src/utils/Statistics.py:142-214): means with circular means for headings, covariances, resultant
 lengths and quantiles on the device, the modes of a multi-modal sample set (mean-shift on the device), `rmse`,
-`translation_distance` and `geodesic_distance` on the host."""
+`translation_distance` and `geodesic_distance` on the host; and the Gaussian kernel Stein discrepancy of a sample set
+against the density's own score (reference: src/utils/Statistics.py:193-245), its pairwise sums on the device."""
 import numpy as np
 
 
@@ -413,3 +414,138 @@ def geodesic_distance(var2point1, var2point2):
         else:
             err += sum((np.asarray(a) - np.asarray(b)) ** 2)
     return np.sqrt(err)
+
+
+# ---- kernel Stein discrepancy: samples graded against the factor graph itself (nfisam_sample_ksd) ---------------------------------
+def ksd_from_sums(row_sum: float, diag_sum: float, n: int, ustat: bool = True):
+    """(ustat, vstat) of the Stein sums: vstat = sum_ij h_ij / n^2 (all pairs), ustat = (sum_ij h_ij - sum_i h_ii) / (n (n - 1))
+    (reference src/utils/Statistics.py:237-238).  `row_sum` = sum of `row`, `diag_sum` = sum of `diag` of `nfisam_hip.ksd_sums`.
+    The U-statistic needs n >= 2 (ValueError); with ustat=False it is returned as None."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("the Stein sums need at least one point")
+    if ustat and n < 2:
+        raise ValueError("the U-statistic needs at least two points (n = %d)" % n)
+    v = float(row_sum) / (n * n)
+    u = (float(row_sum) - float(diag_sum)) / (n * (n - 1)) if ustat else None
+    return u, v
+
+
+def _diagonal_precision(kernel_precision, dim):
+    """A [D] vector or a DIAGONAL [D, D] matrix -> the [D] diagonal; any other dense matrix is refused."""
+    p = np.asarray(kernel_precision, dtype=np.float64)
+    if p.ndim == 2 and p.shape == (dim, dim):
+        if np.any(p != np.diag(np.diag(p))):
+            raise ValueError("kernel_precision is a dense matrix with off-diagonal entries: only a diagonal precision "
+                             "(a [D] vector or a diagonal [D, D] matrix) is supported")
+        p = np.diag(p).copy()
+    if p.shape != (dim,):
+        raise ValueError("kernel_precision must be a [%d] vector or a diagonal [%d, %d] matrix, got shape %s"
+                         % (dim, dim, dim, tuple(p.shape)))
+    if not np.all(np.isfinite(p)) or np.any(p < 0):
+        raise ValueError("kernel_precision must be finite and >= 0")
+    return p
+
+
+def ksd_bootstrap(H, draws) -> np.ndarray:
+    """The reference's bootstrap of the U-statistic (src/utils/Statistics.py:239-242): for every row c of the multinomial
+    counts `draws` [nboot, n], w = c / n and (w - 1/n)' off (w - 1/n) with `off` = H without its diagonal.  H: the [n, n]
+    float64 device matrix of `ksd_sums(matrix=True)`; one matrix product on its device.  -> [nboot] float64 numpy."""
+    import torch
+    n = int(H.shape[0])
+    draws = np.asarray(draws, dtype=np.float64)
+    if draws.ndim != 2 or draws.shape[1] != n:
+        raise ValueError("draws must be [nboot, %d] multinomial counts" % n)
+    W = torch.from_numpy(draws / n - 1.0 / n).to(H.device)
+    off = H - torch.diag(torch.diagonal(H))
+    return ((W @ off) * W).sum(1).cpu().numpy()
+
+
+def kernel_stein_discrepancy(x, score, sigma=None, scale=None, circular=None, nboot=0, rng=None, matrix=False, device=None):
+    """The Gaussian kernel Stein discrepancy of the points x [n, D] (numpy or torch; float32 points) with scores
+    score [n, D] = grad_x log p at them (float64; `nfisam_hip.factor_graph_score`, `NFiSAM.joint_score`), on the device
+    (nfisam_hip.ksd_sums: float64 arithmetic, direct differences) -- it grades the samples against the density itself and
+    needs no second sample set.
+
+    The kernel is exp(-1/2 sum_c p_c d_c^2) with the diagonal precision p_c = scale_c^2 / sigma^2; sigma=None means sqrt(D),
+    the default of `mmd_blocks`; scale=None means all ones (scale_c = 1 / spread of column c standardises the columns; 0
+    takes a column out of the kernel).  circular [D]: columns that are angles, compared by differences wrapped into
+    [-pi, pi].  For a circular column the kernel is continuous but not differentiable at the antipode, where its value is
+    exp(-1/2 p pi^2): negligible for concentrated headings.  The reference does not wrap: pass circular=None for its
+    behaviour.
+
+    -> dict: "ustat" (None for n = 1), "vstat", "row" [n] (row means sum_j h_ij / n: where the samples disagree with the
+    density), "precision" [D]; with matrix=True "H" [n, n] (numpy, n <= 4096); with nboot > 0 (n >= 2, n <= 4096):
+    "bootstrap" [nboot], the reference's multinomial bootstrap with draws from `rng` (numpy Generator or RandomState; default
+    np.random) on the host and the quadratic forms as one matrix product on the device, and "p_value", the share >= ustat."""
+    import nfisam_hip as _nh
+    if np.ndim(x) != 2 or np.ndim(score) != 2:
+        raise ValueError("x and score must be [points, columns]")
+    n, D = int(x.shape[0]), int(x.shape[1])
+    if tuple(score.shape) != (n, D):
+        raise ValueError("score must have the shape of x, %s, got %s" % ((n, D), tuple(score.shape)))
+    if n < 1 or D < 1:
+        raise ValueError("at least one point and one column are needed")
+    sig = float(np.sqrt(D)) if sigma is None else float(sigma)
+    if not np.isfinite(sig) or sig <= 0:
+        raise ValueError("sigma must be positive and finite")
+    sc = np.ones(D) if scale is None else np.asarray(scale, dtype=np.float64).reshape(-1)
+    if sc.size != D:
+        raise ValueError("scale: one value per column (%d), got %d" % (D, sc.size))
+    if not np.all(np.isfinite(sc)):
+        raise ValueError("scale must be finite")
+    wr = None
+    if circular is not None:
+        wr = np.asarray(circular, dtype=bool).reshape(-1)
+        if wr.size != D:
+            raise ValueError("circular: one flag per column (%d), got %d" % (D, wr.size))
+    nboot = int(nboot)
+    if nboot < 0:
+        raise ValueError("nboot must be >= 0")
+    if nboot > 0 and n < 2:
+        raise ValueError("the bootstrap of the U-statistic needs at least two points")
+    precision = sc * sc / (sig * sig)
+    want_h = bool(matrix) or nboot > 0
+    sums = _nh.ksd_sums(x, score, precision, wrap=wr, matrix=want_h, device=device)
+    row = sums["row"].cpu().numpy()
+    u, v = ksd_from_sums(row.sum(), sums["diag"].cpu().numpy().sum(), n, ustat=n >= 2)
+    out = dict(ustat=u, vstat=v, row=row / n, precision=precision)
+    if matrix:
+        out["H"] = sums["H"].cpu().numpy()
+    if nboot > 0:
+        draw = (rng if rng is not None else np.random).multinomial
+        draws = np.stack([draw(n, np.ones(n) / n) for _ in range(nboot)])
+        out["bootstrap"] = ksd_bootstrap(sums["H"], draws)
+        out["p_value"] = float(np.mean(out["bootstrap"] >= u))
+    return out
+
+
+def Gaussian_kernel_stein_discrepancy(joint_factor_or_score, kernel_precision, samples, nboot=10, rng=None, device=None):
+    """The reference's function of this name (src/utils/Statistics.py:216-245) -> (ustats, p_u, off_ksd, vstats), the pairwise
+    sums on the device.  The first argument is the [n, D] score matrix at `samples`, or any object with
+    `grad_x_log_pdf(samples)`; kernel_precision a [D] vector or a DIAGONAL [D, D] matrix (any other dense matrix raises
+    ValueError).  off_ksd [n, n] numpy: h_ij with a zero diagonal; p_u: the share of the `nboot` multinomial bootstrap values
+    (drawn from `rng`, default np.random like the reference) that are >= ustats.  Differences are not wrapped, as there.
+    Nothing is printed."""
+    import nfisam_hip as _nh
+    if np.ndim(samples) != 2:
+        raise ValueError("samples must be [points, columns]")
+    n, D = int(samples.shape[0]), int(samples.shape[1])
+    precision = _diagonal_precision(kernel_precision, D)
+    if n < 2:
+        raise ValueError("the U-statistic needs at least two points (n = %d)" % n)
+    nboot = int(nboot)
+    if nboot < 1:
+        raise ValueError("nboot must be >= 1")
+    score = joint_factor_or_score.grad_x_log_pdf(np.asarray(samples, dtype=np.float64)) \
+        if hasattr(joint_factor_or_score, "grad_x_log_pdf") else joint_factor_or_score
+    if np.ndim(score) != 2 or tuple(score.shape) != (n, D):
+        raise ValueError("the score must have the shape of samples, %s" % ((n, D),))
+    sums = _nh.ksd_sums(samples, score, precision, matrix=True, device=device)
+    ustats, vstats = ksd_from_sums(sums["row"].cpu().numpy().sum(), sums["diag"].cpu().numpy().sum(), n)
+    draw = (rng if rng is not None else np.random).multinomial
+    draws = np.stack([draw(n, np.ones(n) / n) for _ in range(nboot)])
+    boot = ksd_bootstrap(sums["H"], draws)
+    off = sums["H"].cpu().numpy()
+    np.fill_diagonal(off, 0.0)
+    return ustats, float(np.mean(boot >= ustats)), off, vstats
