@@ -5,9 +5,8 @@
 // device table (nfisam_factor_term) and the points are the column-major float32 sample matrix St[total_dim][n] that the
 // tree walk writes: a posterior draw is scored where it lies.
 //
-// Numerics: float32 points in, float64 arithmetic, float64 out -- the value of the float64 formula at the float32 point.
-// The bundled graphs pin the first pose with heading variances down to 1e-12 and their joint values reach 1e4..1e11: every
-// residual, quadratic form, log-sum-exp and both sums are double; parameters travel as doubles.
+// Numerics: the contract of sample_common.h.  The bundled graphs pin the first pose with heading variances down to 1e-12 and
+// their joint values reach 1e4..1e11: every residual, quadratic form, log-sum-exp and both sums are double, like the parameters.
 //
 // Two launches.  (1) a wave owns a 64-point tile and a contiguous run of FAC_RUN factors: the factor index depends on the
 // block index alone, so the code and every parameter are wave-uniform (scalar loads, no divergence inside the wave), each
@@ -15,75 +14,32 @@
 // per_factor[f][p].  (2) per 64-point tile the terms are added strictly in table order (see factor_sum_kernel):
 // log_p[p] is the left-to-right float64 sum of per_factor[0..n_terms)[p], whatever n and whichever tile p falls in.  No
 // float atomics: two calls give the same bits.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "../../include/nfisam_hip.h"
-#include "sample_common.h"
+#include "factor_model.h"
 
 namespace {
 
-using namespace sample_common;
+using namespace factor_model;
 
-constexpr int FAC_RUN = 8;        // factors per wave in the first pass
 constexpr int SUM_WAVES = 16;     // second pass: waves per 64-point tile ...
 constexpr int SUM_ROWS = 8;       // ... and rows each of them has in flight per stage (16 x 8 x 64 doubles = 64 KB of LDS)
 
-// log N(Log(dT); 0, Sigma) + log|det dLog| for dT = (tx, ty, w); p[3..8] = upper triangle of the precision, p[9] = log normaliser.
-// Log: v = V^-1(w) t with V^-1 = [[a, w/2], [-w/2, a]], a = (w/2) cot(w/2) (the half-angle form of
-// geometry/TwoDimension.py:405-418; identity for |w| < 1e-10); det dLog = w^2 / (4 sin^2(w/2)), 1 for |w| < 1e-5 (:437-441).
-__device__ __forceinline__ double se2_tangent_log_pdf(double tx, double ty, double w, const double* __restrict__ p) {
-    const double h = 0.5 * w;
-    double sh, ch;
-    sincos(h, &sh, &ch);
-    const bool small = fabs(w) < 1e-10;
-    const double a = small ? 1.0 : h * ch / sh;
-    const double b = small ? 0.0 : h;
-    const double vx = a * tx + b * ty, vy = a * ty - b * tx;
-    const double q = p[3] * vx * vx + p[6] * vy * vy + p[8] * w * w + 2.0 * (p[4] * vx * vy + p[5] * vx * w + p[7] * vy * w);
-    const double log_det = (fabs(w) < 1e-5) ? 0.0 : 2.0 * log(fabs(h / sh));
-    return p[9] - 0.5 * q + log_det;
-}
-
-__device__ __forceinline__ double range_log_pdf(double ax, double ay, double bx, double by, double d, double inv_var,
-                                                double log_norm) {
-    const double dx = ax - bx, dy = ay - by;
-    const double delta = sqrt(dx * dx + dy * dy) - d;
-    return log_norm - 0.5 * delta * delta * inv_var;
-}
-
 // one factor at one point; `t` is wave-uniform.  pp = the point's column of St (clamped: lanes past n compute and drop).
-// Rows are checked against total_dim here as well (wave-uniform, scalar): a bad table yields NaN, never a stray read.
+// The guard comes first (wave-uniform, scalar): a bad table yields NaN, never a stray read.
 __device__ __forceinline__ double factor_term(const nfisam_factor_term* __restrict__ t, const float* __restrict__ St, size_t n,
                                               size_t pp, int total_dim) {
-    const int code = t->code;
+    if (!record_ok(t, total_dim)) return NAN;
     const double* __restrict__ p = t->p;
-    const bool pose_a = code == NFISAM_FAC_PRIOR_SE2 || code == NFISAM_FAC_REL_SE2;
-    const bool has_b = code == NFISAM_FAC_REL_SE2 || code == NFISAM_FAC_RANGE || code == NFISAM_FAC_REL_R2;
-    if (code < NFISAM_FAC_PRIOR_SE2 || code > NFISAM_FAC_REL_R2) return NAN;      // an unknown code
-    if (t->a < 0 || t->a + (pose_a ? 3 : 2) > total_dim) return NAN;
-    if (has_b && (t->b < 0 || t->b + (code == NFISAM_FAC_REL_SE2 ? 3 : 2) > total_dim)) return NAN;
     const float* __restrict__ A = St + (size_t)t->a * n + pp;
     const double ax = (double)A[0], ay = (double)A[n];
-    switch (code) {
+    switch (t->code) {
     case NFISAM_FAC_PRIOR_SE2: {
-        double s, c;
-        sincos(p[2], &s, &c);
-        const double dx = ax - p[0], dy = ay - p[1];
-        const double w = wrap_pi(wrap_pi(-p[2]) + wrap_pi((double)A[2 * n]));
-        return se2_tangent_log_pdf(c * dx + s * dy, c * dy - s * dx, w, p);
+        const Se2Prior r = se2_prior_residual(ax, ay, (double)A[2 * n], p);
+        return se2_tangent_log_pdf(r.tx, r.ty, r.w, p);
     }
     case NFISAM_FAC_REL_SE2: {
         const float* __restrict__ Bv = St + (size_t)t->b * n + pp;
-        const double thi = (double)A[2 * n], thj = (double)Bv[2 * n];
-        double si, ci, so, co;
-        sincos(thi, &si, &ci);
-        sincos(p[2], &so, &co);
-        const double dx = (double)Bv[0] - ax, dy = (double)Bv[n] - ay;
-        const double rx = ci * dx + si * dy - p[0], ry = ci * dy - si * dx - p[1];
-        const double w = wrap_pi(wrap_pi(-p[2]) + wrap_pi(wrap_pi(-wrap_pi(thi)) + wrap_pi(thj)));
-        return se2_tangent_log_pdf(co * rx + so * ry, co * ry - so * rx, w, p);
+        const Se2Relative r = se2_relative_residual(ax, ay, (double)A[2 * n], (double)Bv[0], (double)Bv[n], (double)Bv[2 * n], p);
+        return se2_tangent_log_pdf(r.m.tx, r.m.ty, r.m.w, p);
     }
     case NFISAM_FAC_RANGE: {
         const float* __restrict__ Bv = St + (size_t)t->b * n + pp;
@@ -91,11 +47,7 @@ __device__ __forceinline__ double factor_term(const nfisam_factor_term* __restri
     }
     case NFISAM_FAC_RANGE_MIX: {
         const int k = t->k;
-        if (k < 1 || k > 4) return NAN;
-        for (int j = 0; j < k; ++j)
-            if (t->cand[j] < 0 || t->cand[j] + 2 > total_dim) return NAN;
-        double term[4];
-        double top = -INFINITY;
+        double term[4], top = -INFINITY;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (j < k) {
@@ -110,20 +62,16 @@ __device__ __forceinline__ double factor_term(const nfisam_factor_term* __restri
             if (j < k) acc += exp(term[j] - top);
         return top + log(acc);
     }
-    case NFISAM_FAC_PRIOR_R2: {
-        const double dx = ax - p[0], dy = ay - p[1];
-        return p[5] - 0.5 * (p[2] * dx * dx + p[4] * dy * dy + 2.0 * p[3] * dx * dy);
-    }
+    case NFISAM_FAC_PRIOR_R2:
+        return r2_log_pdf(ax - p[0], ay - p[1], p);
     case NFISAM_FAC_PRIOR_R2_RANGE:
         return range_log_pdf(ax, ay, p[0], p[1], p[2], p[3], p[4]);
     case NFISAM_FAC_REL_R2: {
         const float* __restrict__ Bv = St + (size_t)t->b * n + pp;
-        const double dx = (double)Bv[0] - ax - p[0], dy = (double)Bv[n] - ay - p[1];
-        return p[5] - 0.5 * (p[2] * dx * dx + p[4] * dy * dy + 2.0 * p[3] * dx * dy);
+        return r2_log_pdf((double)Bv[0] - ax - p[0], (double)Bv[n] - ay - p[1], p);
     }
-    default:
-        return NAN;
     }
+    return NAN;
 }
 
 // grid (tiles of 64 points, runs of FAC_RUN factors), one wave per block
@@ -132,9 +80,8 @@ __global__ void __launch_bounds__(64) factor_terms_kernel(const nfisam_factor_te
                                                           double* __restrict__ per) {
     const int p = blockIdx.x * 64 + threadIdx.x;
     const size_t pp = (p < n) ? (size_t)p : (size_t)(n - 1);
-    const int f0 = blockIdx.y * FAC_RUN;
-    const int f1 = min(f0 + FAC_RUN, n_terms);
-    for (int f = f0; f < f1; ++f) {
+    const int f1 = min((int)(blockIdx.y + 1) * FAC_RUN, n_terms);
+    for (int f = blockIdx.y * FAC_RUN; f < f1; ++f) {
         const double v = factor_term(terms + f, St, (size_t)n, pp, total_dim);
         if (p < n) per[(size_t)f * n + p] = v;
     }
@@ -190,7 +137,7 @@ __global__ void __launch_bounds__(64 * SUM_WAVES) factor_sum_kernel(const double
 extern "C" int nfisam_factor_graph_log_density(const nfisam_factor_term* terms, int n_terms, const float* St, int total_dim,
                                                int n, double* log_p, double* per_factor, nfisam_stream_t stream) {
     if (terms == nullptr || St == nullptr || log_p == nullptr || n_terms < 0 || n < 0 || total_dim < 1) return NFISAM_ERR_ARG;
-    if ((n_terms + FAC_RUN - 1) / FAC_RUN > 65535) return NFISAM_ERR_ARG;       // the grid's second dimension
+    if (fac_runs(n_terms) > GRID_Y_MAX) return NFISAM_ERR_ARG;
     if (n == 0) return NFISAM_OK;
     hipStream_t s = (hipStream_t)stream;
     hipError_t e;
@@ -202,8 +149,7 @@ extern "C" int nfisam_factor_graph_log_density(const nfisam_factor_term* terms, 
         if (e != hipSuccess) return launch_status(e);
     }
     const int tiles = (n + 63) / 64;
-    hipLaunchKernelGGL(factor_terms_kernel, dim3(tiles, (n_terms + FAC_RUN - 1) / FAC_RUN), dim3(64), 0, s, terms, n_terms, St,
-                       total_dim, n, per);
+    hipLaunchKernelGGL(factor_terms_kernel, dim3(tiles, fac_runs(n_terms)), dim3(64), 0, s, terms, n_terms, St, total_dim, n, per);
     e = hipGetLastError();
     if (e == hipSuccess) {
         hipLaunchKernelGGL(factor_sum_kernel, dim3(tiles), dim3(64 * SUM_WAVES), 0, s, per, n_terms, n, log_p);

@@ -6,151 +6,64 @@
 // factors are the table of factor_density.hip (nfisam_factor_term, the same seven codes) and the points are the column-major
 // float32 matrix St[total_dim][n]; the result is the float64 column-major matrix Gt[total_dim][n].
 //
-// Numerics: the contract of sample_common.h -- float32 points in, every operation float64: the derivative of the float64
-// formula that factor_term() of factor_density.hip evaluates, at the float32 point.  It is the derivative of the SMOOTH
-// formula everywhere: the value's own branches (|w| < 1e-10 in the log map, |w| < 1e-5 in its Jacobian) are flat spots of
-// 1e-10 and get no derivative-zero plateaus.  A range of exactly 0 has no direction: its derivative is the zero vector.  A
-// mixture's derivative is sum_j r_j grad term_j with r the softmax of the component terms, shifted by their maximum like the
-// value's log-sum-exp: finite wherever the terms are.
+// Numerics: the contract of sample_common.h.  Value and score are written from the same residuals and terms (factor_model.h):
+// this is the derivative of the float64 formula that factor_term() of factor_density.hip evaluates, at the float32 point -- of
+// the SMOOTH formula everywhere: the value's own branches (|w| < 1e-10 in the log map, |w| < 1e-5 in its Jacobian) are flat
+// spots of 1e-10 and get no derivative-zero plateaus.  A mixture's derivative is sum_j r_j grad term_j with r the softmax of
+// the component terms, shifted by their maximum like the value's log-sum-exp: finite wherever the terms are.
 //
 // Two launches, no float atomics.  (1) like factor_terms_kernel: a wave owns a 64-point tile and a run of FAC_RUN factors,
-// code and parameters wave-uniform; factor f writes its partial derivatives into its own slots slot_off[f] .. of the scratch
-// [n_slots][n] (3 / 6 / 4 / 2 + 2k / 2 / 2 / 4 slots by code, in the order of the factor's rows: a, then b or the candidates).
-// (2) a wave per (64-point tile, row r of G) adds the slots row_slot[row_off[r] .. row_off[r + 1]) in that order -- the host
-// lists a row's slots in table order -- one accumulator per point.  A row without a slot is 0.  Hence: two calls give the same
-// bits, and a point's column does not depend on n or on its tile.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "../../include/nfisam_hip.h"
-#include "sample_common.h"
+// code and parameters wave-uniform; factor f writes its slot_count() partial derivatives into its own slots slot_off[f] .. of
+// the scratch [n_slots][n], in the order of the factor's rows: a, then b or the candidates.  (2) a wave per (64-point tile,
+// row r of G) adds the slots row_slot[row_off[r] .. row_off[r + 1]) in that order -- the host lists a row's slots in table
+// order -- one accumulator per point.  A row without a slot is 0.  Hence: two calls give the same bits, and a point's column
+// does not depend on n or on its tile.
+#include "factor_model.h"
 
 namespace {
 
-using namespace sample_common;
+using namespace factor_model;
 
-constexpr int FAC_RUN = 8;        // factors per wave in the first pass
 constexpr int MAX_SLOTS = 10;     // a mixture of four: 2 + 2 * 4
 constexpr int ADD_ROWS = 8;       // second pass: loads in flight per point
 
-// a(h) = h cot h, its derivative in w = 2h, a'(w) = (cot h - h / sin^2 h) / 2, and the derivative of the log-det term
-// 2 log|h / sin h| in w, l'(w) = 1 / h - cot h.  Both derivatives are differences of two terms of size 1 / h that leave
-// 2h / 3 resp. h / 3: the plain forms lose 1.5 eps / h^2 relative (six digits left at h = 1e-5).  Below SERIES_H the Taylor
-// series in h, through h^9, are used instead (coefficients: 2^2k |B_2k| / (2k)!).  The threshold balances the two errors:
-// at h = 0.1 the plain forms have lost 1.5 eps / h^2 = 1.7e-14 (two digits) and the first dropped terms, 1.3e-5 h^11 and
-// 2.2e-6 h^11 against h / 3, are 3.9e-15 and 6.5e-16 relative -- neither side of the switch is more than about two digits
-// worse than the other, and further from the switch each side only improves.
-constexpr double SERIES_H = 0.1;
-
-__device__ __forceinline__ void log_map_terms(double w, double* a, double* da_dw, double* dlogdet_dw) {
-    const double h = 0.5 * w;
-    if (fabs(h) < SERIES_H) {
-        const double h2 = h * h;
-        *a = 1.0 - h2 * (1.0 / 3.0 + h2 * (1.0 / 45.0 + h2 * (2.0 / 945.0 + h2 * (1.0 / 4725.0 + h2 * (2.0 / 93555.0)))));
-        *da_dw = -h * (1.0 / 3.0 + h2 * (2.0 / 45.0 + h2 * (2.0 / 315.0 + h2 * (4.0 / 4725.0 + h2 * (2.0 / 18711.0)))));
-        *dlogdet_dw = h * (1.0 / 3.0 + h2 * (1.0 / 45.0 + h2 * (2.0 / 945.0 + h2 * (1.0 / 4725.0 + h2 * (2.0 / 93555.0)))));
-    } else {
-        double sh, ch;
-        sincos(h, &sh, &ch);
-        const double cot = ch / sh;
-        *a = h * cot;
-        *da_dw = 0.5 * (cot - h / (sh * sh));
-        *dlogdet_dw = 1.0 / h - cot;
-    }
-}
-
-// d/d(tx, ty, w) of se2_tangent_log_pdf (factor_density.hip): v = (a tx + h ty, a ty - h tx, w), L = c - v'Pv / 2 + logdet(w)
-__device__ __forceinline__ void se2_tangent_score(double tx, double ty, double w, const double* __restrict__ p, double* gtx,
-                                                  double* gty, double* gw) {
-    double a, da, dl;
-    log_map_terms(w, &a, &da, &dl);
-    const double h = 0.5 * w;
-    const double vx = a * tx + h * ty, vy = a * ty - h * tx;
-    const double gvx = -(p[3] * vx + p[4] * vy + p[5] * w);
-    const double gvy = -(p[4] * vx + p[6] * vy + p[7] * w);
-    const double gvw = -(p[5] * vx + p[7] * vy + p[8] * w);
-    *gtx = a * gvx - h * gvy;
-    *gty = h * gvx + a * gvy;
-    *gw = gvw + gvx * (da * tx + 0.5 * ty) + gvy * (da * ty - 0.5 * tx) + dl;
-}
-
-// d/da of the range term -(|a - b| - d)^2 inv_var / 2 (d/db is its negative); the zero vector at |a - b| = 0
-__device__ __forceinline__ void range_score(double ax, double ay, double bx, double by, double d, double inv_var, double* gx,
-                                            double* gy) {
-    const double dx = ax - bx, dy = ay - by;
-    const double r = sqrt(dx * dx + dy * dy);
-    const double c = (r > 0.0) ? -(r - d) * inv_var / r : 0.0;
-    *gx = c * dx, *gy = c * dy;
-}
-
-__device__ __forceinline__ int slot_count(int code, int k) {
-    switch (code) {
-    case NFISAM_FAC_PRIOR_SE2: return 3;
-    case NFISAM_FAC_REL_SE2: return 6;
-    case NFISAM_FAC_RANGE: return 4;
-    case NFISAM_FAC_RANGE_MIX: return (k >= 1 && k <= 4) ? 2 + 2 * k : 0;
-    case NFISAM_FAC_PRIOR_R2: return 2;
-    case NFISAM_FAC_PRIOR_R2_RANGE: return 2;
-    case NFISAM_FAC_REL_R2: return 4;
-    default: return 0;
-    }
-}
-
 // one factor at one point: g[0 .. slot_count) in the order of its rows (a's, then b's or the candidates'); `t` is wave-uniform.
-// The row checks are those of factor_term(): a bad record yields NaN in every slot and reads nothing.
+// The guard comes first, as in factor_term(): a bad record yields NaN in every slot and reads nothing.
 __device__ __forceinline__ void factor_score(const nfisam_factor_term* __restrict__ t, const float* __restrict__ St, size_t n,
                                              size_t pp, int total_dim, double (&g)[MAX_SLOTS]) {
-    const int code = t->code;
-    const double* __restrict__ p = t->p;
 #pragma unroll
     for (int s = 0; s < MAX_SLOTS; ++s) g[s] = NAN;
-    const bool pose_a = code == NFISAM_FAC_PRIOR_SE2 || code == NFISAM_FAC_REL_SE2;
-    const bool has_b = code == NFISAM_FAC_REL_SE2 || code == NFISAM_FAC_RANGE || code == NFISAM_FAC_REL_R2;
-    if (code < NFISAM_FAC_PRIOR_SE2 || code > NFISAM_FAC_REL_R2) return;
-    if (t->a < 0 || t->a + (pose_a ? 3 : 2) > total_dim) return;
-    if (has_b && (t->b < 0 || t->b + (code == NFISAM_FAC_REL_SE2 ? 3 : 2) > total_dim)) return;
+    if (!record_ok(t, total_dim)) return;
+    const double* __restrict__ p = t->p;
     const float* __restrict__ A = St + (size_t)t->a * n + pp;
     const double ax = (double)A[0], ay = (double)A[n];
-    switch (code) {
+    switch (t->code) {
     case NFISAM_FAC_PRIOR_SE2: {
-        double s, c, gtx, gty, gw;
-        sincos(p[2], &s, &c);
-        const double dx = ax - p[0], dy = ay - p[1];
-        const double w = wrap_pi(wrap_pi(-p[2]) + wrap_pi((double)A[2 * n]));
-        se2_tangent_score(c * dx + s * dy, c * dy - s * dx, w, p, &gtx, &gty, &gw);
-        g[0] = c * gtx - s * gty, g[1] = s * gtx + c * gty, g[2] = gw;
+        const Se2Prior r = se2_prior_residual(ax, ay, (double)A[2 * n], p);
+        double gtx, gty, gw;
+        se2_tangent_score(r.tx, r.ty, r.w, p, &gtx, &gty, &gw);
+        g[0] = r.c * gtx - r.s * gty, g[1] = r.s * gtx + r.c * gty, g[2] = gw;
         return;
     }
     case NFISAM_FAC_REL_SE2: {
         const float* __restrict__ Bv = St + (size_t)t->b * n + pp;
-        const double thi = (double)A[2 * n], thj = (double)Bv[2 * n];
-        double si, ci, so, co, gtx, gty, gw;
-        sincos(thi, &si, &ci);
-        sincos(p[2], &so, &co);
-        const double dx = (double)Bv[0] - ax, dy = (double)Bv[n] - ay;
-        const double ux = ci * dx + si * dy, uy = ci * dy - si * dx;          // the difference in pose i's frame
-        const double rx = ux - p[0], ry = uy - p[1];
-        const double w = wrap_pi(wrap_pi(-p[2]) + wrap_pi(wrap_pi(-wrap_pi(thi)) + wrap_pi(thj)));
-        se2_tangent_score(co * rx + so * ry, co * ry - so * rx, w, p, &gtx, &gty, &gw);
-        const double grx = co * gtx - so * gty, gry = so * gtx + co * gty;
-        const double gx = ci * grx - si * gry, gy = si * grx + ci * gry;      // d/d(x_j, y_j)
-        g[0] = -gx, g[1] = -gy, g[2] = grx * uy - gry * ux - gw;            // d ux / d th_i = uy, d uy / d th_i = -ux
+        const Se2Relative r = se2_relative_residual(ax, ay, (double)A[2 * n], (double)Bv[0], (double)Bv[n], (double)Bv[2 * n], p);
+        double gtx, gty, gw;
+        se2_tangent_score(r.m.tx, r.m.ty, r.m.w, p, &gtx, &gty, &gw);
+        const double grx = r.m.c * gtx - r.m.s * gty, gry = r.m.s * gtx + r.m.c * gty;
+        const double gx = r.ci * grx - r.si * gry, gy = r.si * grx + r.ci * gry;      // d/d(x_j, y_j)
+        g[0] = -gx, g[1] = -gy, g[2] = grx * r.uy - gry * r.ux - gw;        // d ux / d th_i = uy, d uy / d th_i = -ux
         g[3] = gx, g[4] = gy, g[5] = gw;
         return;
     }
     case NFISAM_FAC_RANGE: {
         const float* __restrict__ Bv = St + (size_t)t->b * n + pp;
-        double gx, gy;
-        range_score(ax, ay, (double)Bv[0], (double)Bv[n], p[0], p[1], &gx, &gy);
-        g[0] = gx, g[1] = gy, g[2] = -gx, g[3] = -gy;
+        range_score(ax, ay, (double)Bv[0], (double)Bv[n], p[0], p[1], &g[0], &g[1]);
+        g[2] = -g[0], g[3] = -g[1];
         return;
     }
     case NFISAM_FAC_RANGE_MIX: {
         const int k = t->k;
-        if (k < 1 || k > 4) return;
-        for (int j = 0; j < k; ++j)
-            if (t->cand[j] < 0 || t->cand[j] + 2 > total_dim) return;
         double term[4], gx[4], gy[4];
         double top = -INFINITY;
 #pragma unroll
@@ -159,9 +72,7 @@ __device__ __forceinline__ void factor_score(const nfisam_factor_term* __restric
             if (j < k) {
                 const float* __restrict__ Cv = St + (size_t)t->cand[j] * n + pp;
                 const double cx = (double)Cv[0], cy = (double)Cv[n];
-                const double ddx = ax - cx, ddy = ay - cy;
-                const double delta = sqrt(ddx * ddx + ddy * ddy) - p[3 * j];
-                term[j] = p[3 * j + 2] - 0.5 * delta * delta * p[3 * j + 1];           // range_log_pdf of factor_density.hip
+                term[j] = range_log_pdf(ax, ay, cx, cy, p[3 * j], p[3 * j + 1], p[3 * j + 2]);
                 range_score(ax, ay, cx, cy, p[3 * j], p[3 * j + 1], &gx[j], &gy[j]);
                 top = fmax(top, term[j]);
             }
@@ -184,26 +95,18 @@ __device__ __forceinline__ void factor_score(const nfisam_factor_term* __restric
         g[0] = sx, g[1] = sy;
         return;
     }
-    case NFISAM_FAC_PRIOR_R2: {
-        const double dx = ax - p[0], dy = ay - p[1];
-        g[0] = -(p[2] * dx + p[3] * dy), g[1] = -(p[3] * dx + p[4] * dy);
+    case NFISAM_FAC_PRIOR_R2:
+        r2_score(ax - p[0], ay - p[1], p, &g[0], &g[1]);
         return;
-    }
-    case NFISAM_FAC_PRIOR_R2_RANGE: {
-        double gx, gy;
-        range_score(ax, ay, p[0], p[1], p[2], p[3], &gx, &gy);
-        g[0] = gx, g[1] = gy;
+    case NFISAM_FAC_PRIOR_R2_RANGE:
+        range_score(ax, ay, p[0], p[1], p[2], p[3], &g[0], &g[1]);
         return;
-    }
     case NFISAM_FAC_REL_R2: {
         const float* __restrict__ Bv = St + (size_t)t->b * n + pp;
-        const double dx = (double)Bv[0] - ax - p[0], dy = (double)Bv[n] - ay - p[1];
-        const double gx = -(p[2] * dx + p[3] * dy), gy = -(p[3] * dx + p[4] * dy);   // d/db
-        g[0] = -gx, g[1] = -gy, g[2] = gx, g[3] = gy;
+        r2_score((double)Bv[0] - ax - p[0], (double)Bv[n] - ay - p[1], p, &g[2], &g[3]);         // d/db
+        g[0] = -g[2], g[1] = -g[3];
         return;
     }
-    default:
-        return;
     }
 }
 
@@ -214,9 +117,8 @@ __global__ void __launch_bounds__(64) factor_score_kernel(const nfisam_factor_te
                                                           double* __restrict__ slots) {
     const int p = blockIdx.x * 64 + threadIdx.x;
     const size_t pp = (p < n) ? (size_t)p : (size_t)(n - 1);
-    const int f0 = blockIdx.y * FAC_RUN;
-    const int f1 = min(f0 + FAC_RUN, n_terms);
-    for (int f = f0; f < f1; ++f) {
+    const int f1 = min((int)(blockIdx.y + 1) * FAC_RUN, n_terms);
+    for (int f = blockIdx.y * FAC_RUN; f < f1; ++f) {
         double g[MAX_SLOTS];
         factor_score(terms + f, St, (size_t)n, pp, total_dim, g);
         const int cnt = slot_count(terms[f].code, terms[f].k);
@@ -276,15 +178,15 @@ extern "C" int nfisam_factor_graph_score(const nfisam_factor_term* terms, int n_
     if (St == nullptr || Gt == nullptr || n_terms < 0 || n < 0 || total_dim < 1 || n_slots < 0) return NFISAM_ERR_ARG;
     if (n_terms > 0 && (terms == nullptr || slot_off == nullptr || row_off == nullptr || row_slot == nullptr || scratch == nullptr))
         return NFISAM_ERR_ARG;
-    if ((n_terms + FAC_RUN - 1) / FAC_RUN > 65535 || total_dim > 65535) return NFISAM_ERR_ARG;   // the grids' second dimension
+    if (fac_runs(n_terms) > GRID_Y_MAX || total_dim > GRID_Y_MAX) return NFISAM_ERR_ARG;
     if ((long long)n_slots > (long long)MAX_SLOTS * n_terms) return NFISAM_ERR_ARG;
     if (n == 0) return NFISAM_OK;
     hipStream_t s = (hipStream_t)stream;
     if (n_terms == 0)                                                  // the empty graph: a zero score
         return launch_status(hipMemsetAsync(Gt, 0, (size_t)total_dim * n * sizeof(double), s));
     const int tiles = (n + 63) / 64;
-    hipLaunchKernelGGL(factor_score_kernel, dim3(tiles, (n_terms + FAC_RUN - 1) / FAC_RUN), dim3(64), 0, s, terms, n_terms, St,
-                       total_dim, n, slot_off, n_slots, scratch);
+    hipLaunchKernelGGL(factor_score_kernel, dim3(tiles, fac_runs(n_terms)), dim3(64), 0, s, terms, n_terms, St, total_dim, n,
+                       slot_off, n_slots, scratch);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) {
         hipLaunchKernelGGL(score_gather_kernel, dim3(tiles, total_dim), dim3(64), 0, s, scratch, n_slots, n, row_off, row_slot, Gt);

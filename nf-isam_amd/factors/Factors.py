@@ -57,6 +57,9 @@ class Factor(object):
     def is_gaussian(self) -> bool:
         return False
 
+    def pdf(self, x: np.ndarray) -> np.ndarray:
+        return np.exp(self.log_pdf(x))
+
     def __str__(self) -> str:
         return "Factor " + self.__class__.__name__ + " " + " ".join(str(v.name) for v in self.vars)
 
@@ -170,7 +173,7 @@ def _log_map_terms(w):
     1 / h - cot h.  The two derivatives are differences of terms of size 1 / h that leave h / 3: the plain forms lose
     1.5 eps / h^2 relative.  Below |h| = 0.1 the Taylor series through h^9 replace them: there the plain forms have lost
     two digits (1.7e-14) and the first dropped series terms are 3.9e-15 and 6.5e-16 relative, so neither side of the switch
-    is more than about two digits worse than the other (the same switch as csrc/factor_score.hip)."""
+    is more than about two digits worse than the other (the same switch as csrc/factor_model.h)."""
     h = 0.5 * np.asarray(w, dtype=np.float64)
     ser = np.abs(h) < _SERIES_H
     h2 = np.where(ser, h * h, 0.0)
@@ -198,11 +201,14 @@ def _se2_tangent_score(tx, ty, w, precision):
             gvw + gvx * (da * tx + 0.5 * ty) + gvy * (da * ty - 0.5 * tx) + dl)
 
 
-def _range_score(ta, tb, d, sigma):
+def _range_log_pdf(r, d, sigma):
+    delta = r - d
+    return _gaussian_log_norm(sigma ** 2) - 0.5 * delta * delta * (1.0 / sigma ** 2)
+
+
+def _range_score(diff, r, d, sigma):
     """d/d(ta) of log N(|ta - tb| - d; 0, sigma^2) (d/d(tb) is its negative): -(r - d) / sigma^2 (ta - tb) / r, and the
     zero vector at r = 0 exactly, where the range has no direction."""
-    diff = ta - tb
-    r = np.sqrt((diff ** 2).sum(1))
     c = np.zeros_like(r)
     ok = r > 0
     c[ok] = -(r[ok] - d) / (sigma ** 2 * r[ok])
@@ -267,28 +273,26 @@ class UnarySE2ApproximateGaussianPriorFactor(ExplicitPriorFactor, UnaryFactor):
         out[:, 2] = (self._prior_pose.theta + theta + np.pi) % (2 * np.pi) - np.pi
         return out
 
+    def _residual(self, x):
+        """-> (tx, ty, w) = prior^-1 * T, and (cos, sin) of the prior's heading: the rotation a gradient goes back through."""
+        x = _as_points(x, 3)
+        px, py, pth = self._prior_pose.array
+        c, s = np.cos(pth), np.sin(pth)
+        dx, dy = x[:, 0] - px, x[:, 1] - py
+        w = wrap_pi(wrap_pi(-pth) + wrap_pi(x[:, 2]))
+        return c * dx + s * dy, -s * dx + c * dy, w, c, s
+
     def log_pdf(self, x: np.ndarray) -> np.ndarray:
         """Density in (x, y, theta) of the pose: the tangent Gaussian of prior^-1 * T times the Jacobian of Log
         (reference :823-827)."""
-        x = _as_points(x, 3)
-        px, py, pth = self._prior_pose.array
-        c, s = np.cos(pth), np.sin(pth)
-        dx, dy = x[:, 0] - px, x[:, 1] - py
-        w = wrap_pi(wrap_pi(-pth) + wrap_pi(x[:, 2]))
-        return _se2_tangent_log_pdf(c * dx + s * dy, -s * dx + c * dy, w, self._precision, self._log_norm)
+        tx, ty, w, c, s = self._residual(x)
+        return _se2_tangent_log_pdf(tx, ty, w, self._precision, self._log_norm)
 
     def grad_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
         """d log_pdf / d(x, y, theta), [n, 3] float64 (reference :829-850); the heading wrap has derivative 1."""
-        x = _as_points(x, 3)
-        px, py, pth = self._prior_pose.array
-        c, s = np.cos(pth), np.sin(pth)
-        dx, dy = x[:, 0] - px, x[:, 1] - py
-        w = wrap_pi(wrap_pi(-pth) + wrap_pi(x[:, 2]))
-        gtx, gty, gw = _se2_tangent_score(c * dx + s * dy, -s * dx + c * dy, w, self._precision)
+        tx, ty, w, c, s = self._residual(x)
+        gtx, gty, gw = _se2_tangent_score(tx, ty, w, self._precision)
         return np.stack([c * gtx - s * gty, s * gtx + c * gty, gw], 1)
-
-    def pdf(self, x: np.ndarray) -> np.ndarray:
-        return np.exp(self.log_pdf(x))
 
     def density_record(self) -> dict:
         return dict(code="PRIOR_SE2", a=self.var, b=None, cand=[],
@@ -382,35 +386,32 @@ class SE2RelativeGaussianLikelihoodFactor(LikelihoodFactor, BinaryFactor, OdomFa
             raise ValueError("Dimensionality of variable 1 or variable 2 is wrong")
         return self._noisy_relative(se2_compose(se2_inverse(var1), var2), var1.shape[0])
 
-    def log_pdf(self, x: np.ndarray) -> np.ndarray:
-        """Density of x = [T_i | T_j]: the tangent Gaussian of observation^-1 * (T_i^-1 * T_j) times the Jacobian of Log
-        (reference :1443-1448)."""
+    def _residual(self, x):
+        """-> (tx, ty, w) = observation^-1 * (T_i^-1 * T_j), then what a gradient goes back through: (cos, sin) of the
+        observation's heading and of pose i's, and (ux, uy), the difference of the positions in pose i's frame."""
         x = _as_points(x, 6)
         ox, oy, oth = self.observation
         ci, si = np.cos(x[:, 2]), np.sin(x[:, 2])
         dx, dy = x[:, 3] - x[:, 0], x[:, 4] - x[:, 1]
-        rx, ry = ci * dx + si * dy - ox, -si * dx + ci * dy - oy
-        co, so = np.cos(oth), np.sin(oth)
-        w = wrap_pi(wrap_pi(-oth) + wrap_pi(wrap_pi(-wrap_pi(x[:, 2])) + wrap_pi(x[:, 5])))
-        return _se2_tangent_log_pdf(co * rx + so * ry, -so * rx + co * ry, w, self._precision, self._log_norm)
-
-    def grad_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
-        """d log_pdf / d[T_i | T_j], [n, 6] float64 (reference :1450-1478)."""
-        x = _as_points(x, 6)
-        ox, oy, oth = self.observation
-        ci, si = np.cos(x[:, 2]), np.sin(x[:, 2])
-        dx, dy = x[:, 3] - x[:, 0], x[:, 4] - x[:, 1]
-        ux, uy = ci * dx + si * dy, -si * dx + ci * dy              # the difference in pose i's frame
+        ux, uy = ci * dx + si * dy, -si * dx + ci * dy
         rx, ry = ux - ox, uy - oy
         co, so = np.cos(oth), np.sin(oth)
         w = wrap_pi(wrap_pi(-oth) + wrap_pi(wrap_pi(-wrap_pi(x[:, 2])) + wrap_pi(x[:, 5])))
-        gtx, gty, gw = _se2_tangent_score(co * rx + so * ry, -so * rx + co * ry, w, self._precision)
+        return co * rx + so * ry, -so * rx + co * ry, w, co, so, ci, si, ux, uy
+
+    def log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """Density of x = [T_i | T_j]: the tangent Gaussian of observation^-1 * (T_i^-1 * T_j) times the Jacobian of Log
+        (reference :1443-1448)."""
+        tx, ty, w = self._residual(x)[:3]
+        return _se2_tangent_log_pdf(tx, ty, w, self._precision, self._log_norm)
+
+    def grad_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """d log_pdf / d[T_i | T_j], [n, 6] float64 (reference :1450-1478)."""
+        tx, ty, w, co, so, ci, si, ux, uy = self._residual(x)
+        gtx, gty, gw = _se2_tangent_score(tx, ty, w, self._precision)
         grx, gry = co * gtx - so * gty, so * gtx + co * gty
         gx, gy = ci * grx - si * gry, si * grx + ci * gry           # d/d(x_j, y_j)
         return np.stack([-gx, -gy, grx * uy - gry * ux - gw, gx, gy, gw], 1)
-
-    def pdf(self, x: np.ndarray) -> np.ndarray:
-        return np.exp(self.log_pdf(x))
 
     def density_record(self) -> dict:
         return dict(code="REL_SE2", a=self.var1, b=self.var2, cand=[],
@@ -495,23 +496,23 @@ class SE2R2RangeGaussianLikelihoodFactor(LikelihoodFactor, BinaryFactor):
         r = np.sqrt(((t2 - t1) ** 2).sum(1))
         return np.exp(-0.5 * ((r - self._observation[0]) / self._sigma) ** 2) / (np.sqrt(2 * np.pi) * self._sigma)
 
+    def _residual(self, x):
+        """-> (x, the position columns of var1 and of var2, t_1 - t_2, |t_1 - t_2|)."""
+        x = _as_points(x, self.var1.dim + self.var2.dim)
+        i1 = np.asarray(self.var1.t_dim_indices)
+        i2 = self.var1.dim + np.asarray(self.var2.t_dim_indices)
+        diff = x[:, i1] - x[:, i2]
+        return x, i1, i2, diff, np.sqrt((diff ** 2).sum(1))
+
     def log_pdf(self, x: np.ndarray) -> np.ndarray:
         """log N(|t_1 - t_2| - observation; 0, sigma^2) at x = [var1 | var2] (reference :2724-2730, :2195-2201)."""
-        x = _as_points(x, self.var1.dim + self.var2.dim)
-        d1 = self.var1.dim
-        t1 = x[:, :d1][:, self.var1.t_dim_indices]
-        t2 = x[:, d1:][:, self.var2.t_dim_indices]
-        delta = np.sqrt(((t1 - t2) ** 2).sum(1)) - self._observation[0]
-        return _gaussian_log_norm(self._sigma ** 2) - 0.5 * delta * delta * (1.0 / self._sigma ** 2)
+        return _range_log_pdf(self._residual(x)[-1], self._observation[0], self._sigma)
 
     def grad_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
         """d log_pdf / d[var1 | var2], float64 (reference :2732-2751, :2203-2223): along the line between the two ends,
         0 in a heading column, and the zero vector at a range of exactly 0 (the reference divides by it)."""
-        x = _as_points(x, self.var1.dim + self.var2.dim)
-        d1 = self.var1.dim
-        i1 = np.asarray(self.var1.t_dim_indices)
-        i2 = d1 + np.asarray(self.var2.t_dim_indices)
-        g = _range_score(x[:, i1], x[:, i2], self._observation[0], self._sigma)
+        x, i1, i2, diff, r = self._residual(x)
+        g = _range_score(diff, r, self._observation[0], self._sigma)
         out = np.zeros_like(x)
         out[:, i1], out[:, i2] = g, -g
         return out
@@ -601,11 +602,15 @@ class BinaryFactorMixture(LikelihoodFactor):
     def pdf(self, x: np.ndarray) -> np.ndarray:
         return sum(c.pdf(x[:, self.comp2idx[c]]) * w for c, w in zip(self.components, self.weights))
 
+    def _terms(self, x):
+        """-> (x, the weighted component terms log w_k + log p_k(x), [k, n])."""
+        x = _as_points(x, self.dim)
+        return x, np.stack([c.log_pdf(x[:, self.comp2idx[c]]) + np.log(w) for c, w in zip(self.components, self.weights)])
+
     def log_pdf(self, x: np.ndarray) -> np.ndarray:
         """log sum_k w_k p_k(x) by log-sum-exp: finite far from every component, where the reference's log of a sum of
         exps (:3126-3133) is -inf; equal to it wherever that is finite."""
-        x = _as_points(x, self.dim)
-        terms = np.stack([c.log_pdf(x[:, self.comp2idx[c]]) + np.log(w) for c, w in zip(self.components, self.weights)])
+        x, terms = self._terms(x)
         top = terms.max(0)
         return top + np.log(np.exp(terms - top).sum(0))
 
@@ -613,8 +618,7 @@ class BinaryFactorMixture(LikelihoodFactor):
         """d log_pdf / dx = sum_k r_k grad log p_k with r the softmax of the weighted component terms, shifted by their
         maximum like `log_pdf`: finite far from every component, where the reference (:3135-3156) divides by a sum of pdfs
         that has underflowed to 0.  A repeated candidate's contributions add into the same columns."""
-        x = _as_points(x, self.dim)
-        terms = np.stack([c.log_pdf(x[:, self.comp2idx[c]]) + np.log(w) for c, w in zip(self.components, self.weights)])
+        x, terms = self._terms(x)
         e = np.exp(terms - terms.max(0))
         r = e / e.sum(0)
         out = np.zeros_like(x)
@@ -757,18 +761,17 @@ class UnaryR2GaussianPriorFactor(ExplicitPriorFactor, UnaryFactor):
     def sample(self, num_samples: int, **kwargs) -> np.ndarray:
         return self._mu + _gaussian_noise(self._chol, num_samples)
 
+    def _residual(self, x):
+        return _as_points(x, 2) - self._mu
+
     def log_pdf(self, x: np.ndarray) -> np.ndarray:
         """log N(x; mu, covariance) (reference :373: the distribution's own log_pdf)."""
-        d = _as_points(x, 2) - self._mu
-        return _gaussian_log_norm(self._covariance) - 0.5 * _quad_form(d, np.linalg.inv(self._covariance))
+        return _gaussian_log_norm(self._covariance) - 0.5 * _quad_form(self._residual(x), np.linalg.inv(self._covariance))
 
     def grad_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
         """-precision (x - mu), [n, 2] float64."""
         P = np.linalg.inv(self._covariance)
-        return -(_as_points(x, 2) - self._mu) @ (0.5 * (P + P.T))
-
-    def pdf(self, x: np.ndarray) -> np.ndarray:
-        return np.exp(self.log_pdf(x))
+        return -self._residual(x) @ (0.5 * (P + P.T))
 
     def density_record(self) -> dict:
         return dict(code="PRIOR_R2", a=self.var, b=None, cand=[],
@@ -826,20 +829,18 @@ class UnaryR2RangeGaussianPriorFactor(ExplicitPriorFactor, UnaryFactor):
         phi = np.random.uniform(-np.pi, np.pi, num_samples)
         return self._center + np.stack([r * np.cos(phi), r * np.sin(phi)], 1)
 
+    def _residual(self, x):
+        diff = _as_points(x, 2) - self._center[None, :]
+        return diff, np.sqrt((diff ** 2).sum(1))
+
     def log_pdf(self, x: np.ndarray) -> np.ndarray:
         """log N(|x - center| - mu; 0, sigma^2): the range likelihood (reference :2195-2201) with one end at the centre,
         i.e. the density of the radius `sample` draws (see the module docstring on the reference's own body)."""
-        x = _as_points(x, 2)
-        delta = np.sqrt(((x - self._center) ** 2).sum(1)) - self._mu
-        return _gaussian_log_norm(self._sigma ** 2) - 0.5 * delta * delta * (1.0 / self._sigma ** 2)
+        return _range_log_pdf(self._residual(x)[-1], self._mu, self._sigma)
 
     def grad_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
         """d log_pdf / dx, [n, 2] float64: the range term's derivative with one end at the centre; 0 at the centre itself."""
-        x = _as_points(x, 2)
-        return _range_score(x, self._center[None, :], self._mu, self._sigma)
-
-    def pdf(self, x: np.ndarray) -> np.ndarray:
-        return np.exp(self.log_pdf(x))
+        return _range_score(*self._residual(x), self._mu, self._sigma)
 
     def density_record(self) -> dict:
         return dict(code="PRIOR_R2_RANGE", a=self.var, b=None, cand=[],
@@ -915,21 +916,19 @@ class R2RelativeGaussianLikelihoodFactor(LikelihoodFactor, BinaryFactor, OdomFac
             raise ValueError("Dimensionality of variable 1 or variable 2 is wrong")
         return var2 - var1 + _gaussian_noise(self._chol, var1.shape[0])
 
+    def _residual(self, x):
+        x = _as_points(x, 4)
+        return x[:, 2:] - x[:, :2] - self._observation
+
     def log_pdf(self, x: np.ndarray) -> np.ndarray:
         """log N(var2 - var1 - observation; 0, covariance) at x = [var1 | var2] (reference :1070-1074)."""
-        x = _as_points(x, 4)
-        d = x[:, 2:] - x[:, :2] - self._observation
-        return _gaussian_log_norm(self._covariance) - 0.5 * _quad_form(d, np.linalg.inv(self._covariance))
+        return _gaussian_log_norm(self._covariance) - 0.5 * _quad_form(self._residual(x), np.linalg.inv(self._covariance))
 
     def grad_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
         """d log_pdf / d[var1 | var2], [n, 4] float64: +-precision (var2 - var1 - observation)."""
-        x = _as_points(x, 4)
         P = np.linalg.inv(self._covariance)
-        g = -(x[:, 2:] - x[:, :2] - self._observation) @ (0.5 * (P + P.T))
+        g = -self._residual(x) @ (0.5 * (P + P.T))
         return np.concatenate([-g, g], 1)
-
-    def pdf(self, x: np.ndarray) -> np.ndarray:
-        return np.exp(self.log_pdf(x))
 
     def density_record(self) -> dict:
         return dict(code="REL_R2", a=self.var1, b=self.var2, cand=[],

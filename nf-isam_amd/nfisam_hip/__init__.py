@@ -775,7 +775,7 @@ def posterior_log_density(table: np.ndarray, cols: np.ndarray, obs: np.ndarray, 
 FACTOR_DTYPE = np.dtype([("code", np.int32), ("a", np.int32), ("b", np.int32), ("k", np.int32), ("cand", np.int32, (4,)),
                          ("p", np.float64, (16,))])
 assert FACTOR_DTYPE.itemsize == C.sizeof(FactorTerm)
-# NFISAM_FAC_* of include/nfisam_hip.h; _FAC_ROWS: code -> (rows of St read at `a`, rows read at `b` or 0)
+# NFISAM_FAC_* of include/nfisam_hip.h; _FAC_ROWS: code -> (rows of St read at `a`, at `b` or 0), as csrc/factor_model.h has them
 FAC_CODES = {"PRIOR_SE2": 1, "REL_SE2": 2, "RANGE": 3, "RANGE_MIX": 4, "PRIOR_R2": 5, "PRIOR_R2_RANGE": 6, "REL_R2": 7}
 _FAC_ROWS = {1: (3, 0), 2: (3, 3), 3: (2, 2), 4: (2, 0), 5: (2, 0), 6: (2, 0), 7: (2, 2)}
 
@@ -832,22 +832,14 @@ def factor_graph_log_density(terms: np.ndarray, S, device, per_factor=False, ter
     points, the arithmetic is float64).  Launched on the current stream.  `terms_dev`: an uploaded copy of `terms` to reuse
     (uint8 device tensor, kept by callers that score every update).
     -> log_p [n] float64 device tensor; with per_factor: (log_p, per [n_terms, n] float64)."""
-    if not (torch.is_tensor(S) or isinstance(S, np.ndarray)) or S.ndim != 2:
-        raise ValueError("S must be a [n, total_dim] tensor or array")
-    check_factor_terms(terms, int(S.shape[1]))
-    if torch.is_tensor(S):
-        St = S.to(device=device, dtype=torch.float32).t().contiguous()
-    else:
-        St = torch.from_numpy(np.ascontiguousarray(S.T, dtype=np.float32)).to(device)
-    return factor_graph_log_density_t(terms, St, device, per_factor=per_factor, terms_dev=terms_dev, checked=True)
+    check_factor_terms(terms, _points_width(S))
+    return factor_graph_log_density_t(terms, _columns(S, device), device, per_factor=per_factor, terms_dev=terms_dev, checked=True)
 
 
 def factor_graph_log_density_t(terms: np.ndarray, St, device, per_factor=False, terms_dev=None, checked=False):
     """`factor_graph_log_density` on the COLUMN-major matrix St [total_dim, n] (contiguous float32 device tensor): what the
     tree walk wrote, scored in place."""
-    if not torch.is_tensor(St) or St.ndim != 2 or St.dtype != torch.float32 or not St.is_contiguous():
-        raise ValueError("St must be a contiguous float32 [total_dim, n] tensor")
-    total_dim, n = int(St.shape[0]), int(St.shape[1])
+    total_dim, n = _points_shape_t(St)
     if not checked:
         check_factor_terms(terms, total_dim)
     nt = int(terms.shape[0])
@@ -858,13 +850,10 @@ def factor_graph_log_density_t(terms: np.ndarray, St, device, per_factor=False, 
     if nt == 0 or n == 0:
         log_p.zero_()                                       # the empty graph / no points: nothing to launch
     else:
-        if terms_dev is None:
-            terms_dev, = upload(terms.view(np.uint8).reshape(-1), device=device)
-        _check(lib().nfisam_factor_graph_log_density(C.c_void_p(terms_dev.data_ptr()), nt, _ptr(St), total_dim, n, _ptr(log_p),
-                                                     _ptr(per), _stream()), "nfisam_factor_graph_log_density")
-    if per_factor:
-        return log_p, per
-    return log_p
+        dev = _factor_tables(device, terms, terms_dev)
+        _check(lib().nfisam_factor_graph_log_density(_ptr(dev["terms"]), nt, _ptr(St), total_dim, n, _ptr(log_p), _ptr(per),
+                                                     _stream()), "nfisam_factor_graph_log_density")
+    return (log_p, per) if per_factor else log_p
 
 
 # ---- the front of the sample bindings: what every evaluator over the walk's sample matrix checks and stages ---------------------
@@ -931,6 +920,24 @@ def _flags(a):
 
 def _table_bytes(blocks):
     return blocks.view(np.uint8).reshape(-1)
+
+
+# the factor evaluators' front: a bad S or table is a ValueError before the device matters, then `_columns(S, device)` copies
+def _points_width(S):
+    if not (torch.is_tensor(S) or isinstance(S, np.ndarray)) or S.ndim != 2:
+        raise ValueError("S must be a [n, total_dim] tensor or array")
+    return int(S.shape[1])
+
+
+def _points_shape_t(St):
+    if not torch.is_tensor(St) or St.ndim != 2 or St.dtype != torch.float32 or not St.is_contiguous():
+        raise ValueError("St must be a contiguous float32 [total_dim, n] tensor")
+    return int(St.shape[0]), int(St.shape[1])
+
+
+def _factor_tables(device, terms, terms_dev, **lists):
+    """-> {"terms": the table's device copy (`terms_dev` reused, else `terms` uploaded), **`lists`}: ONE staged copy for the rest."""
+    return _upload_named(device, terms=terms_dev if terms_dev is not None else _table_bytes(np.ascontiguousarray(terms)), **lists)
 
 
 def _upload_named(device, **arrays):
@@ -1055,12 +1062,9 @@ def mmd_sums_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, scale=None, wrap=None, 
 
 
 # ---- the score of the joint density (nfisam_factor_graph_score) ------------------------------------------------------------------
-# slots a factor writes, by code: one per row it touches, a's rows first, then b's or the candidates' (csrc/factor_score.hip)
-_FAC_SLOTS = {1: 3, 2: 6, 3: 4, 5: 2, 6: 2, 7: 4}                  # (4, RANGE_MIX: 2 + 2 k)
-
-
 def _slot_rows(terms: np.ndarray):
-    """-> (slot_off [n_terms] int32, rows [n_slots] int64: the row of G every slot adds into), in table order."""
+    """-> (slot_off [n_terms] int32, rows [n_slots] int64: the row of G every slot adds into), in table order: a factor writes
+    one slot per row it touches, a's rows first, then b's or the candidates' (slot_count of csrc/factor_model.h)."""
     slot_off, rows = np.zeros(terms.shape[0], dtype=np.int32), []
     for i in range(terms.shape[0]):
         code, a, b, k = int(terms["code"][i]), int(terms["a"][i]), int(terms["b"][i]), int(terms["k"][i])
@@ -1095,10 +1099,9 @@ def factor_graph_score(terms: np.ndarray, S, device, terms_dev=None, gather=None
     `pack_score_gather(terms, total_dim)` to reuse.
     -> G [n, total_dim] float64 device tensor (a view of the column-major result); with slots=True: (G, slot values
     [n_slots, n] float64, the per-factor partial derivatives the rows are added from)."""
-    if not (torch.is_tensor(S) or isinstance(S, np.ndarray)) or S.ndim != 2:
-        raise ValueError("S must be a [n, total_dim] tensor or array")
+    total_dim = _points_width(S)
     if gather is None:
-        gather = pack_score_gather(terms, int(S.shape[1]))
+        gather = pack_score_gather(terms, total_dim)                   # (checks the table)
     out = factor_graph_score_t(terms, _columns(S, device), device, terms_dev=terms_dev, gather=gather, slots=slots)
     return (out[0].t(), out[1]) if slots else out.t()
 
@@ -1106,9 +1109,7 @@ def factor_graph_score(terms: np.ndarray, S, device, terms_dev=None, gather=None
 def factor_graph_score_t(terms: np.ndarray, St, device, terms_dev=None, gather=None, slots=False):
     """`factor_graph_score` on the COLUMN-major matrix St [total_dim, n] (contiguous float32 device tensor): what the tree
     walk wrote, differentiated in place.  -> Gt [total_dim, n] float64 device tensor, the layout `ksd_sums_t` reads."""
-    if not torch.is_tensor(St) or St.ndim != 2 or St.dtype != torch.float32 or not St.is_contiguous():
-        raise ValueError("St must be a contiguous float32 [total_dim, n] tensor")
-    total_dim, n = int(St.shape[0]), int(St.shape[1])
+    total_dim, n = _points_shape_t(St)
     if gather is None:
         gather = pack_score_gather(terms, total_dim)                   # (checks the table)
     elif gather["row_off"].shape[0] != total_dim + 1 or gather["slot_off"].shape[0] != terms.shape[0]:
@@ -1120,10 +1121,9 @@ def factor_graph_score_t(terms: np.ndarray, St, device, terms_dev=None, gather=N
     vals = torch.empty(ns, n, dtype=torch.float64, device=device)     # the scratch: from torch's allocator
     if nt > 0 and n > 0:
         with torch.cuda.device(device):
-            dev = _upload_named(device, terms=terms_dev if terms_dev is not None else _table_bytes(np.ascontiguousarray(terms)),
-                                slot_off=gather["slot_off"], row_off=gather["row_off"], row_slot=gather["row_slot"])
-            count = int(lib().nfisam_factor_graph_score_scratch_count(ns, n))
-            assert count == vals.numel()
+            dev = _factor_tables(device, terms, terms_dev, slot_off=gather["slot_off"], row_off=gather["row_off"],
+                                 row_slot=gather["row_slot"])
+            assert int(lib().nfisam_factor_graph_score_scratch_count(ns, n)) == vals.numel()
             _check(lib().nfisam_factor_graph_score(_ptr(dev["terms"]), nt, _ptr(St), total_dim, n, _ptr(dev["slot_off"]), ns,
                                                    _ptr(dev["row_off"]), _ptr(dev["row_slot"]), _ptr(Gt), _ptr(vals),
                                                    _stream()), "nfisam_factor_graph_score")

@@ -836,6 +836,20 @@ class NFiSAM(FactorGraphSolver):
                 S[:, pcol[v]:pcol[v] + v.dim] = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
         return S
 
+    def _need_graph(self, what: str, factors: bool = True):
+        """RuntimeError unless variables (and, with `factors`, measurement factors) have been added and ordered."""
+        if (factors and not self.physical_factors) or not self._elimination_ordering:
+            raise RuntimeError("%s: no factor graph yet (run an incremental update first)" % what)
+
+    def _need_tree(self, what: str):
+        """RuntimeError unless there is a Bayes tree and every clique of it has a trained model: what a draw or log q needs."""
+        tree = self._physical_bayes_tree
+        if tree is None or tree.root is None:
+            raise RuntimeError("%s: no Bayes tree yet (run an incremental update first)" % what)
+        for clique in tree.clique_ordering():
+            if clique not in self._clique_density_model:
+                raise RuntimeError("%s: clique %s has no trained model yet" % (what, clique))
+
     def posterior_log_pdf(self, samples, per_clique: bool = False):
         """log q(X) of the tree's posterior at n points, not in the reference: the sum over the cliques of the physical Bayes
         tree of log q_c(frontal | separator, true observations), each the clique's trained flow evaluated forward on the
@@ -850,12 +864,7 @@ class NFiSAM(FactorGraphSolver):
         heading spreads SLAM produces (std << pi).  Stream-ordered on the current stream behind the fits and the walk.
         Raises RuntimeError when there is no tree (or no trained model) yet, ValueError for a missing variable or ragged n,
         before anything is launched."""
-        tree = self._physical_bayes_tree
-        if tree is None or tree.root is None:
-            raise RuntimeError("posterior_log_pdf: no Bayes tree yet (run an incremental update first)")
-        for clique in tree.clique_ordering():
-            if clique not in self._clique_density_model:
-                raise RuntimeError("posterior_log_pdf: clique %s has no trained model yet" % clique)
+        self._need_tree("posterior_log_pdf")
         values, n = self._check_points(samples, "posterior_log_pdf")
         t = self._posterior_table()
         K, H, B, L = t["cfg"]
@@ -882,13 +891,18 @@ class NFiSAM(FactorGraphSolver):
         self._joint_cache = cache
         return cache
 
+    @staticmethod
+    def _joint_terms_dev(cache, device, n: int):
+        """The cached table's copy on `device`: uploaded on the first call with points, kept until the table grows."""
+        if device not in cache["dev"] and n:
+            cache["dev"][device], = _nh.upload(cache["terms"].view(np.uint8).reshape(-1), device=device, cached=True)
+        return cache["dev"].get(device)
+
     def _joint_launch(self, S, pcol, device, per_factor: bool = False):
         cache = self._joint_terms(pcol)
         _nh.check_factor_terms(cache["terms"], int(S.shape[1]))
-        if device not in cache["dev"] and int(S.shape[0]):
-            cache["dev"][device], = _nh.upload(cache["terms"].view(np.uint8).reshape(-1), device=device, cached=True)
         return _nh.factor_graph_log_density(cache["terms"], S, device, per_factor=per_factor,
-                                            terms_dev=cache["dev"].get(device))
+                                            terms_dev=self._joint_terms_dev(cache, device, int(S.shape[0])))
 
     def joint_log_pdf(self, samples, per_factor: bool = False):
         """log p(X, Z) = sum over the measurement factors f of log p_f(x_f) at n points: the reference's JointFactor.log_pdf
@@ -901,9 +915,8 @@ class NFiSAM(FactorGraphSolver):
         is the left-to-right float64 sum of the terms.  Headings count modulo 2 pi.
         Raises RuntimeError when no factor graph has been built yet, ValueError for a missing variable, a wrong width or
         ragged n, NotImplementedError naming the class of a factor without a device code -- before anything is launched."""
+        self._need_graph("joint_log_pdf")
         factors = self.physical_factors
-        if not factors or not self._elimination_ordering:
-            raise RuntimeError("joint_log_pdf: no factor graph yet (run an incremental update first)")
         values, n = self._check_points(samples, "joint_log_pdf")
         pcol, total_dim = self._post_columns()
         self._joint_terms(pcol)                              # (packs: an unknown factor class raises here)
@@ -928,14 +941,8 @@ class NFiSAM(FactorGraphSolver):
         estimates log p(Z) and `elbo` bounds it from below; headings are compared modulo 2 pi on both sides.  log_w is
         therefore not something that should average to zero.  log q is a float32 value of magnitude ~5e3 (spacing 5e-4);
         log w inherits that."""
-        if not self.physical_factors or not self._elimination_ordering:
-            raise RuntimeError("posterior_diagnostics: no factor graph yet (run an incremental update first)")
-        tree = self._physical_bayes_tree
-        if tree is None or tree.root is None:
-            raise RuntimeError("posterior_diagnostics: no Bayes tree yet (run an incremental update first)")
-        for clique in tree.clique_ordering():
-            if clique not in self._clique_density_model:
-                raise RuntimeError("posterior_diagnostics: clique %s has no trained model yet" % clique)
+        self._need_graph("posterior_diagnostics")
+        self._need_tree("posterior_diagnostics")
         if samples is not None:
             values, rows = self._check_points(samples, "posterior_diagnostics")
         t = self._posterior_table()
@@ -978,9 +985,8 @@ class NFiSAM(FactorGraphSolver):
         g = cache.get("gather")
         if g is None or g["row_off"].shape[0] != total_dim + 1:
             g = cache["gather"] = _nh.pack_score_gather(cache["terms"], total_dim)
-        if device not in cache["dev"] and int(St.shape[1]):
-            cache["dev"][device], = _nh.upload(cache["terms"].view(np.uint8).reshape(-1), device=device, cached=True)
-        return _nh.factor_graph_score_t(cache["terms"], St, device, terms_dev=cache["dev"].get(device), gather=g)
+        return _nh.factor_graph_score_t(cache["terms"], St, device, gather=g,
+                                        terms_dev=self._joint_terms_dev(cache, device, int(St.shape[1])))
 
     def joint_score(self, samples) -> np.ndarray:
         """The score grad_x log p(X, Z) of the measurement factors at n points: the reference's JointFactor.grad_x_log_pdf
@@ -990,9 +996,7 @@ class NFiSAM(FactorGraphSolver):
 
         samples: as `joint_log_pdf`.  -> np.ndarray [n, total_dim] float64, columns in the walk's permanent layout
         (`_post_columns`: variable -> first column).  Raises what `joint_log_pdf` raises, before anything is launched."""
-        factors = self.physical_factors
-        if not factors or not self._elimination_ordering:
-            raise RuntimeError("joint_score: no factor graph yet (run an incremental update first)")
+        self._need_graph("joint_score")
         values, n = self._check_points(samples, "joint_score")
         pcol, total_dim = self._post_columns()
         self._joint_terms(pcol)                              # (packs: an unknown factor class raises here)
@@ -1021,15 +1025,9 @@ class NFiSAM(FactorGraphSolver):
         device code, ValueError for bad points or options -- before anything is launched."""
         from utils import Statistics as ST
         what = "posterior_ksd"
-        if not self.physical_factors or not self._elimination_ordering:
-            raise RuntimeError("%s: no factor graph yet (run an incremental update first)" % what)
+        self._need_graph(what)
         if samples is None:
-            tree = self._physical_bayes_tree
-            if tree is None or tree.root is None:
-                raise RuntimeError("%s: no Bayes tree yet (run an incremental update first)" % what)
-            for clique in tree.clique_ordering():
-                if clique not in self._clique_density_model:
-                    raise RuntimeError("%s: clique %s has no trained model yet" % (what, clique))
+            self._need_tree(what)
         values, rows = self._summary_points(what, samples, n)
         nboot = int(nboot)
         if nboot < 0 or (nboot > 0 and (rows < 2 or rows > _nh.KSD_MATRIX_MAX_N)):
@@ -1099,15 +1097,9 @@ class NFiSAM(FactorGraphSolver):
             raise ValueError("%s: estimator must be one of %s, got %r" % (what, ESTIMATORS, estimator))
         if columns not in ("xy", "all"):
             raise ValueError("%s: columns must be 'xy' or 'all', got %r" % (what, columns))
-        if not self._elimination_ordering:
-            raise RuntimeError("%s: no factor graph yet (run an incremental update first)" % what)
+        self._need_graph(what, factors=False)
         if samples is None:
-            tree = self._physical_bayes_tree
-            if tree is None or tree.root is None:
-                raise RuntimeError("%s: no Bayes tree yet (run an incremental update first)" % what)
-            for clique in tree.clique_ordering():
-                if clique not in self._clique_density_model:
-                    raise RuntimeError("%s: clique %s has no trained model yet" % (what, clique))
+            self._need_tree(what)
         known = set(self._elimination_ordering)
         if variables is None:
             variables = [v for v in self._elimination_ordering if v in reference]
@@ -1194,20 +1186,13 @@ class NFiSAM(FactorGraphSolver):
     # ---- what posterior_summary and posterior_modes share: arguments, block table, the device matrix and its weights ----
     def _summary_blocks(self, what, samples, variables, pairs, weights):
         """The checks that need no points -> (importance, variables, pairs)."""
-        if not self._elimination_ordering:
-            raise RuntimeError("%s: no factor graph yet (run an incremental update first)" % what)
+        self._need_graph(what, factors=False)
         importance = isinstance(weights, str)
         if importance and weights != "importance":
             raise ValueError("%s: weights is None, an [n] array or 'importance', got %r" % (what, weights))
         if samples is None or importance:
-            if importance and not self.physical_factors:
-                raise RuntimeError("%s: no factor graph yet (run an incremental update first)" % what)
-            tree = self._physical_bayes_tree
-            if tree is None or tree.root is None:
-                raise RuntimeError("%s: no Bayes tree yet (run an incremental update first)" % what)
-            for clique in tree.clique_ordering():
-                if clique not in self._clique_density_model:
-                    raise RuntimeError("%s: clique %s has no trained model yet" % (what, clique))
+            self._need_graph(what, factors=importance)
+            self._need_tree(what)
         known = set(self._elimination_ordering)
         variables = list(self._elimination_ordering) if variables is None else list(variables)
         pairs = [tuple(p) for p in pairs] if pairs is not None else []

@@ -182,3 +182,70 @@ def test_empty_inputs_and_the_c_entry_refusals():
     assert call(*ok) == nh.OK
     torch.cuda.synchronize()
     assert not Gt.cpu().numpy().any()
+
+
+def test_one_guard_serves_both_entries():
+    """Ten records in two FAC_RUN runs, eight of them bad, straight into both C entries (the Python checks refuse each of them):
+    a bad record reads nothing -- St is the middle of a larger tensor whose outer rows hold a sentinel no result may show --
+    and yields NaN as its term and in the slots it owns; the good records' bits are those of the table without the bad ones."""
+    import ctypes as C
+    X, L0, L1 = SE2Variable("X0"), R2Variable("L0", VariableType.Landmark), R2Variable("L1", VariableType.Landmark)
+    good = nh.pack_factor_terms([F.SE2R2RangeGaussianLikelihoodFactor(X, L0, 4.0, 0.5),
+                                 F.UnaryR2GaussianPriorFactor(L1, np.array([1.0, -2.0]), np.diag([0.04, 0.09]))],
+                                {X: 0, L0: 3, L1: 5})
+    total, n, sentinel = 7, 65, 1.0e30
+
+    def rec(code, a=0, b=0, k=0, cand=(0, 0, 0, 0)):
+        t = np.zeros(1, dtype=nh.FACTOR_DTYPE)
+        t["code"], t["a"], t["b"], t["k"], t["cand"] = code if isinstance(code, int) else nh.FAC_CODES[code], a, b, k, cand
+        t["p"][0, :10] = [1.0, 0.5, 0.1, 2.0, 0.1, 0.2, 3.0, 0.3, 4.0, -1.0]
+        return t
+    bad = [rec("RANGE", a=-1, b=3), rec("PRIOR_SE2", a=5), rec("REL_SE2", a=0, b=5), rec("RANGE", a=0, b=6),
+           rec("RANGE_MIX", k=0, cand=(3, 3, 3, 3)), rec("RANGE_MIX", k=5, cand=(3, 3, 3, 3)),
+           rec("RANGE_MIX", k=2, cand=(3, 6, 0, 0)), rec(8)]
+    owned = [4, 3, 6, 4, 0, 0, 6, 0]                                          # slot_count of the code and k
+    for t in bad:                                                             # before any launch: each refused on its own
+        with pytest.raises(ValueError):
+            nh.check_factor_terms(t, total)
+    terms = np.concatenate([good[:1]] + bad + [good[1:]])
+    assert terms.shape[0] == 10 and nh.check_factor_terms(good, total) is None
+    rng = np.random.RandomState(3)
+    big = torch.full((11, n), sentinel, dtype=torch.float32, device=DEV)
+    big[2:9] = torch.from_numpy((rng.randn(total, n) * 2.0).astype(np.float32)).to(DEV)
+    St = big[2:9]
+    assert St.is_contiguous()
+    ptr, null = (lambda t: C.c_void_p(t.data_ptr())), C.c_void_p(0)
+
+    def density(tb):
+        dev, = nh.upload(nh._table_bytes(tb), device=DEV)
+        log_p = torch.zeros(n, dtype=torch.float64, device=DEV)
+        per = torch.zeros(tb.shape[0], n, dtype=torch.float64, device=DEV)
+        assert nh.lib().nfisam_factor_graph_log_density(ptr(dev), tb.shape[0], ptr(St), total, n, ptr(log_p), ptr(per), null) == nh.OK
+        torch.cuda.synchronize()
+        return log_p.cpu().numpy(), per.cpu().numpy()
+
+    def score(tb, stride):
+        nt, ns = tb.shape[0], stride * tb.shape[0]
+        dev = nh._upload_named(DEV, terms=nh._table_bytes(tb), slot_off=stride * np.arange(nt, dtype=np.int32),
+                               row_off=np.zeros(total + 1, dtype=np.int32), row_slot=np.zeros(1, dtype=np.int32))
+        Gt = torch.full((total, n), sentinel, dtype=torch.float64, device=DEV)
+        scratch = torch.full((ns, n), sentinel, dtype=torch.float64, device=DEV)
+        assert nh.lib().nfisam_factor_graph_score(ptr(dev["terms"]), nt, ptr(St), total, n, ptr(dev["slot_off"]), ns,
+                                                  ptr(dev["row_off"]), ptr(dev["row_slot"]), ptr(Gt), ptr(scratch), null) == nh.OK
+        torch.cuda.synchronize()
+        return Gt.cpu().numpy(), scratch.cpu().numpy()
+
+    log_p2, per2 = density(good)
+    log_p, per = density(terms)
+    assert np.all(np.isfinite(per2)) and np.all(np.abs(per2) < 1e6)            # (no sentinel went into a good term)
+    assert np.all(np.isnan(per[1:9])) and np.all(np.isnan(log_p))
+    assert np.array_equal(per[0], per2[0]) and np.array_equal(per[9], per2[1])
+    G2, s2 = score(good, 10)
+    G, s = score(terms, 10)
+    assert not G.any() and not G2.any()                                        # empty row lists: Gt is all zero
+    assert np.all(np.isfinite(s2[:4])) and np.all(np.isfinite(s2[10:12])) and np.all(np.abs(s2[:4]) < 1e6)
+    assert np.array_equal(s[0:4], s2[0:4]) and np.array_equal(s[90:92], s2[10:12])
+    assert np.all(s[4:10] == sentinel) and np.all(s[92:] == sentinel)
+    for i, cnt in enumerate(owned, start=1):
+        assert np.all(np.isnan(s[10 * i:10 * i + cnt])), i
+        assert np.all(s[10 * i + cnt:10 * (i + 1)] == sentinel), i
