@@ -716,26 +716,17 @@ def posterior_walk_raw(table: np.ndarray, cols: np.ndarray, obs: np.ndarray, tot
     return St.t().contiguous()
 
 
-def posterior_log_density(table: np.ndarray, cols: np.ndarray, obs: np.ndarray, S, max_D, K, H, B, L, device,
-                          per_clique=False, latent=False):
-    """Joint log-density of the tree's posterior at the n rows of S (nfisam_nsf_posterior_log_density): the clique table
-    of `posterior_walk_raw` (numpy POST_DTYPE, parents first), S [n, total_dim] as the walk returns it (tensor or numpy).
-    Launched on the current stream.  -> log_q [n] (device tensor); with per_clique or latent: (log_q, per [n_cliques, n] or
-    None, latent [total_dim, n] or None) -- `latent` holds z of every frontal column at the row of Zt the walk reads that
-    column's draw from (rows of no frontal column are zero)."""
+def check_posterior_table(table: np.ndarray, cols, obs, total_dim: int, max_D, K, H, B, L, latent=False):
+    """ValueError for a clique table the log-density kernel must not see -> (cols int32, obs float32), flattened."""
     if not isinstance(table, np.ndarray) or table.dtype != POST_DTYPE or table.ndim != 1:
         raise ValueError("table must be a 1-D numpy array of POST_DTYPE")
-    if not (torch.is_tensor(S) or isinstance(S, np.ndarray)) or S.ndim != 2:
-        raise ValueError("S must be a [n, total_dim] tensor or array")
-    n, total_dim = int(S.shape[0]), int(S.shape[1])
     cols = np.asarray(cols, dtype=np.int32).reshape(-1)
     obs = np.asarray(obs, dtype=np.float32).reshape(-1)
     if not supported(K, H):
         raise ValueError("num_knots=%r, hidden_dim=%r: no kernels for this (K, H)" % (K, H))
     if int(L) < 1 or not float(B) > 0 or int(max_D) < 1:
         raise ValueError("L >= 1, B > 0 and max_D >= 1 are required")
-    nc = int(table.shape[0])
-    if nc:
+    if int(table.shape[0]):
         n_obs, n_sep, n_fr = (table[f].astype(np.int64) for f in ("n_obs", "n_sep", "n_frontal"))
         Dm = table["D_model"].astype(np.int64)
         if (min(n_obs.min(), n_sep.min(), n_fr.min()) < 0 or np.any(n_obs + n_sep + n_fr > Dm) or Dm.max() > int(max_D)
@@ -749,10 +740,29 @@ def posterior_log_density(table: np.ndarray, cols: np.ndarray, obs: np.ndarray, 
             raise ValueError("a column index is out of range of the %d columns of S" % total_dim)
         if latent and int(n_fr.sum()) > total_dim:
             raise ValueError("the cliques' frontal columns exceed the %d latent rows" % total_dim)
-    if torch.is_tensor(S):
-        St = S.to(device=device, dtype=torch.float32).t().contiguous()
-    else:
-        St = torch.from_numpy(np.ascontiguousarray(S.T, dtype=np.float32)).to(device)
+    return cols, obs
+
+
+def posterior_log_density(table: np.ndarray, cols: np.ndarray, obs: np.ndarray, S, max_D, K, H, B, L, device,
+                          per_clique=False, latent=False):
+    """Joint log-density of the tree's posterior at the n rows of S (nfisam_nsf_posterior_log_density): the clique table
+    of `posterior_walk_raw` (numpy POST_DTYPE, parents first), S [n, total_dim] as the walk returns it (tensor or numpy).
+    Launched on the current stream.  -> log_q [n] (device tensor); with per_clique or latent: (log_q, per [n_cliques, n] or
+    None, latent [total_dim, n] or None) -- `latent` holds z of every frontal column at the row of Zt the walk reads that
+    column's draw from (rows of no frontal column are zero)."""
+    cols, obs = check_posterior_table(table, cols, obs, _points_width(S), max_D, K, H, B, L, latent)
+    return posterior_log_density_t(table, cols, obs, _columns(S, device), max_D, K, H, B, L, device, per_clique=per_clique,
+                                   latent=latent, checked=True)
+
+
+def posterior_log_density_t(table: np.ndarray, cols: np.ndarray, obs: np.ndarray, St, max_D, K, H, B, L, device,
+                            per_clique=False, latent=False, checked=False):
+    """`posterior_log_density` on the COLUMN-major matrix St [total_dim, n] (contiguous float32 device tensor): what the tree
+    walk wrote, scored in place.  `checked` skips the table check (the caller has made it)."""
+    total_dim, n = _points_shape_t(St)
+    if not checked:
+        cols, obs = check_posterior_table(table, cols, obs, total_dim, max_D, K, H, B, L, latent)
+    nc = int(table.shape[0])
     log_q = torch.empty(n, dtype=torch.float32, device=device)
     # the per-clique terms are the first pass's output; they come from torch's allocator even when the caller does not want
     # them (the C entry would otherwise take a scratch buffer from HIP's own stream-ordered pool)

@@ -1,0 +1,606 @@
+"""slam.PosteriorEvaluation -- what a trained NFiSAM solver says about its posterior, not in the reference: densities
+(`posterior_log_pdf`, `joint_log_pdf`, `joint_score`), the solver grading itself (`posterior_diagnostics`, `map_estimate`,
+`posterior_ksd`, `posterior_mmd`) and what the posterior holds (`posterior_summary`, `posterior_modes`).
+
+A mixin of `slam.NFiSAM.NFiSAM`: the walk (`posterior_launch`, `_post_columns`, `_posterior_table`) and the solver's state
+are reached through `self`.  Every public method goes through ONE front, `_eval_points`, which makes the checks that need no
+device and hands back an `EvalPoints` record; the kernels then read the record's column-major matrix `St` [total_dim, n]
+through the `_t` bindings of nfisam_hip.  A new evaluation starts with a call of the front, not with a copy of another's
+opening lines."""
+import numpy as np
+import torch
+
+import nfisam_hip as _nh
+
+
+def _device():
+    if not torch.cuda.is_available():
+        raise RuntimeError("slam.NFiSAM needs a ROCm device (MI355X): the flow hot path has no CPU fallback")
+    return "cuda:%d" % torch.cuda.current_device()
+
+
+# how `_check_points` words its refusals: (a missing variable, a wrong shape, ragged rows, the letter of the row count)
+_SAMPLE_NOUNS = ("samples lack", "samples", "ragged samples", "n")
+_REFERENCE_NOUNS = ("the reference lacks", "reference samples", "ragged reference", "m")
+
+
+class EvalPoints:
+    """What `_eval_points` returns: values ({variable: array}, None for points that are to be drawn), rows, pcol (variable
+    -> first column), total_dim, table (the clique table when log q is evaluated, else None), device (the table's, else
+    where a draw lies, else the current ROCm device: asked for on first use, so that every check comes before the device
+    matters) and St, the column-major float32 device matrix [total_dim, rows] -- formed on first use and once: given values
+    are laid out on their side of the bus and copied over, a draw is the walk's matrix transposed."""
+    __slots__ = ("values", "rows", "pcol", "total_dim", "table", "_solver", "_device", "_St")
+
+    def __init__(self, solver, values, rows, pcol, total_dim, table):
+        self.values, self.rows, self.pcol, self.total_dim, self.table = values, rows, pcol, total_dim, table
+        self._solver, self._device, self._St = solver, None, None
+
+    @property
+    def device(self):
+        if self._device is None:
+            if self.table is not None:
+                self._device = torch.device(self.table["device"])
+            else:
+                self._device = self.St.device if self.values is None else torch.device(_device())
+        return self._device
+
+    @property
+    def St(self):
+        if self._St is None:
+            values, pcol = self.values, self.pcol
+            if values is None:                           # [n, total_dim] on the device, as the walk hands it back
+                St = self._solver.posterior_launch(self.rows)["S"].t().contiguous()
+            elif values and all(torch.is_tensor(a) for a in values.values()):
+                St = torch.zeros(self.total_dim, self.rows, dtype=torch.float32, device=self.device)
+                for v, a in values.items():
+                    St[pcol[v]:pcol[v] + v.dim] = a.to(device=self.device, dtype=torch.float32).t()
+            else:
+                host = np.zeros((self.total_dim, self.rows or 0), dtype=np.float32)
+                for v, a in values.items():
+                    host[pcol[v]:pcol[v] + v.dim] = (a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).T
+                St = torch.from_numpy(host).to(self.device)
+            self._St = St
+        return self._St
+
+
+class PosteriorEvaluation:
+    # ---- the front ----------------------------------------------------------------------------------------------------------
+    def _check_points(self, samples, what: str, variables=None, nouns=_SAMPLE_NOUNS, host: bool = False):
+        """Validation of a sample dict: `samples` maps every variable of `variables` (default: the elimination ordering) to
+        [n, dim] values (numpy or torch, extra keys ignored; `host`: brought to numpy).  -> ({variable: array}, n); ValueError
+        names what is wrong, in the words of `nouns`."""
+        lacks, shaped, ragged, letter = nouns
+        n, values = None, {}
+        for v in self._elimination_ordering if variables is None else variables:
+            if v not in samples:
+                raise ValueError("%s: %s variable %s" % (what, lacks, v.name))
+            a = samples[v]
+            if host:
+                a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+            if a.ndim == 1 and v.dim == 1:
+                a = a.reshape(-1, 1)
+            if a.ndim != 2 or a.shape[1] != v.dim:
+                raise ValueError("%s: %s of %s must be [%s, %d], got %s" % (what, shaped, v.name, letter, v.dim, tuple(a.shape)))
+            if n is None:
+                n = int(a.shape[0])
+            elif int(a.shape[0]) != n:
+                raise ValueError("%s: %s: %s has %d rows, the others %d" % (what, ragged, v.name, a.shape[0], n))
+            values[v] = a
+        return values, n
+
+    def _need_graph(self, what: str, factors: bool = True):
+        """RuntimeError unless variables (and, with `factors`, measurement factors) have been added and ordered."""
+        if (factors and not self.physical_factors) or not self._elimination_ordering:
+            raise RuntimeError("%s: no factor graph yet (run an incremental update first)" % what)
+
+    def _need_tree(self, what: str):
+        """RuntimeError unless there is a Bayes tree and every clique of it has a trained model: what a draw or log q needs."""
+        tree = self._physical_bayes_tree
+        if tree is None or tree.root is None:
+            raise RuntimeError("%s: no Bayes tree yet (run an incremental update first)" % what)
+        for clique in tree.clique_ordering():
+            if clique not in self._clique_density_model:
+                raise RuntimeError("%s: clique %s has no trained model yet" % (what, clique))
+
+    def _eval_points(self, what, samples, n=None, graph=True, factors=False, log_q=False, nonempty=False) -> EvalPoints:
+        """What every public evaluation calls first, in this order: the graph must exist (`graph`; with `factors`: and hold
+        measurement factors), the tree must be trained (for a draw, and with `log_q` for given points too), `samples` are
+        checked or -- None -- the row count of a draw is `n` (default posterior_sample_num), `nonempty` refuses 0 rows, the
+        columns are assigned, with `factors` the joint table is packed (an unknown factor class raises here) and with `log_q`
+        the clique table is built, which then names the device.  Nothing is launched and no device is touched."""
+        if graph:
+            self._need_graph(what, factors=factors)
+        if samples is None or log_q:
+            self._need_tree(what)
+        if samples is not None:
+            values, rows = self._check_points(samples, what)
+        else:
+            values, rows = None, int(self._args.posterior_sample_num if n is None else n)
+        if nonempty and rows < 1:
+            raise ValueError("%s: no points" % what)
+        pcol, total_dim = self._post_columns()
+        if factors:
+            self._joint_terms(pcol)
+        return EvalPoints(self, values, rows, pcol, total_dim, self._posterior_table() if log_q else None)
+
+    # ---- the launches behind them: log q, log p, the score ---------------------------------------------------------------------
+    def _joint_terms(self, pcol):
+        """The table of the physical factors (numpy FACTOR_DTYPE) and its uploaded copies.  Factors are only ever added and a
+        variable's rows are permanent: the table is cached and extended by the records of the factors that arrived since."""
+        factors = self.physical_factors
+        cache = self.__dict__.get("_joint_cache")
+        if cache is None or cache["count"] > len(factors):
+            cache = dict(count=0, terms=np.zeros(0, dtype=_nh.FACTOR_DTYPE), dev={})
+        if cache["count"] < len(factors):
+            fresh = _nh.pack_factor_terms(factors[cache["count"]:], pcol)        # NotImplementedError names the class
+            cache = dict(count=len(factors), terms=np.concatenate([cache["terms"], fresh]), dev={})
+        self._joint_cache = cache
+        return cache
+
+    @staticmethod
+    def _joint_terms_dev(cache, device, n: int):
+        """The cached table's copy on `device`: uploaded on the first call with points, kept until the table grows."""
+        if device not in cache["dev"] and n:
+            cache["dev"][device], = _nh.upload(cache["terms"].view(np.uint8).reshape(-1), device=device, cached=True)
+        return cache["dev"].get(device)
+
+    def _log_q_launch(self, pts: EvalPoints, per_clique: bool = False):
+        t = pts.table
+        K, H, B, L = t["cfg"]
+        return _nh.posterior_log_density_t(t["table"], t["cols"], t["obs"], pts.St, t["max_D"], K, H, B, L, pts.device,
+                                           per_clique=per_clique)
+
+    def _joint_launch(self, pts: EvalPoints, per_factor: bool = False):
+        cache = self._joint_terms(pts.pcol)
+        _nh.check_factor_terms(cache["terms"], pts.total_dim)
+        return _nh.factor_graph_log_density_t(cache["terms"], pts.St, pts.device, per_factor=per_factor, checked=True,
+                                              terms_dev=self._joint_terms_dev(cache, pts.device, pts.rows))
+
+    def _log_p_q(self, pts: EvalPoints):
+        """The two launches behind log w = log p - log q -> (log_p float64 [n], log_q float32 [n]) on the device.  What is made
+        of them differs on purpose: `posterior_diagnostics` forms the weights on the host, `_weights` on the device."""
+        log_q = self._log_q_launch(pts)
+        return self._joint_launch(pts), log_q
+
+    def _score_launch(self, pts: EvalPoints):
+        """Gt [total_dim, n] float64 on the device: the cached table of `_joint_terms`, its gather lists kept next to it."""
+        cache = self._joint_terms(pts.pcol)
+        g = cache.get("gather")
+        if g is None or g["row_off"].shape[0] != pts.total_dim + 1:
+            g = cache["gather"] = _nh.pack_score_gather(cache["terms"], pts.total_dim)
+        return _nh.factor_graph_score_t(cache["terms"], pts.St, pts.device, gather=g,
+                                        terms_dev=self._joint_terms_dev(cache, pts.device, pts.rows))
+
+    # ---- the densities -------------------------------------------------------------------------------------------------------
+    def posterior_log_pdf(self, samples, per_clique: bool = False):
+        """log q(X) of the tree's posterior at n points, not in the reference: the sum over the cliques of the physical Bayes
+        tree of log q_c(frontal | separator, true observations), each the clique's trained flow evaluated forward on the
+        device (all cliques in one launch plus a per-point sum: nfisam_nsf_posterior_log_density).
+
+        samples: mapping variable -> [n, dim] values (numpy or torch; the dict or LazyPosterior that `sample_posterior`
+        returns is valid input); it must hold every variable of the current tree, extra keys are ignored.
+        -> np.ndarray[n] float32; with per_clique=True: (total [n], terms [n, n_cliques], cliques in table order).
+
+        The density is in the variables' own units (metres, radians) and periodic in every angle.  On the circle it is
+        normalised up to the mass each clique's flow puts beyond +-pi / std of its heading columns -- negligible for the
+        heading spreads SLAM produces (std << pi).  Stream-ordered on the current stream behind the fits and the walk.
+        Raises RuntimeError when there is no tree (or no trained model) yet, ValueError for a missing variable or ragged n,
+        before anything is launched."""
+        pts = self._eval_points("posterior_log_pdf", samples, graph=False, log_q=True)
+        out = self._log_q_launch(pts, per_clique=per_clique)
+        if per_clique:
+            log_q, per, _ = out
+            return log_q.cpu().numpy(), per.t().cpu().numpy(), list(pts.table["cliques"])
+        return out.cpu().numpy()
+
+    def joint_log_pdf(self, samples, per_factor: bool = False):
+        """log p(X, Z) = sum over the measurement factors f of log p_f(x_f) at n points: the reference's JointFactor.log_pdf
+        (src/sampler/sampler_utils.py:85-98) over `physical_factors` -- the factors of the graph, never the FlowsPriorFactor
+        messages of the working graph -- evaluated on the device in float64 at the float32 points
+        (nfisam_factor_graph_log_density; mixtures by log-sum-exp, finite where the reference underflows to -inf).
+
+        samples: as `posterior_log_pdf` (dict or LazyPosterior, numpy or torch, extra keys ignored).
+        -> np.ndarray[n] float64; with per_factor=True: (total [n], terms [n, n_factors], factors in table order); the total
+        is the left-to-right float64 sum of the terms.  Headings count modulo 2 pi.
+        Raises RuntimeError when no factor graph has been built yet, ValueError for a missing variable, a wrong width or
+        ragged n, NotImplementedError naming the class of a factor without a device code -- before anything is launched."""
+        pts = self._eval_points("joint_log_pdf", samples, factors=True)
+        factors = self.physical_factors
+        out = self._joint_launch(pts, per_factor=per_factor)
+        if per_factor:
+            return out[0].cpu().numpy(), out[1].t().cpu().numpy(), list(factors)
+        return out.cpu().numpy()
+
+    def posterior_diagnostics(self, samples=None, n: int = None) -> dict:
+        """The solver grading itself without ground truth: log w = log p - log q at posterior samples.
+
+        samples=None draws `n` (default posterior_sample_num) points through the tree walk and scores the device matrix where
+        it lies; otherwise `samples` is scored (as `posterior_log_pdf` / `joint_log_pdf` accept it) and nothing is drawn: the
+        solver's state and random streams are untouched.
+        -> dict: log_p, log_q, log_w (float64 [n]), elbo (mean log w), log_evidence (logsumexp(log w) - log n), ess
+        ((sum w)^2 / sum w^2 from max-shifted weights, in [1, n]), map_index (argmax of log p over the draw: the reference's
+        MAP rule, src/slam/FactorGraphSolver.py:660-671), map_sample (variable -> [dim]).
+
+        p is the unnormalised joint p(X, Z) of the measurement factors and q a normalised density of X, so `log_evidence`
+        estimates log p(Z) and `elbo` bounds it from below; headings are compared modulo 2 pi on both sides.  log_w is
+        therefore not something that should average to zero.  log q is a float32 value of magnitude ~5e3 (spacing 5e-4);
+        log w inherits that."""
+        pts = self._eval_points("posterior_diagnostics", samples, n, factors=True, log_q=True)
+        log_p, log_q = self._log_p_q(pts)
+        log_p, log_q = log_p.cpu().numpy(), log_q.cpu().numpy().astype(np.float64)
+        log_w = log_p - log_q
+        out = dict(log_p=log_p, log_q=log_q, log_w=log_w)
+        if log_w.size == 0:
+            raise ValueError("posterior_diagnostics: no points")
+        top = log_w.max()
+        w = np.exp(log_w - top)
+        out["elbo"] = float(log_w.mean())
+        out["log_evidence"] = float(top + np.log(w.sum()) - np.log(log_w.size))
+        out["ess"] = float(w.sum() ** 2 / (w * w).sum())
+        k = int(np.argmax(log_p))
+        row, pcol = pts.St[:, k].cpu().numpy(), pts.pcol
+        out["map_index"] = k
+        out["map_sample"] = {v: row[pcol[v]:pcol[v] + v.dim].copy() for v in self._elimination_ordering}
+        return out
+
+    def map_estimate(self, samples=None) -> dict:
+        """The sample of highest joint density log p among `samples` (or a fresh posterior draw): the reference's MAP
+        estimate (FactorGraphSolver.plot2d_MAP_rbt_only, src/slam/FactorGraphSolver.py:660-671).  -> variable -> [dim]."""
+        return self.posterior_diagnostics(samples)["map_sample"]
+
+    # ---- the solver graded against the factor graph itself: score and kernel Stein discrepancy -------------------------
+    def joint_score(self, samples) -> np.ndarray:
+        """The score grad_x log p(X, Z) of the measurement factors at n points: the reference's JointFactor.grad_x_log_pdf
+        (src/sampler/sampler_utils.py:101-118) over `physical_factors`, on the device in float64 at the float32 points
+        (nfisam_factor_graph_score: the zero vector at a range of exactly 0, softmax weights for mixtures -- finite where the
+        reference divides by zero).
+
+        samples: as `joint_log_pdf`.  -> np.ndarray [n, total_dim] float64, columns in the walk's permanent layout
+        (`_post_columns`: variable -> first column).  Raises what `joint_log_pdf` raises, before anything is launched."""
+        return self._score_launch(self._eval_points("joint_score", samples, factors=True)).t().cpu().numpy()
+
+    def posterior_ksd(self, samples=None, n: int = None, sigma=None, standardise: bool = True, nboot: int = 0,
+                      seed=None) -> dict:
+        """The solver graded against the factor graph itself, without a second sample set: the Gaussian kernel Stein
+        discrepancy (reference src/utils/Statistics.py:216-245) between posterior samples and the joint density p(X, Z)
+        through its score, both evaluated on the device where the sample matrix lies (nfisam_factor_graph_score,
+        nfisam_sample_ksd).
+
+        samples=None draws `n` (default posterior_sample_num) points through the tree walk; otherwise `samples` is graded (as
+        `joint_log_pdf` accepts it) and nothing is drawn.  standardise: every column's differences are divided by its spread
+        (the circular standard deviation for a heading; a column without spread leaves the kernel: scale 0); sigma: the
+        bandwidth in those units, None = sqrt(total_dim).  Headings are flagged circular from the variables: see
+        `Statistics.kernel_stein_discrepancy` on the antipode.  nboot > 0 adds the reference's multinomial bootstrap, its draws
+        from a generator of its own seeded with `seed`.
+        -> dict: ustat (None for n = 1), vstat, row_mean [n] (sum_j h_ij / n per point: where the draw disagrees with the
+        graph), precision (variable -> [dim]), sigma, n, and p_value / bootstrap with nboot > 0.
+        Nothing of the solver's state or random streams is touched (a draw uses the walk's generator as `sample_posterior`
+        does).  Raises RuntimeError when there is no graph / tree yet, NotImplementedError naming a factor class without a
+        device code, ValueError for bad points or options -- before anything is launched."""
+        from utils import Statistics as ST
+        what = "posterior_ksd"
+        pts = self._eval_points(what, samples, n, factors=True, nonempty=True)
+        rows, pcol, total_dim = pts.rows, pts.pcol, pts.total_dim
+        nboot = int(nboot)
+        if nboot < 0 or (nboot > 0 and (rows < 2 or rows > _nh.KSD_MATRIX_MAX_N)):
+            raise ValueError("%s: the bootstrap needs nboot >= 0 and 2 <= n <= %d" % (what, _nh.KSD_MATRIX_MAX_N))
+        if sigma is not None and not (np.isfinite(sigma) and sigma > 0):
+            raise ValueError("%s: sigma must be positive and finite" % what)
+        order = list(self._elimination_ordering)
+        flags, used = np.zeros(total_dim, dtype=bool), np.zeros(total_dim, dtype=bool)
+        for v in order:
+            flags[pcol[v]:pcol[v] + v.dim] = [bool(c) for c in v.circular_dim_list]
+            used[pcol[v]:pcol[v] + v.dim] = True
+        cols = np.flatnonzero(used)
+        scale = np.zeros(total_dim)
+        if standardise:
+            circ = flags[cols].astype(np.uint8)
+            mean, res, cov = _nh.sample_moments_t(pts.St, _nh.pack_moment_blocks(np.ones(cols.size, dtype=np.int64)), cols,
+                                                  circ if circ.any() else None, None, checked=True)
+            scale[cols] = ST.mode_scale(cov.cpu().numpy(), res.cpu().numpy(), flags[cols])
+        else:
+            scale[cols] = 1.0
+        sig = float(np.sqrt(cols.size)) if sigma is None else float(sigma)
+        precision = scale * scale / (sig * sig)
+        Gt = self._score_launch(pts)
+        sums = _nh.ksd_sums_t(pts.St, Gt, precision, wrap=flags.astype(np.uint8) if flags.any() else None, matrix=nboot > 0)
+        row = sums["row"].cpu().numpy()
+        u, vstat = ST.ksd_from_sums(row.sum(), sums["diag"].cpu().numpy().sum(), rows, ustat=rows >= 2)
+        out = dict(ustat=u, vstat=vstat, row_mean=row / rows, n=rows, sigma=sig,
+                   precision={v: precision[pcol[v]:pcol[v] + v.dim].copy() for v in order})
+        if nboot > 0:
+            rng = np.random.RandomState(seed)
+            draws = np.stack([rng.multinomial(rows, np.ones(rows) / rows) for _ in range(nboot)])
+            out["bootstrap"] = ST.ksd_bootstrap(sums["H"], draws)
+            out["p_value"] = float(np.mean(out["bootstrap"] >= u))
+        return out
+
+    # ---- the solver graded against a reference sample set --------------------------------------------------------
+    def posterior_mmd(self, reference, samples=None, n: int = None, variables=None, blocks=None, columns: str = "xy",
+                      estimator: str = "mmd", sigma=None, standardise: bool = False, joint: bool = True) -> dict:
+        """MMD between the posterior and a reference sample set -- how the paper grades NF-iSAM (the reference's
+        src/utils/Statistics.py:13-84 and icra_paper/compute_mmd.py: one joint `mmd` per step and the mean over the
+        variables of the xy-marginal `mmd`) -- with the joint block, every variable's marginal and any further blocks in ONE
+        device launch (nfisam_sample_mmd: float32 points, float64 arithmetic).
+
+        reference: mapping variable -> [m, dim] (numpy or torch): a reference solution, another solver's `sample_posterior`
+        output, a LazyPosterior.  samples=None draws `n` (default posterior_sample_num) points through the tree walk and scores
+        the device matrix where it lies; otherwise `samples` is what `posterior_log_pdf` accepts and nothing is drawn.
+        variables: which to compare and in which order (default: those of the elimination ordering that `reference` holds).
+        columns: "xy" the reference's rule, the first two columns of every variable (compute_mmd.py:88-98); "all" adds the
+        headings, compared by differences wrapped into [-pi, pi).  standardise: divide each non-circular column's differences
+        by the reference set's std of that column (floored at 1e-3).  blocks: further blocks, each a tuple of variables
+        (e.g. (pose, landmark)).  estimator, sigma: as `utils.Statistics.mmd_blocks` ("mmd": k_sigma2 = 1; "MMDb" / "MMDu2":
+        sigma = sqrt(columns of the block)).
+        -> dict: joint (None without `joint`), marginal (variable -> value), marginal_mean (the reference's "marginal mmd"),
+        blocks (list), floor = sqrt(1 / m + 1 / n) (the value MMDb takes when no pair of the two sets is within kernel
+        reach: a statistic that sits there says nothing), m (reference points), n (posterior points), estimator.
+        Raises RuntimeError when there is nothing to grade yet, ValueError for an unknown option, a requested variable that
+        the ordering, `reference` or `samples` lack, a wrong width, ragged rows or too few points -- before anything is
+        launched."""
+        from utils.Statistics import ESTIMATORS, mmd_from_sums
+        what = "posterior_mmd"
+        if estimator not in ESTIMATORS:
+            raise ValueError("%s: estimator must be one of %s, got %r" % (what, ESTIMATORS, estimator))
+        if columns not in ("xy", "all"):
+            raise ValueError("%s: columns must be 'xy' or 'all', got %r" % (what, columns))
+        pts = self._eval_points(what, samples, n)
+        rows, pcol = pts.rows, pts.pcol
+        known = set(self._elimination_ordering)
+        variables = [v for v in self._elimination_ordering if v in reference] if variables is None else list(variables)
+        extra = [tuple(b) for b in blocks] if blocks is not None else []
+        if not variables:
+            raise ValueError("%s: no variable to compare (the reference holds none of the ordering's)" % what)
+        for v in list(variables) + [v for b in extra for v in b]:
+            if v not in known:
+                raise ValueError("%s: variable %s is not in the elimination ordering" % (what, v.name))
+            if v not in reference:
+                raise ValueError("%s: the reference lacks variable %s" % (what, v.name))
+        for b in extra:
+            if not b or any(v not in variables for v in b):
+                raise ValueError("%s: a block is a non-empty tuple of compared variables" % what)
+        # the reference set: its own column layout, the requested variables side by side
+        ref, m = self._check_points(reference, what, variables, _REFERENCE_NOUNS, host=True)
+        rcol, width = {}, 0
+        for v in variables:
+            rcol[v] = width
+            width += v.dim
+        need = 1 if estimator == "MMDb" else 2
+        if m < need or rows < need:
+            raise ValueError("%s: %s needs at least %d points in each set (reference %d, posterior %d)"
+                             % (what, estimator, need, m, rows))
+        Y = np.concatenate([ref[v] for v in variables], axis=1).astype(np.float32)
+
+        def cols_of(v):
+            return range(v.dim if columns == "all" else min(v.dim, 2))
+
+        table = ([tuple(variables)] if joint else []) + [(v,) for v in variables] + extra
+        xcols, ycols, wrap, dims = [], [], [], []
+        for blk in table:
+            k = 0
+            for v in blk:
+                circ = v.circular_dim_list
+                for c in cols_of(v):
+                    xcols.append(pcol[v] + c); ycols.append(rcol[v] + c); wrap.append(bool(circ[c]))
+                    k += 1
+            dims.append(k)
+        xcols, ycols, wrap = np.asarray(xcols, dtype=np.int32), np.asarray(ycols, dtype=np.int32), np.asarray(wrap, dtype=np.uint8)
+        dims = np.asarray(dims)
+        if sigma is None:
+            sig = np.ones(len(table)) if estimator == "mmd" else np.sqrt(dims.astype(np.float64))
+        else:
+            sig = np.broadcast_to(np.asarray(sigma, dtype=np.float64).reshape(-1), (len(table),)) if np.size(sigma) == 1 else \
+                np.asarray(sigma, dtype=np.float64).reshape(-1)
+            if sig.size != len(table) or not np.all(np.isfinite(sig) & (sig > 0)):
+                raise ValueError("%s: sigma is one positive bandwidth, or one per block (%d)" % (what, len(table)))
+        scale = None
+        if standardise:
+            std = np.maximum(Y.astype(np.float64).std(axis=0), 1e-3)
+            scale = np.where(wrap != 0, 1.0, 1.0 / std[ycols])
+        flags = wrap if wrap.any() else None
+        blocks_np = _nh.pack_mmd_blocks(dims, sig)
+        _nh.check_mmd_blocks(blocks_np, xcols, ycols, pts.total_dim, width, scale, flags)
+        sums = _nh.mmd_sums_t(pts.St, _nh._columns(Y, pts.device), blocks_np, xcols, ycols, scale, flags, checked=True)
+        val = mmd_from_sums(sums.cpu().numpy(), rows, m, estimator)
+        k0 = 1 if joint else 0
+        marginal = {v: float(val[k0 + i]) for i, v in enumerate(variables)}
+        return dict(joint=float(val[0]) if joint else None, marginal=marginal,
+                    marginal_mean=float(np.mean(list(marginal.values()))),
+                    blocks=[float(x) for x in val[k0 + len(variables):]], floor=float(np.sqrt(1.0 / m + 1.0 / rows)),
+                    m=m, n=rows, estimator=estimator)
+
+    # ---- what posterior_summary and posterior_modes share: arguments, block table, the weights ------------------------------
+    def _summary_front(self, what, samples, n, variables, pairs, weights):
+        """The 'importance' spelling, the front, then the checks of the block arguments -> (pts, importance, variables, pairs)."""
+        importance = isinstance(weights, str)
+        if importance and weights != "importance":
+            raise ValueError("%s: weights is None, an [n] array or 'importance', got %r" % (what, weights))
+        pts = self._eval_points(what, samples, n, factors=importance, log_q=importance, nonempty=True)
+        known = set(self._elimination_ordering)
+        variables = list(self._elimination_ordering) if variables is None else list(variables)
+        pairs = [tuple(p) for p in pairs] if pairs is not None else []
+        if not variables:
+            raise ValueError("%s: no variable to summarise" % what)
+        for p in pairs:
+            if len(p) != 2:
+                raise ValueError("%s: a pair is a tuple (a, b) of two variables" % what)
+        for v in variables + [v for p in pairs for v in p]:
+            if v not in known:
+                raise ValueError("%s: variable %s is not in the elimination ordering" % (what, getattr(v, "name", v)))
+        for a, b in pairs:
+            if a.dim + b.dim > _nh.MOMENTS_MAX_D:
+                raise ValueError("%s: the pair (%s, %s) is %d columns wide; a block holds at most %d"
+                                 % (what, a.name, b.name, a.dim + b.dim, _nh.MOMENTS_MAX_D))
+        return pts, importance, variables, pairs
+
+    @staticmethod
+    def _summary_weights(what, weights, importance, rows):
+        """-> the checked [rows] float64 host weights (a device tensor is brought over); None without weights, for "importance"."""
+        if weights is None or importance:
+            return None
+        try:
+            return _nh._check_weights(weights.detach().cpu().numpy() if torch.is_tensor(weights) else weights, rows)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (what, e)) from None
+
+    @staticmethod
+    def _summary_table(variables, pairs, pcol):
+        """-> (table, cols, circ): every variable, then every pair; entry = one column of the sample matrix."""
+        table = [(v,) for v in variables] + pairs
+        cols, circ = [], []
+        for blk in table:
+            for v in blk:
+                cols.extend(pcol[v] + c for c in range(v.dim))
+                circ.extend(bool(c) for c in v.circular_dim_list)
+        return table, np.asarray(cols, dtype=np.int32), np.asarray(circ, dtype=np.uint8)
+
+    def _weights(self, what, pts: EvalPoints, importance, w_host):
+        """-> (weights: None, the host array or, for "importance", exp(log w - max) on the device; ess)."""
+        if importance:
+            log_p, log_q = self._log_p_q(pts)
+            log_w = log_p - log_q.to(torch.float64)
+            w_dev = torch.exp(log_w - log_w.max())
+            ess = float((w_dev.sum() ** 2 / (w_dev * w_dev).sum()).item())
+            if not np.isfinite(ess):
+                raise ValueError("%s: the importance weights are not finite" % what)
+            return w_dev, ess
+        if w_host is not None:
+            return w_host, float(w_host.sum() ** 2 / (w_host * w_host).sum())
+        return None, float(pts.rows)
+
+    # ---- what the posterior says: point estimates, spreads, intervals ---------------------------------------------
+    def posterior_summary(self, samples=None, n: int = None, variables=None, pairs=None, weights=None, quantiles=None,
+                          truth=None) -> dict:
+        """Means, covariances, heading concentrations and quantiles of the posterior, computed on the device from the sample
+        matrix the tree walk left there -- brought into the column-major layout the kernels read on the device, once, and
+        never copied to the host -- (nfisam_sample_moments / nfisam_sample_quantiles: float32 points, float64
+        arithmetic, every variable and pair in one call) -- what the reference does on the host with `sample_mean` and numpy
+        after copying the whole matrix out (src/utils/Statistics.py:142-214 and its run scripts).
+
+        samples=None draws `n` (default posterior_sample_num) points through the tree walk; otherwise `samples` is what
+        `posterior_log_pdf` accepts, nothing is drawn and no solver state is touched.  variables: which to summarise (default:
+        the elimination ordering).  pairs: (a, b) tuples, each summarised as ONE joint block of a.dim + b.dim <= 16 columns.
+        weights: None, an [n] array of non-negative weights, or "importance": the self-normalised importance weights
+        exp(log p - log q - max) of the same matrix (the log w of `posterior_diagnostics`), kept on the device.  quantiles: a
+        list of probabilities (not together with weights; n <= 16384).  truth: variable -> [dim] ground truth.
+        -> dict: mean (variable -> [dim]; a heading's is the circular mean in [-pi, pi)), cov (variable -> [dim, dim]: population
+        form; a heading's deviations are wrapped about its circular mean), resultant (variable -> mean resultant length of its
+        heading, for variables that have one), pair_cov ((a, b) -> matrix), quantiles (variable -> [n_probs, dim], None when not
+        asked for; a heading's are NOT wrapped back into [-pi, pi) so that an interval's ends stay ordered), n, ess
+        ((sum w)^2 / sum w^2; n without weights), and with `truth`, over the summarised variables that `truth` holds:
+        translation_rmse (utils.Statistics.translation_distance of the means), translation_error (variable -> its term, the
+        squared xy distance), geodesic (utils.Statistics.geodesic_distance).
+        Raises RuntimeError when there is nothing to summarise yet; ValueError for an unknown variable, a wrong width, ragged
+        rows, bad weights or probabilities, quantiles with weights or with more than 16384 points, a pair wider than 16 columns
+        -- before anything is launched."""
+        from utils import Statistics as ST
+        what = "posterior_summary"
+        pts, importance, variables, pairs = self._summary_front(what, samples, n, variables, pairs, weights)
+        rows = pts.rows
+        probs = None
+        if quantiles is not None:
+            if weights is not None:
+                raise ValueError("%s: quantiles are unweighted; ask for them without weights" % what)
+            probs = np.asarray(quantiles, dtype=np.float64).reshape(-1)
+            if probs.size < 1 or not np.all((probs >= 0.0) & (probs <= 1.0)):
+                raise ValueError("%s: quantiles is a non-empty list of probabilities in [0, 1]" % what)
+            if rows > _nh.QUANTILE_MAX_N:
+                raise ValueError("%s: quantiles take at most %d points, got %d" % (what, _nh.QUANTILE_MAX_N, rows))
+        w_host = self._summary_weights(what, weights, importance, rows)
+        graded = []
+        if truth is not None:
+            graded = [v for v in variables if v in truth]
+            if not graded:
+                raise ValueError("%s: truth holds none of the summarised variables" % what)
+            for v in graded:
+                if np.ndim(truth[v]) != 1 or len(truth[v]) != v.dim:
+                    raise ValueError("%s: truth of %s must be [%d], got shape %s" % (what, v.name, v.dim, np.shape(truth[v])))
+
+        # the table: every variable, then every pair; entry = one column of the sample matrix
+        table, cols, circ = self._summary_table(variables, pairs, pts.pcol)
+        blocks = _nh.pack_moment_blocks([sum(v.dim for v in blk) for blk in table])
+        _nh.check_moment_blocks(blocks, cols, pts.total_dim, circ)
+        flags = circ if circ.any() else None
+        w_dev, ess = self._weights(what, pts, importance, w_host)
+        mean_d, res_d, cov_d = _nh.sample_moments_t(pts.St, blocks, cols, flags, w_dev, checked=True)
+        q = None
+        if probs is not None:
+            nq = sum(v.dim for v in variables)
+            q = _nh.sample_quantiles_t(pts.St, cols[:nq], probs, None if flags is None else circ[:nq], mean_d[:nq], checked=True)
+            q = q.cpu().numpy()
+        mean, res, cov = mean_d.cpu().numpy(), res_d.cpu().numpy(), cov_d.cpu().numpy()
+        out = dict(mean={}, cov={}, resultant={}, pair_cov={}, quantiles=None if q is None else {}, n=rows, ess=ess)
+        for blk, row in zip(table, blocks):
+            o, d, c = int(row["col_off"]), int(row["d"]), int(row["cov_off"])
+            m = cov[c:c + d * d].reshape(d, d).copy()
+            if len(blk) == 2:
+                out["pair_cov"][blk] = m
+                continue
+            v = blk[0]
+            out["mean"][v], out["cov"][v] = mean[o:o + d].copy(), m
+            heading = [k for k, f in enumerate(v.circular_dim_list) if f]
+            if heading:
+                out["resultant"][v] = float(res[o + heading[0]]) if len(heading) == 1 else res[o:o + d][heading].copy()
+            if q is not None:
+                out["quantiles"][v] = q[o:o + d].T.copy()
+        if truth is not None:
+            est = {v: out["mean"][v] for v in graded}
+            ref = {v: np.asarray(truth[v], dtype=np.float64) for v in graded}
+            out["translation_rmse"] = float(ST.translation_distance(est, ref))
+            out["translation_error"] = {v: float(e) for v, e in ST.translation_terms(est, ref).items()}
+            out["geodesic"] = float(ST.geodesic_distance(est, ref))
+        return out
+
+    # ---- which hypotheses the posterior holds: modes, their masses, who belongs to which -----------------------------
+    def posterior_modes(self, samples=None, n: int = None, variables=None, pairs=None, weights=None, sigma=None, tol=1e-7,
+                        merge=1e-2, max_iters=500, max_modes=16) -> dict:
+        """The modes of every variable's marginal posterior, found on the device from the sample matrix the tree walk left
+        there (nfisam_sample_modes: from every sample a mean-shift ascent on the Gaussian kernel density estimate of the
+        variable's own samples, then a deterministic merge of the converged points; float32 points, float64 arithmetic, every
+        variable and pair in one call).  Where `posterior_summary` reports one mean between the hypotheses of a bimodal
+        variable, this reports each hypothesis, its mass and its members.
+
+        samples, n, variables, pairs and weights are those of `posterior_summary` (a pair (a, b) is ONE joint block of
+        a.dim + b.dim <= 16 columns; weights: None, an [n] array or "importance").  Columns are standardised by their
+        (weighted) spread -- the circular standard deviation for a heading, whose differences are wrapped: a mode may sit across
+        the +-pi seam -- and a column without spread is ignored.  sigma: one bandwidth or one per block (variables, then pairs)
+        in those units; None: Scott's rule ess^(-1 / (dim + 4)).  tol, merge: in sigmas; max_modes <= 32.
+        Every bump of the density estimate is a mode: with Scott's rule a near-Gaussian marginal of some hundred samples has
+        small ones in its tails, and ascents there can run into max_iters.  Read `mass` before counting hypotheses and
+        `not_converged` before trusting a position; a larger `sigma` smooths the bumps away.
+        -> dict: modes (variable -> list of {position [dim], mass, density}, by falling density), pair_modes ((a, b) -> list),
+        labels (variable -> device int32 [n]: the mode of every sample, -1 for one left over when max_modes was reached), n,
+        ess, sigma (variable or pair -> the bandwidth used), not_converged (variable or pair -> ascents that stopped on
+        max_iters), unlabelled (variable or pair -> count).
+        It changes no solver state and draws random numbers only when `samples` is None.  Raises what `posterior_summary`
+        raises, and ValueError for a bad sigma, tol, merge, max_iters or max_modes -- before anything is launched."""
+        from utils import Statistics as ST
+        what = "posterior_modes"
+        pts, importance, variables, pairs = self._summary_front(what, samples, n, variables, pairs, weights)
+        try:
+            sigma, _ = ST.check_mode_options(len(variables) + len(pairs), 1, sigma, None, tol, merge, max_iters, max_modes)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (what, e)) from None
+        w_host = self._summary_weights(what, weights, importance, pts.rows)
+        table, cols, circ = self._summary_table(variables, pairs, pts.pcol)
+        w_dev, ess = self._weights(what, pts, importance, w_host)
+        flags = np.zeros(pts.total_dim, dtype=bool)
+        flags[cols] = circ != 0
+        blocks, at = [], 0
+        for blk in table:
+            d = sum(v.dim for v in blk)
+            blocks.append(cols[at:at + d])
+            at += d
+        res = ST.sample_modes_t(pts.St, blocks, circular=flags, weights=w_dev, sigma=sigma, tol=tol, merge=merge,
+                                max_iters=max_iters, max_modes=max_modes, checked=True)
+        out = dict(modes={}, pair_modes={}, labels={}, n=pts.rows, ess=ess, sigma={}, not_converged={}, unlabelled={})
+        for b, blk in enumerate(table):
+            key = blk if len(blk) == 2 else blk[0]
+            out["pair_modes" if len(blk) == 2 else "modes"][key] = res["modes"][b]
+            if len(blk) == 1:
+                out["labels"][key] = res["labels"][b]
+            out["sigma"][key] = float(res["sigma"][b])
+            out["not_converged"][key] = int(res["iterations"]["not_converged"][b])
+            out["unlabelled"][key] = int(res["unlabelled"][b])
+        return out

@@ -321,7 +321,8 @@ def _fake_graph_solver(monkeypatch):
     s.update_physical_and_working_graphs()
     assert len(s.physical_factors) == 2
     refuse = _Refuse()
-    for name in ("factor_graph_log_density", "factor_graph_log_density_t", "posterior_log_density", "upload"):
+    for name in ("factor_graph_log_density", "factor_graph_log_density_t", "posterior_log_density", "posterior_log_density_t",
+                 "upload"):
         monkeypatch.setattr(nh, name, refuse)
     return s, X0, L1, refuse
 

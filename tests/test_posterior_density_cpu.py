@@ -82,6 +82,7 @@ def _fake_tree_solver(monkeypatch):
     s._elimination_ordering = [X0, L1]
     refuse = _Refuse()
     monkeypatch.setattr(nh, "posterior_log_density", refuse)
+    monkeypatch.setattr(nh, "posterior_log_density_t", refuse)
     monkeypatch.setattr(NFiSAM, "_posterior_table", refuse)
     return s, X0, L1, refuse
 

@@ -157,6 +157,26 @@ def test_latent_round_trip_with_the_walk(L, H):
     assert np.all(np.isfinite(lq.cpu().numpy()))
 
 
+def test_column_major_form_gives_the_row_major_bits():
+    """`posterior_log_density_t(St)` is `posterior_log_density(S)` without the transpose: equal bits at one point and either
+    side of a wave of 64, with and without the per-clique terms."""
+    L, H, K = 1, 8, 9
+    rng = np.random.RandomState(11)
+    total, angle, specs, entries, host = _tree(L, K, H, rng)
+    table, cols, obs, max_D = _table(entries)
+    for n in (1, 63, 65):
+        S = dev(rng.randn(n, total))
+        St = S.t().contiguous()
+        for per_clique in (False, True):
+            row = nh.posterior_log_density(table, cols, obs, S, max_D, K, H, B, L, DEV, per_clique=per_clique)
+            col = nh.posterior_log_density_t(table, cols, obs, St, max_D, K, H, B, L, DEV, per_clique=per_clique)
+            if per_clique:
+                assert row[2] is None and col[2] is None and col[1].shape == (len(entries), n)
+                assert torch.equal(row[1], col[1])
+                row, col = row[0], col[0]
+            assert col.shape == (n,) and torch.equal(row, col) and bool(torch.isfinite(col).all()), (n, per_clique)
+
+
 def _solve(steps, **kw):
     from slam.NFiSAM import NFiSAM, NFiSAMArgs
     args = dict(num_knots=9, hidden_dim=8, flow_iterations=2000, local_sample_num=2000, learning_rate=0.015,

@@ -211,7 +211,7 @@ def _fake_graph_solver(monkeypatch):
     s.add_factor(F.SE2R2RangeGaussianLikelihoodFactor(X0, L1, 3.0, 0.5))
     s.update_physical_and_working_graphs()
     refuse = Refuse()
-    for name in ("mmd_sums", "mmd_sums_t", "posterior_walk_raw", "upload"):
+    for name in ("mmd_sums", "mmd_sums_t", "_columns", "posterior_walk_raw", "upload"):
         monkeypatch.setattr(nh, name, refuse)
     return s, X0, L1, refuse
 

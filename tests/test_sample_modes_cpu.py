@@ -427,7 +427,7 @@ def test_posterior_modes_errors_come_before_any_launch(monkeypatch):
     s.update_physical_and_working_graphs()
     refuse = Refuse()
     for name in ("sample_moments", "sample_moments_t", "sample_modes", "sample_modes_t", "posterior_walk_raw", "upload",
-                 "posterior_log_density", "factor_graph_log_density"):
+                 "posterior_log_density", "posterior_log_density_t", "factor_graph_log_density", "factor_graph_log_density_t"):
         monkeypatch.setattr(nh, name, refuse)
     X9 = SE2Variable("X9")
     own = {X0: np.zeros((7, 3)), L1: np.zeros((7, 2))}

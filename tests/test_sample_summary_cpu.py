@@ -236,7 +236,7 @@ def _fake_graph_solver(monkeypatch):
     s.update_physical_and_working_graphs()
     refuse = Refuse()
     for name in ("sample_moments", "sample_moments_t", "sample_quantiles", "sample_quantiles_t", "posterior_walk_raw", "upload",
-                 "posterior_log_density", "factor_graph_log_density"):
+                 "posterior_log_density", "posterior_log_density_t", "factor_graph_log_density", "factor_graph_log_density_t"):
         monkeypatch.setattr(nh, name, refuse)
     return s, X0, L1, refuse
 
