@@ -336,6 +336,48 @@ size_t nfisam_sample_ksd_scratch_count(int n);                          /* 0 for
 int nfisam_sample_ksd(const float* Xt, const double* Gt, int rows, int n, const double* precision, const uint8_t* wrap,
                       double* row, double* diag, double* H, double* scratch, nfisam_stream_t stream);
 
+/* ---- Stein variational direction and step: posterior samples moved along the joint score (sample_svgd.hip) --------------------
+ * phi(x_i) = 1/n sum_j [ k(x_j, x_i) grad log p(x_j) + grad_{x_j} k(x_j, x_i) ] (Liu & Wang 2016; not in the reference), per
+ * block of the nfisam_mmd_block table: block b owns the entries col_off .. col_off + d of `cols`, entry e names row cols[e] of Xt
+ * and of Gt, and its kernel sees the block's own columns only.  With d_ij,e = x_i - x_j in row cols[e], brought into [-pi, pi] as
+ * sign(d) wrap(|d|) where wrap[e] is set (d_ji = -d_ij to the bit):
+ *     k_b(i, j) = exp(-inv_two_sigma2 sum_e (scale_e d_ij,e)^2)
+ *     phi[e][i] = ( sum_j k_b(i, j) ( Gt[cols[e]][j] + 2 inv_two_sigma2 scale_e^2 d_ij,e ) ) / n
+ * An entry with scale_e = 0 leaves the kernel and still gets its sum_j k g / n; d has no upper limit.
+ *   Xt[x_rows][n]: COLUMN-major float32 device matrix; Gt[x_rows][n]: COLUMN-major float64 device matrix (what
+ *   nfisam_factor_graph_score writes); blocks[n_blocks]: HOST copy of the table (validated here), blocks_dev: DEVICE copy (what
+ *   the kernels read); cols [n_entries] int32, scale [n_entries] double (nullable: 1), wrap [n_entries] uint8 (nullable): DEVICE
+ *   arrays; phi[n_entries][n] double, ENTRY-major: blocks own disjoint entries, so no two blocks write one address; an entry
+ *   that no block owns is left as it was; scratch: nfisam_sample_svgd_scratch_count(n, n_blocks, n_entries) doubles on the device.
+ * Float32 points in; float64 differences, products, exp and sums; direct differences.  Two launches, no float atomics: a
+ * 256-thread group per (64 x 64 tile of pairs, block) walks the block's columns twice in chunks of 16 -- the squared distances and
+ * the 64 x 64 kernel values, then per column the sums over the tile's j -- and writes one partial per (tile of j, entry, i); then
+ * phi[e][i] adds them in tile order and divides by n.  Two calls give the same bits, and a block's rows are the same bits alone or
+ * among hundreds, wherever it stands in the table; swapping the two points of a two-point set swaps their phi bit for bit.
+ * NFISAM_ERR_ARG: a NULL pointer (scale and wrap excepted), x_rows, n, n_entries or n_blocks < 1, a block with d < 1 or
+ * inv_two_sigma2 not positive and finite, two blocks that share an entry, more than 65535 blocks, n > 65535 * 64.  The device
+ * arrays are not read on the host: a block whose entries leave [0, n_entries) or that names a row outside the matrix yields NaN
+ * for its entries (nothing is read or written out of bounds); the Python binding refuses such tables before upload.
+ *
+ * nfisam_sample_step applies phi to the points in place, the AdaGrad-with-decay rule of the original SVGD code, in float64 per
+ * (entry e, point i):
+ *     hist = first ? phi^2 : alpha hist + (1 - alpha) phi^2
+ *     y    = (double)Xt[cols[e]][i] + eps[e] phi / (sqrt(hist) + fudge)
+ *     Xt[cols[e]][i] = (float)(wrap[e] ? wrap_pi(y) : y)          (wrap_pi: into [-pi, pi), the sign convention of theta_to_pipi)
+ *   eps[n_entries] double: DEVICE array, one step length per entry in the column's own unit; hist[n_entries][n] double: the
+ *   caller's state, read unless `first`, always written; phi as nfisam_sample_svgd writes it (or any direction of that layout).
+ * The points stay float32: a step smaller than the float32 spacing of a coordinate is lost (7.6e-6 at 100 m).  A wrapped value
+ * that rounds to +-float32(pi), outside [-pi, pi), becomes the float32 just inside -pi.  One launch, elementwise: the same bits
+ * on every call.  A row of Xt named by two entries would be written twice: the Python binding refuses it.
+ * NFISAM_ERR_ARG: a NULL pointer (wrap excepted), x_rows, n or n_entries < 1, n_entries > 65535, alpha outside [0, 1), fudge not
+ * positive and finite.  An entry whose row lies outside the matrix moves nothing and gets NaN in hist.  (Additive: ABI 1600.) */
+size_t nfisam_sample_svgd_scratch_count(int n, int n_blocks, int n_entries);   /* 0 for arguments the entry refuses */
+int nfisam_sample_svgd(const float* Xt, int x_rows, int n, const double* Gt, const nfisam_mmd_block* blocks,
+                       const nfisam_mmd_block* blocks_dev, int n_blocks, const int32_t* cols, int n_entries, const double* scale,
+                       const uint8_t* wrap, double* phi, double* scratch, nfisam_stream_t stream);
+int nfisam_sample_step(float* Xt, int x_rows, int n, const int32_t* cols, int n_entries, const uint8_t* wrap, const double* phi,
+                       double* hist, const double* eps, double alpha, double fudge, int first, nfisam_stream_t stream);
+
 /* ---- sample summaries: means, resultant lengths, covariances and quantiles of many column blocks (sample_summary.hip) -------
  * The reference summarises a draw on the host: `sample_mean` (src/utils/Statistics.py:151-171: np.mean, and scipy's
  * circmean(high = pi, low = -pi) for headings) and, built on it, `rmse` (:142-148), `geodesic_distance` (:179-191) and

@@ -33,6 +33,7 @@ EXPORTS = [
     "nfisam_sample_modes", "nfisam_sample_modes_merge",
     "nfisam_factor_graph_score", "nfisam_factor_graph_score_scratch_count",
     "nfisam_sample_ksd", "nfisam_sample_ksd_scratch_count",
+    "nfisam_sample_svgd", "nfisam_sample_svgd_scratch_count", "nfisam_sample_step",
 ]
 
 
@@ -120,6 +121,7 @@ def lib():
         _lib.nfisam_sample_mmd_scratch_count.restype = C.c_size_t
         _lib.nfisam_factor_graph_score_scratch_count.restype = C.c_size_t
         _lib.nfisam_sample_ksd_scratch_count.restype = C.c_size_t
+        _lib.nfisam_sample_svgd_scratch_count.restype = C.c_size_t
         for name in EXPORTS:
             getattr(_lib, name)   # raises AttributeError if the ABI is incomplete
     return _lib
@@ -1005,6 +1007,26 @@ def _check_rows(cols):
                              % (name, int(rows), "the" if len(cols) == 1 else "its"))
 
 
+def _check_disjoint(off, d, why):
+    """No two blocks of (col_off, d) share an entry: for results that are stored by entry (`why` says which)."""
+    order = np.argsort(off, kind="stable")
+    clash = (off[order][1:] < (off + d)[order][:-1])
+    if np.any(clash):
+        raise ValueError("blocks %d and %d share an entry: %s"
+                         % (int(order[:-1][np.argmax(clash)]), int(order[1:][np.argmax(clash)]), why))
+
+
+def _score_front(name, Gt, Xt):
+    """The head of a binding that reads a score matrix next to the points `Xt`: `Gt` must be a contiguous float64
+    [rows, points] tensor on Xt's ROCm device (its shape is the caller's check)."""
+    if not torch.is_tensor(Gt) or not Gt.is_cuda:
+        raise RuntimeError("%s must be a tensor on a ROCm device (no CPU path exists)" % name)
+    if Gt.ndim != 2 or Gt.dtype != torch.float64 or not Gt.is_contiguous():
+        raise ValueError("%s must be a contiguous float64 [rows, points] tensor" % name)
+    if Gt.device != Xt.device:
+        raise ValueError("Xt and %s must be on the same device" % name)
+
+
 # ---- two-sample MMD: the kernel sums of many column blocks in one launch (nfisam_sample_mmd) ------------------------------------
 MMD_BLOCK_DTYPE = np.dtype([("col_off", np.int32), ("d", np.int32), ("inv_two_sigma2", np.float64)])
 assert MMD_BLOCK_DTYPE.itemsize == C.sizeof(MmdBlock)
@@ -1179,12 +1201,7 @@ def ksd_sums_t(Xt, Gt, precision, wrap=None, matrix=False, checked=False):
     """`ksd_sums` on the COLUMN-major matrices Xt [D, n] (contiguous float32) and Gt [D, n] (contiguous float64) on one
     ROCm device, used in place: the tree walk's St and `factor_graph_score_t`'s result."""
     rows, n = _column_major_front("Xt", Xt)
-    if not torch.is_tensor(Gt) or not Gt.is_cuda:
-        raise RuntimeError("Gt must be a tensor on a ROCm device (no CPU path exists)")
-    if Gt.ndim != 2 or Gt.dtype != torch.float64 or not Gt.is_contiguous():
-        raise ValueError("Gt must be a contiguous float64 [rows, points] tensor")
-    if Gt.device != Xt.device:
-        raise ValueError("Xt and Gt must be on the same device")
+    _score_front("Gt", Gt, Xt)
     if not checked:
         check_ksd_args(rows, n, tuple(Gt.shape), precision, wrap, matrix)
     device = Xt.device
@@ -1200,6 +1217,130 @@ def ksd_sums_t(Xt, Gt, precision, wrap=None, matrix=False, checked=False):
         _check(lib().nfisam_sample_ksd(_ptr(Xt), _ptr(Gt), rows, n, _ptr(dev["precision"]), _ptr(dev["wrap"]), _ptr(row),
                                        _ptr(diag), _ptr(H), _ptr(scratch), _stream()), "nfisam_sample_ksd")
     return dict(row=row, diag=diag, H=H)
+
+
+# ---- Stein variational direction and step: the samples moved along the score (nfisam_sample_svgd, nfisam_sample_step) ----------
+def check_svgd_blocks(blocks: np.ndarray, cols, x_rows: int, scale=None, wrap=None) -> None:
+    """ValueError for tables the kernels must not see: what `check_mmd_blocks` refuses (no block or more than 65535, d < 1, a
+    bandwidth term that is not positive and finite, entries outside [0, n_entries), a row outside [0, x_rows), per-entry arrays
+    of another length, a scale that is not finite), two blocks that share an entry, and a row of Xt named more than once: a
+    column has one direction.  (A device tensor's length alone is checked: checking its values would read it back.)"""
+    named = {"cols": (cols, x_rows)}
+    off, d = _check_table_layout(blocks, MMD_BLOCK_DTYPE, "MMD_BLOCK_DTYPE", named, dict(scale=scale, wrap=wrap))
+    _check_disjoint(off, d, "the direction is stored by entry")
+    _check_bandwidths(blocks)
+    _check_rows(named)
+    c = np.asarray(cols)
+    if np.unique(c).size != c.size:
+        raise ValueError("cols: a row of Xt is named more than once: a column has one direction")
+    if scale is not None and not (torch.is_tensor(scale) and scale.is_cuda) and \
+            not np.all(np.isfinite(np.asarray(scale, dtype=np.float64))):
+        raise ValueError("scale must be finite")
+
+
+def svgd_tables(device, blocks: np.ndarray, cols, scale=None, wrap=None, eps=None) -> dict:
+    """The tables of `svgd_direction_t` / `sample_step_t` on `device`, one upload, to reuse over the steps of a loop:
+    {"host": the contiguous block table, "blocks", "cols", "scale", "wrap", "eps": device tensors or None, "n_entries"}."""
+    blocks = np.ascontiguousarray(blocks)
+    c = np.asarray(cols, dtype=np.int32)
+    dev = _upload_named(device, blocks=_table_bytes(blocks), cols=c, scale=_entry_f64(scale), wrap=_flags(wrap),
+                        eps=_entry_f64(eps))
+    return dict(dev, host=blocks, n_entries=int(c.size))
+
+
+def svgd_direction(X, G, blocks: np.ndarray, cols, scale=None, wrap=None, device=None):
+    """The Stein variational direction of the points X [n, x_cols] (tensor or numpy; float32 points) with scores G [n, x_cols]
+    (float64) for every block of `blocks` (nfisam_sample_svgd, on the current stream): `blocks` numpy MMD_BLOCK_DTYPE
+    (`pack_mmd_blocks`: widths and bandwidths; no two blocks share an entry), entry e is column cols[e] of X and of G (no
+    column twice); scale [n_entries] multiplies an entry's differences in the kernel (0: the column leaves it and still gets
+    its kernel-weighted mean score), wrap [n_entries] marks angles (differences brought into [-pi, pi]).
+    -> Phi [n_entries, n] float64 device tensor:
+    Phi[e, i] = sum_j k_b(i, j) (G[j, cols[e]] + 2 inv_two_sigma2 scale_e^2 (x_i - x_j)_e) / n."""
+    device = _row_major_front("svgd_direction", device, X=X, G=G)
+    if tuple(G.shape) != tuple(X.shape):
+        raise ValueError("the score matrix must have the shape of the points: %s, got %s" % (tuple(X.shape), tuple(G.shape)))
+    if int(X.shape[0]) < 1:
+        raise ValueError("svgd_direction: no points")
+    check_svgd_blocks(blocks, cols, int(X.shape[1]), scale, wrap)
+    Gt = G.to(device=device, dtype=torch.float64).t().contiguous() if torch.is_tensor(G) else \
+        torch.from_numpy(np.ascontiguousarray(np.asarray(G, dtype=np.float64).T)).to(device)
+    return svgd_direction_t(_columns(X, device), Gt, blocks, cols, scale, wrap, checked=True)
+
+
+def svgd_direction_t(Xt, Gt, blocks: np.ndarray, cols, scale=None, wrap=None, checked=False, tables=None):
+    """`svgd_direction` on the COLUMN-major matrices Xt [x_rows, n] (contiguous float32) and Gt [x_rows, n] (contiguous
+    float64) on one ROCm device, used in place: the tree walk's St and `factor_graph_score_t`'s result.  `tables`: the result
+    of `svgd_tables` for the same arguments, to reuse over the steps of a loop."""
+    x_rows, n = _column_major_front("Xt", Xt)
+    _score_front("Gt", Gt, Xt)
+    if tuple(Gt.shape) != (x_rows, n):
+        raise ValueError("the score matrix must have the shape of the points: %s, got %s" % ((x_rows, n), tuple(Gt.shape)))
+    if n < 1:
+        raise ValueError("svgd_direction: no points")
+    if not checked:
+        check_svgd_blocks(blocks, cols, x_rows, scale, wrap)
+    device = Xt.device
+    with torch.cuda.device(device):
+        t = tables if tables is not None else svgd_tables(device, blocks, cols, scale, wrap)
+        nb, ne = int(t["host"].shape[0]), t["n_entries"]
+        count = int(lib().nfisam_sample_svgd_scratch_count(n, nb, ne))
+        if count < 1:
+            raise ValueError("svgd_direction: %d points in %d blocks exceed the grid" % (n, nb))
+        scratch = torch.empty(count, dtype=torch.float64, device=device)       # the per-tile partials: torch's allocator
+        Phi = torch.zeros(ne, n, dtype=torch.float64, device=device)           # (an entry no block owns keeps its zero)
+        _check(lib().nfisam_sample_svgd(_ptr(Xt), x_rows, n, _ptr(Gt), t["host"].ctypes.data_as(C.c_void_p), _ptr(t["blocks"]),
+                                        nb, _ptr(t["cols"]), ne, _ptr(t["scale"]), _ptr(t["wrap"]), _ptr(Phi), _ptr(scratch),
+                                        _stream()), "nfisam_sample_svgd")
+    return Phi
+
+
+def check_step_args(alpha, fudge, eps=None) -> None:
+    """ValueError for what nfisam_sample_step refuses (alpha outside [0, 1), a fudge that is not positive and finite) and for
+    host step lengths that are not finite."""
+    if not (np.isfinite(alpha) and 0.0 <= alpha < 1.0):
+        raise ValueError("alpha must lie in [0, 1), got %r" % (alpha,))
+    if not (np.isfinite(fudge) and fudge > 0):
+        raise ValueError("fudge must be positive and finite, got %r" % (fudge,))
+    if eps is not None and not (torch.is_tensor(eps) and eps.is_cuda) and not np.all(np.isfinite(np.asarray(eps, dtype=np.float64))):
+        raise ValueError("eps must be finite")
+
+
+def sample_step_t(Xt, cols, Phi, hist, eps, wrap=None, alpha=0.9, fudge=1e-6, first=False, checked=False, tables=None):
+    """One step of the points Xt [x_rows, n] (contiguous float32 device matrix) along the direction Phi [n_entries, n]
+    (float64, as `svgd_direction_t` returns it), IN PLACE (nfisam_sample_step, on the current stream):
+        hist = phi^2 if first else alpha hist + (1 - alpha) phi^2;  x += eps[e] phi / (sqrt(hist) + fudge)
+    in float64, rounded to float32, entry e being row cols[e] of Xt (no row twice); wrap [n_entries] marks angles, which are
+    brought back into [-pi, pi).  hist [n_entries, n] float64: the caller's state, updated in place; eps [n_entries]: one step
+    length per entry in the column's own unit.  A step below the float32 spacing of a coordinate is lost (7.6e-6 at 100 m).
+    `tables`: the result of `svgd_tables(..., eps=eps)` to reuse.  -> None."""
+    x_rows, n = _column_major_front("Xt", Xt)
+    ne = int(tables["n_entries"]) if tables is not None else int(np.size(cols))
+    for name, t in (("Phi", Phi), ("hist", hist)):
+        _score_front(name, t, Xt)
+        if tuple(t.shape) != (ne, n):
+            raise ValueError("%s must be [n_entries, n] = %s, got %s" % (name, (ne, n), tuple(t.shape)))
+    if n < 1 or ne < 1:
+        raise ValueError("sample_step: no points or no entries")
+    if not checked:
+        c = np.asarray(cols)
+        if c.ndim != 1:
+            raise ValueError("cols must be a 1-D list of at least one row")
+        _check_rows({"cols": (c, x_rows)})
+        if np.unique(c).size != c.size:
+            raise ValueError("cols: a row of Xt is named more than once: a column has one direction")
+        for name, a in (("eps", eps), ("wrap", wrap)):
+            if a is not None and (tuple(a.shape) if torch.is_tensor(a) else np.shape(a)) != (ne,):
+                raise ValueError("%s must have one %s per entry (%d)" % (name, "flag" if name == "wrap" else "value", ne))
+        if eps is None:
+            raise ValueError("eps must have one value per entry (%d)" % ne)
+        check_step_args(alpha, fudge, eps)
+    device = Xt.device
+    with torch.cuda.device(device):
+        t = tables if tables is not None else _upload_named(device, cols=np.asarray(cols, dtype=np.int32), wrap=_flags(wrap),
+                                                            eps=_entry_f64(eps))
+        _check(lib().nfisam_sample_step(_ptr(Xt), x_rows, n, _ptr(t["cols"]), ne, _ptr(t["wrap"]), _ptr(Phi), _ptr(hist),
+                                        _ptr(t["eps"]), C.c_double(float(alpha)), C.c_double(float(fudge)), C.c_int(int(bool(first))),
+                                        _stream()), "nfisam_sample_step")
 
 
 # ---- sample summaries: means, resultant lengths, covariances, quantiles (nfisam_sample_moments, nfisam_sample_quantiles) --------
@@ -1364,11 +1505,7 @@ def check_mode_blocks(blocks: np.ndarray, cols, x_rows: int, scale=None, wrap=No
     negative or not finite (a device tensor's length alone is checked: checking its values would read it back)."""
     cols = {"cols": (cols, x_rows)}
     off, d = _check_table_layout(blocks, MMD_BLOCK_DTYPE, "MMD_BLOCK_DTYPE", cols, dict(scale=scale, wrap=wrap), MODES_MAX_D)
-    order = np.argsort(off, kind="stable")
-    clash = (off[order][1:] < (off + d)[order][:-1])
-    if np.any(clash):
-        raise ValueError("blocks %d and %d share an entry: the converged points are stored by entry (list the column twice)"
-                         % (int(order[:-1][np.argmax(clash)]), int(order[1:][np.argmax(clash)])))
+    _check_disjoint(off, d, "the converged points are stored by entry (list the column twice)")
     _check_bandwidths(blocks)
     _check_rows(cols)
     if scale is not None and not (torch.is_tensor(scale) and scale.is_cuda):     # (a device tensor is taken as it is)

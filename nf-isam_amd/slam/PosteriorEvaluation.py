@@ -1,6 +1,7 @@
 """slam.PosteriorEvaluation -- what a trained NFiSAM solver says about its posterior, not in the reference: densities
 (`posterior_log_pdf`, `joint_log_pdf`, `joint_score`), the solver grading itself (`posterior_diagnostics`, `map_estimate`,
-`posterior_ksd`, `posterior_mmd`) and what the posterior holds (`posterior_summary`, `posterior_modes`).
+`posterior_ksd`, `posterior_mmd`), what the posterior holds (`posterior_summary`, `posterior_modes`) and its samples moved
+along the joint score (`posterior_refine`, `map_refine`).
 
 A mixin of `slam.NFiSAM.NFiSAM`: the walk (`posterior_launch`, `_post_columns`, `_posterior_table`) and the solver's state
 are reached through `self`.  Every public method goes through ONE front, `_eval_points`, which makes the checks that need no
@@ -62,6 +63,12 @@ class EvalPoints:
                 St = torch.from_numpy(host).to(self.device)
             self._St = St
         return self._St
+
+    def over(self, St):
+        """The same record over another matrix of the same layout (a copy to refine, a selection of its points)."""
+        other = EvalPoints(self._solver, self.values, int(St.shape[1]), self.pcol, self.total_dim, self.table)
+        other._device, other._St = self.device, St
+        return other
 
 
 class PosteriorEvaluation:
@@ -249,6 +256,32 @@ class PosteriorEvaluation:
         estimate (FactorGraphSolver.plot2d_MAP_rbt_only, src/slam/FactorGraphSolver.py:660-671).  -> variable -> [dim]."""
         return self.posterior_diagnostics(samples)["map_sample"]
 
+    # ---- what posterior_ksd, posterior_refine and map_refine share: the columns in use, their flags and spreads ----------------
+    def _column_flags(self, pts: EvalPoints):
+        """-> (flags [total_dim] bool: the heading columns, from the variables; cols: the columns the ordering's variables
+        take, ascending).  No device."""
+        flags, used = np.zeros(pts.total_dim, dtype=bool), np.zeros(pts.total_dim, dtype=bool)
+        for v in self._elimination_ordering:
+            flags[pts.pcol[v]:pts.pcol[v] + v.dim] = [bool(c) for c in v.circular_dim_list]
+            used[pts.pcol[v]:pts.pcol[v] + v.dim] = True
+        return flags, np.flatnonzero(used)
+
+    @staticmethod
+    def _column_scale(pts: EvalPoints, flags, cols, standardise: bool):
+        """-> scale [total_dim]: with `standardise` 1 / spread of every column of `cols` over the points of `pts`
+        (`sample_moments_t` + `Statistics.mode_scale`: the circular spread for a heading, 0 for a column without spread), else
+        1; 0 in the columns no variable takes."""
+        from utils import Statistics as ST
+        scale = np.zeros(pts.total_dim)
+        if standardise:
+            circ = flags[cols].astype(np.uint8)
+            mean, res, cov = _nh.sample_moments_t(pts.St, _nh.pack_moment_blocks(np.ones(cols.size, dtype=np.int64)), cols,
+                                                  circ if circ.any() else None, None, checked=True)
+            scale[cols] = ST.mode_scale(cov.cpu().numpy(), res.cpu().numpy(), flags[cols])
+        else:
+            scale[cols] = 1.0
+        return scale
+
     # ---- the solver graded against the factor graph itself: score and kernel Stein discrepancy -------------------------
     def joint_score(self, samples) -> np.ndarray:
         """The score grad_x log p(X, Z) of the measurement factors at n points: the reference's JointFactor.grad_x_log_pdf
@@ -288,19 +321,8 @@ class PosteriorEvaluation:
         if sigma is not None and not (np.isfinite(sigma) and sigma > 0):
             raise ValueError("%s: sigma must be positive and finite" % what)
         order = list(self._elimination_ordering)
-        flags, used = np.zeros(total_dim, dtype=bool), np.zeros(total_dim, dtype=bool)
-        for v in order:
-            flags[pcol[v]:pcol[v] + v.dim] = [bool(c) for c in v.circular_dim_list]
-            used[pcol[v]:pcol[v] + v.dim] = True
-        cols = np.flatnonzero(used)
-        scale = np.zeros(total_dim)
-        if standardise:
-            circ = flags[cols].astype(np.uint8)
-            mean, res, cov = _nh.sample_moments_t(pts.St, _nh.pack_moment_blocks(np.ones(cols.size, dtype=np.int64)), cols,
-                                                  circ if circ.any() else None, None, checked=True)
-            scale[cols] = ST.mode_scale(cov.cpu().numpy(), res.cpu().numpy(), flags[cols])
-        else:
-            scale[cols] = 1.0
+        flags, cols = self._column_flags(pts)
+        scale = self._column_scale(pts, flags, cols, standardise)
         sig = float(np.sqrt(cols.size)) if sigma is None else float(sigma)
         precision = scale * scale / (sig * sig)
         Gt = self._score_launch(pts)
@@ -315,6 +337,128 @@ class PosteriorEvaluation:
             out["bootstrap"] = ST.ksd_bootstrap(sums["H"], draws)
             out["p_value"] = float(np.mean(out["bootstrap"] >= u))
         return out
+
+    # ---- the samples moved along the joint score: Stein variational refinement and a MAP ascent ----------------------------------
+    def _refine_front(self, what, samples, n, steps, step_size, standardise, blocks_of, sigma=None):
+        """What posterior_refine and map_refine share: the front, every option check (no device; `blocks_of(pts, cols)` makes
+        the method's own and returns its column blocks), then the spreads of the starting points
+        -> (pts, flags, cols, blocks, scale [total_dim], step [total_dim]).  A column's step is `step_size`
+        times its spread with `standardise` (`step_size` itself for a column without spread), else `step_size`."""
+        from utils import Statistics as ST
+        pts = self._eval_points(what, samples, n, factors=True, nonempty=True)
+        flags, cols = self._column_flags(pts)
+        blocks = blocks_of(pts, cols)
+        try:
+            if np.ndim(step_size) != 0:
+                raise ValueError("step_size is one positive finite step")
+            ST.check_refine_options(pts.total_dim, blocks, sigma, None, flags, steps, step_size)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (what, e)) from None
+        scale = self._column_scale(pts, flags, cols, bool(standardise))
+        step = np.full(pts.total_dim, float(step_size))
+        if standardise:
+            step[scale > 0] = float(step_size) / scale[scale > 0]
+        return pts, flags, cols, blocks, scale, step
+
+    def _samples_of(self, St, pcol):
+        host = St.t().cpu().numpy()
+        return {v: host[:, pcol[v]:pcol[v] + v.dim].copy() for v in self._elimination_ordering}
+
+    def posterior_refine(self, samples=None, n: int = None, steps: int = 100, step_size: float = 1e-2, kernel="variable",
+                         sigma=None, standardise: bool = True) -> dict:
+        """Posterior samples moved along the score of the joint density p(X, Z), on the device where the sample matrix lies:
+        Stein variational gradient descent (nfisam_sample_svgd, nfisam_sample_step: float32 points, float64 arithmetic) --
+        phi(x_i) = 1/n sum_j [k(x_j, x_i) grad log p(x_j) + grad_{x_j} k(x_j, x_i)], the descent direction of the statistic
+        `posterior_ksd` reports, applied `steps` times with the AdaGrad rule of the original SVGD code.  Not in the reference.
+
+        samples=None draws `n` (default posterior_sample_num) points through the tree walk; otherwise `samples` is refined (as
+        `joint_log_pdf` accepts it) and nothing is drawn.  kernel: "variable" one kernel per variable of the elimination
+        ordering (each sees its own columns; the fixed point is still p), "joint" one kernel over all columns, None no kernel:
+        every point climbs the score alone (see `map_refine`).  standardise: every column's differences are divided by its
+        spread over the STARTING points, as in `posterior_ksd`, and a column's step is `step_size` times that spread; otherwise
+        the step is `step_size` in every column's own unit.  sigma: the bandwidth in those units, one or (kernel="variable") one
+        per variable in ordering order; None = sqrt(block width).  Headings are flagged circular from the variables.  The
+        points stay float32: a step below a coordinate's float32 spacing (7.6e-6 at 100 m) is lost.
+        -> dict: samples (variable -> [n, dim] float32: valid input to every other evaluation), log_p_before, log_p_after
+        ([n] float64: `joint_log_pdf` of the points), steps, kernel, sigma (variable -> bandwidth, one bandwidth for "joint",
+        None without kernel), precision (variable -> [dim], scale^2 / sigma^2 as `posterior_ksd` reports it; scale^2 without
+        kernel), n.
+        A copy of the sample matrix is refined: no solver state changes and refined samples are not fed back; random numbers
+        are drawn only when `samples` is None.  Raises RuntimeError when there is no graph / tree yet, NotImplementedError naming
+        a factor class without a device code, ValueError for bad points or options -- before anything is launched."""
+        from utils import Statistics as ST
+        what = "posterior_refine"
+
+        def blocks_of(pts, cols):
+            if kernel not in ("variable", "joint", None):
+                raise ValueError("%s: kernel must be 'variable', 'joint' or None, got %r" % (what, kernel))
+            if kernel == "variable":
+                return [np.arange(pts.pcol[v], pts.pcol[v] + v.dim) for v in self._elimination_ordering]
+            return [cols]
+
+        pts, flags, cols, blocks, scale, step = self._refine_front(what, samples, n, steps, step_size, standardise, blocks_of,
+                                                                   sigma if kernel is not None else None)
+        pcol, order = pts.pcol, list(self._elimination_ordering)
+        work = pts.over(pts.St.clone())                                # never the walk's own tensor
+        log_p_before = self._joint_launch(pts)
+        res = ST.stein_variational_refine_t(work.St, lambda Xt: self._score_launch(work), blocks, int(steps), step, sigma=sigma
+                                            if kernel is not None else None, scale=scale, circular=flags,
+                                            kernel=kernel is not None)
+        log_p_after = self._joint_launch(work) if res["steps"] else log_p_before
+        opt = ST.check_refine_options(pts.total_dim, blocks, sigma if kernel is not None else None)
+        sig_col = np.ones(pts.total_dim)
+        if kernel is not None:
+            for b, s in zip(blocks, opt["sigma"]):
+                sig_col[b] = s
+        precision = scale * scale / (sig_col * sig_col)
+        sig_out = None if kernel is None else float(opt["sigma"][0]) if kernel == "joint" else \
+            {v: float(s) for v, s in zip(order, opt["sigma"])}
+        return dict(samples=self._samples_of(work.St, pcol), log_p_before=log_p_before.cpu().numpy(),
+                    log_p_after=log_p_after.cpu().numpy(), steps=res["steps"], kernel=kernel, sigma=sig_out,
+                    precision={v: precision[pcol[v]:pcol[v] + v.dim].copy() for v in order}, n=pts.rows)
+
+    def map_refine(self, samples=None, n: int = None, top: int = 8, steps: int = 200, step_size: float = 1e-2,
+                   standardise: bool = True) -> dict:
+        """A MAP estimate that is not limited to the best draw: the `top` points of highest joint density log p(X, Z) among
+        `samples` (or a fresh posterior draw of `n`) each climb the score alone (`posterior_refine` with kernel=None: the
+        AdaGrad steps of nfisam_sample_step), log p is evaluated after every step, and the best iterate of every climber --
+        its start included -- is kept on the device.  The result is therefore never below `map_estimate` on the same points.
+        standardise: a column's step is `step_size` times its spread over ALL the given points.
+        -> dict: map_sample (variable -> [dim] float32), log_p (its joint log density), start_log_p (the best of the input:
+        `map_estimate`'s), improved (log_p > start_log_p), climbers ([top] float64: the best log p every climber reached, by
+        falling start), steps, top (min(top, n)), n.
+        No solver state changes; random numbers are drawn only when `samples` is None.  Raises what `posterior_refine` raises,
+        and ValueError for a `top` that is no integer >= 1 -- before anything is launched."""
+        from utils import Statistics as ST
+        what = "map_refine"
+
+        def blocks_of(pts, cols):
+            if isinstance(top, bool) or int(top) != top or int(top) < 1:
+                raise ValueError("%s: top must be an integer >= 1, got %r" % (what, top))
+            return [cols]
+
+        pts, flags, cols, blocks, scale, step = self._refine_front(what, samples, n, steps, step_size, standardise, blocks_of)
+        top = min(int(top), pts.rows)
+        log_p = self._joint_launch(pts)
+        best_lp, idx = torch.topk(log_p, top)                          # by falling log p
+        start_log_p = float(best_lp[0].item())
+        work = pts.over(pts.St[:, idx].contiguous())
+        best, best_lp = work.St.clone(), best_lp.clone()
+
+        def keep(Xt, t):
+            lp = self._joint_launch(work)
+            better = lp > best_lp                                      # (False for a NaN: the start stays)
+            best_lp.copy_(torch.where(better, lp, best_lp))
+            best.copy_(torch.where(better.unsqueeze(0), Xt, best))
+
+        res = ST.stein_variational_refine_t(work.St, lambda Xt: self._score_launch(work), blocks, int(steps), step, scale=scale,
+                                            circular=flags, kernel=False, after_step=keep)
+        k = int(torch.argmax(best_lp).item())
+        row, pcol = best[:, k].cpu().numpy(), pts.pcol
+        out_lp = float(best_lp[k].item())
+        return dict(map_sample={v: row[pcol[v]:pcol[v] + v.dim].copy() for v in self._elimination_ordering}, log_p=out_lp,
+                    start_log_p=start_log_p, improved=bool(out_lp > start_log_p), climbers=best_lp.cpu().numpy(),
+                    steps=res["steps"], top=top, n=pts.rows)
 
     # ---- the solver graded against a reference sample set --------------------------------------------------------
     def posterior_mmd(self, reference, samples=None, n: int = None, variables=None, blocks=None, columns: str = "xy",

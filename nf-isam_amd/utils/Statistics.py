@@ -549,3 +549,154 @@ def Gaussian_kernel_stein_discrepancy(joint_factor_or_score, kernel_precision, s
     off = sums["H"].cpu().numpy()
     np.fill_diagonal(off, 0.0)
     return ustats, float(np.mean(boot >= ustats)), off, vstats
+
+
+# ---- the samples moved along the score: Stein variational refinement and plain ascent (nfisam_sample_svgd / _step) ------------
+def check_refine_options(width, blocks, sigma=None, scale=None, circular=None, steps=0, step_size=1.0, alpha=0.9, fudge=1e-6):
+    """Every option of the Stein variational functions, checked with no device: `blocks` a non-empty list of non-empty column
+    lists of any width inside [0, width) that share no column (a column has one direction); sigma one positive bandwidth or one
+    per block (None: sqrt(block width), the rule of `kernel_stein_discrepancy`); scale one finite value per column (None: ones);
+    circular one flag per column; steps an integer >= 0; step_size one positive finite step or one per column; alpha in [0, 1);
+    fudge positive and finite.  -> dict(cols: list of int64 arrays, flat, dims, sigma [n_blocks], scale [width], flags [width],
+    step [width], steps)."""
+    import nfisam_hip as _nh
+    cols = []
+    for k, b in enumerate(blocks):
+        c = np.asarray(b, dtype=np.int64)
+        if c.ndim != 1 or c.size < 1:
+            raise ValueError("block %d: a block is a non-empty list of columns" % k)
+        if c.min() < 0 or c.max() >= width:
+            raise ValueError("block %d names a column outside the %d columns of the sample set" % (k, width))
+        cols.append(c)
+    if not cols:
+        raise ValueError("no blocks")
+    flat = np.concatenate(cols)
+    if np.unique(flat).size != flat.size:
+        raise ValueError("overlapping blocks: a column is named more than once, and a column has one direction")
+    dims = np.array([c.size for c in cols])
+    if sigma is None:
+        sig = np.sqrt(dims.astype(np.float64))
+    else:
+        sig = np.broadcast_to(np.asarray(sigma, dtype=np.float64).reshape(-1), (len(cols),)).copy() if np.size(sigma) == 1 else \
+            np.asarray(sigma, dtype=np.float64).reshape(-1)
+        if sig.size != len(cols) or not np.all(np.isfinite(sig) & (sig > 0)):
+            raise ValueError("sigma is one positive bandwidth, or one per block (%d)" % len(cols))
+    sc = np.ones(width) if scale is None else np.asarray(scale, dtype=np.float64).reshape(-1)
+    if sc.size != width or not np.all(np.isfinite(sc)):
+        raise ValueError("scale: one finite value per column of x (%d)" % width)
+    flags = _column_flags(circular, width)
+    if isinstance(steps, bool) or int(steps) != steps or int(steps) < 0:
+        raise ValueError("steps must be an integer >= 0, got %r" % (steps,))
+    step = np.broadcast_to(np.asarray(step_size, dtype=np.float64).reshape(-1), (width,)).copy() if np.size(step_size) == 1 else \
+        np.asarray(step_size, dtype=np.float64).reshape(-1)
+    if step.size != width or not np.all(np.isfinite(step) & (step > 0)):
+        raise ValueError("step_size is one positive finite step, or one per column (%d)" % width)
+    _nh.check_step_args(alpha, fudge)
+    return dict(cols=cols, flat=flat, dims=dims, sigma=sig, scale=sc, flags=flags, step=step, steps=int(steps))
+
+
+def _refine_tables(opt, device):
+    """The checked options `opt` as the tables of the two bindings on `device` (one upload) -> (block table, tables)."""
+    import nfisam_hip as _nh
+    flat = opt["flat"]
+    table = _nh.pack_mmd_blocks(opt["dims"], opt["sigma"])
+    wrap = opt["flags"][flat].astype(np.uint8)
+    return table, _nh.svgd_tables(device, table, flat, opt["scale"][flat], wrap if wrap.any() else None, opt["step"][flat])
+
+
+def stein_variational_direction(x, score, blocks, sigma=None, scale=None, circular=None, device=None) -> np.ndarray:
+    """The Stein variational direction phi(x_i) = 1/n sum_j [k(x_j, x_i) score_j + grad_{x_j} k(x_j, x_i)] of the points x [n, D]
+    (numpy or torch; float32 points) with scores score [n, D] = grad_x log p at them (float64), on the device
+    (nfisam_hip.svgd_direction: float64 arithmetic, direct differences): the direction in which `kernel_stein_discrepancy`
+    falls fastest.  `blocks`: a list of column lists, as `sample_modes` takes them but of any width and sharing no column; each
+    block's kernel exp(-sum_c (scale_c d_c)^2 / (2 sigma^2)) sees the block's own columns only.  sigma: one bandwidth or one per
+    block, None = sqrt(block width); scale: per column (1 / spread standardises; 0 takes a column out of the kernel); circular
+    [D]: columns that are angles, compared by differences wrapped into [-pi, pi].
+    -> [n, D] float64 numpy, zero in the columns no block names.  Every ValueError is raised before anything is launched."""
+    import nfisam_hip as _nh
+    if np.ndim(x) != 2 or np.ndim(score) != 2:
+        raise ValueError("x and score must be [points, columns]")
+    n, D = int(x.shape[0]), int(x.shape[1])
+    if tuple(score.shape) != (n, D):
+        raise ValueError("score must have the shape of x, %s, got %s" % ((n, D), tuple(score.shape)))
+    if n < 1 or D < 1:
+        raise ValueError("at least one point and one column are needed")
+    opt = check_refine_options(D, blocks, sigma, scale, circular)
+    flat = opt["flat"]
+    wrap = opt["flags"][flat].astype(np.uint8)
+    Phi = _nh.svgd_direction(x, score, _nh.pack_mmd_blocks(opt["dims"], opt["sigma"]), flat, opt["scale"][flat],
+                             wrap if wrap.any() else None, device=device)
+    out = np.zeros((n, D))
+    out[:, flat] = Phi.cpu().numpy().T
+    return out
+
+
+def stein_variational_refine_t(Xt, score_t, blocks, steps, step_size, sigma=None, scale=None, circular=None, kernel=True,
+                               alpha=0.9, fudge=1e-6, after_step=None) -> dict:
+    """Stein variational gradient descent of the particles in the COLUMN-major device matrix Xt [D, n] (contiguous float32),
+    IN PLACE and entirely on the device: `steps` times Gt = score_t(Xt) (a callable Xt -> the float64 column-major device
+    matrix of grad log p, e.g. around `nfisam_hip.factor_graph_score_t`), phi = `nfisam_hip.svgd_direction_t`, then
+    `nfisam_hip.sample_step_t`: x += step phi / (sqrt(hist) + fudge) with hist the decayed mean of phi^2 (the AdaGrad rule
+    of the original SVGD code).  blocks, sigma, scale, circular: as `stein_variational_direction`; step_size: one step length or
+    one per column, in the column's own unit.  kernel=False: phi is the score itself, every particle climbs alone (a MAP ascent)
+    and no pairwise launch is made.  after_step: a callable (Xt, step index) run after every step (what `map_refine` keeps its
+    best iterates with).  The points stay float32: a step below a coordinate's float32 spacing (7.6e-6 at 100 m) is lost.
+    -> dict(hist [n_entries, n] float64 device tensor, entries in block order; cols: the row of every entry; steps).
+    steps = 0 leaves every bit alone; two runs give the same bits.  Every option is checked before anything is launched."""
+    import nfisam_hip as _nh
+    import torch
+    if not callable(score_t):
+        raise ValueError("score_t must be a callable Xt -> Gt")
+    if np.ndim(Xt) != 2:
+        raise ValueError("Xt must be [columns, points]")
+    opt = check_refine_options(int(Xt.shape[0]), blocks, sigma, scale, circular, steps, step_size, alpha, fudge)
+    D, n = _nh._column_major_front("Xt", Xt)
+    if n < 1:
+        raise ValueError("stein_variational_refine: no points")
+    table, tables = _refine_tables(opt, Xt.device)
+    hist = torch.zeros(opt["flat"].size, n, dtype=torch.float64, device=Xt.device)
+    rows = tables["cols"].to(torch.int64)
+    for t in range(opt["steps"]):
+        Gt = score_t(Xt)
+        if kernel:
+            Phi = _nh.svgd_direction_t(Xt, Gt, table, opt["flat"], checked=True, tables=tables)
+        else:
+            _nh._score_front("the score", Gt, Xt)
+            if tuple(Gt.shape) != (D, n):
+                raise ValueError("the score matrix must have the shape of the points: %s, got %s" % ((D, n), tuple(Gt.shape)))
+            Phi = Gt.index_select(0, rows)
+        _nh.sample_step_t(Xt, None, Phi, hist, None, alpha=alpha, fudge=fudge, first=t == 0, checked=True, tables=tables)
+        if after_step is not None:
+            after_step(Xt, t)
+    return dict(hist=hist, cols=opt["flat"], steps=opt["steps"])
+
+
+def stein_variational_refine(x, score, blocks, steps, step_size, sigma=None, scale=None, circular=None, kernel=True, alpha=0.9,
+                             fudge=1e-6, device=None) -> dict:
+    """`stein_variational_refine_t` for row-major points x [n, D] (numpy or torch) and a score that is a callable on numpy:
+    score(points [n, D] float64) -> [n, D].  The direction and the step run on the device; the score is called on the host
+    once per step -- the convenience form: a device score belongs behind `stein_variational_refine_t`.
+    -> dict(x [n, D] float32 numpy: the refined points, hist [n, D] float64 numpy (zero in the columns no block names), steps)."""
+    import nfisam_hip as _nh
+    import torch
+    if not callable(score):
+        raise ValueError("score must be a callable points -> scores")
+    if np.ndim(x) != 2:
+        raise ValueError("x must be [points, columns]")
+    n, D = int(x.shape[0]), int(x.shape[1])
+    if n < 1 or D < 1:
+        raise ValueError("at least one point and one column are needed")
+    check_refine_options(D, blocks, sigma, scale, circular, steps, step_size, alpha, fudge)
+    device = _nh._row_major_front("stein_variational_refine", device, x=x)
+    Xt = _nh._columns(x, device)
+
+    def score_t(Xt):
+        g = np.asarray(score(Xt.t().cpu().numpy().astype(np.float64)), dtype=np.float64)
+        if g.shape != (n, D):
+            raise ValueError("score must return the shape of x, %s, got %s" % ((n, D), g.shape))
+        return torch.from_numpy(np.ascontiguousarray(g.T)).to(Xt.device)
+
+    res = stein_variational_refine_t(Xt, score_t, blocks, steps, step_size, sigma, scale, circular, kernel, alpha, fudge)
+    hist = np.zeros((n, D))
+    hist[:, res["cols"]] = res["hist"].cpu().numpy().T
+    return dict(x=Xt.t().cpu().numpy().copy(), hist=hist, steps=res["steps"])
