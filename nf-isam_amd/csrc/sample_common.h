@@ -1,7 +1,8 @@
 // sample_common.h — what the float64 evaluators over the column-major sample matrix share (factor_density.hip,
 // factor_score.hip, sample_mmd.hip, sample_ksd.hip, sample_svgd.hip, sample_summary.hip, sample_modes.hip): the angle wrap, the wave
 // reductions, the launch epilogue.  A new evaluator over that matrix starts from this header -- one of the FACTORS from
-// factor_model.h, which includes it and holds the factor model the two factor units share; it does NOT include nsf_host.h
+// factor_model.h, which includes it and holds the factor model the two factor units share, one over PAIRS of points from
+// sample_pairs.h, which includes it and holds what the MMD, KSD and SVGD units share; it does NOT include nsf_host.h
 // (the flow kernels' headers and `using namespace nsf`, whose float wave_sum / wrap_pi are other functions).
 //
 // THE MATRIX AND THE NUMERICS.  The points are the COLUMN-major float32 device matrix [rows][n] that the tree walk writes (St):

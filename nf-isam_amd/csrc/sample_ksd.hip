@@ -14,28 +14,22 @@
 // differences, never the Gram identity.  A wrapped difference is sign(d) wrap(|d|), so d_ji = -d_ij to the bit and H is
 // symmetric to the bit.
 //
-// Two launches, no float atomics.  (1) the FULL T x T grid of 64 x 64 tiles of pairs (h is symmetric, but the transposed row
-// contributions of an upper-triangle walk would need a second fixed-order pass; the full grid is the simpler form).  A
-// 256-thread group per tile: a lane owns one i and 16 j, with four accumulators per pair (sum p d^2, s.s, sum (s_i - s_j) p d,
-// sum p^2 d^2: 64 doubles); it walks the columns in chunks of 16, the i side read coalesced from the column-major matrices,
-// the j side (points and scores) staged as two [16][64] double tiles in LDS and read by broadcast.  Then 16 exp, the lane's
-// sum in j order, the four waves in order (waves_in_order), one store to partial[tj][i].  (2) row[i] = the partials of i in
-// tile order.  Everything but i and j is wave-uniform.  Hence: two calls give the same bits, and `row` is the same bits with
-// and without H.
+// Two launches, no float atomics.  (1) the FULL T x T grid of tiles of pairs (sample_pairs.h; h is symmetric, but the
+// transposed row contributions of an upper-triangle walk would need a second fixed-order pass).  Four accumulators per pair
+// (sum p d^2, s.s, sum (s_i - s_j) p d, sum p^2 d^2: 64 doubles a lane), points AND scores on both sides, an entry being its
+// own row: no table.  Then 16 exp, the lane's sum in j order, the four waves in order, one store to partial[tj][i].
+// (2) row[i] = the partials of i in tile order.  Hence: two calls give the same bits, and `row` is the same bits with and
+// without H.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/nfisam_hip.h"
-#include "sample_common.h"
+#include "sample_pairs.h"
 
 namespace {
 
-using namespace sample_common;
-
-constexpr int TILE = 64;          // pairs tile: 64 i (one per lane) x 64 j (16 per wave-lane, 4 waves)
-constexpr int JPL = 16;           // j per lane
-constexpr int CH = 16;            // columns per staged chunk
+using namespace sample_pairs;
 
 template <bool WRAP>
 __device__ __forceinline__ void column_step(double (&q)[JPL], double (&ss)[JPL], double (&sd)[JPL], double (&pp)[JPL], double xi,
@@ -44,10 +38,7 @@ __device__ __forceinline__ void column_step(double (&q)[JPL], double (&ss)[JPL],
 #pragma unroll
     for (int jj = 0; jj < JPL; ++jj) {
         double d = xi - xrow[jj];
-        if (WRAP) {
-            const double m = wrap_pi_near(fabs(d));
-            d = (d < 0.0) ? -m : m;
-        }
+        if (WRAP) d = signed_wrap(d);
         const double sj = srow[jj];
         const double pd = pc * d;
         q[jj] = fma(pd, d, q[jj]);
@@ -136,14 +127,6 @@ __global__ void __launch_bounds__(64) ksd_row_kernel(const double* __restrict__ 
     double s = 0.0;
     for (int t = 0; t < T; ++t) s += partial[(size_t)t * ((size_t)T * TILE) + (size_t)i];
     row[i] = s;
-}
-
-bool tile_count(int n, int* T) {
-    if (n < 1) return false;
-    const long long t = ((long long)n + TILE - 1) / TILE;
-    if (t > 65535) return false;                                       // the grid's second dimension
-    *T = (int)t;
-    return true;
 }
 
 }  // namespace

@@ -13,28 +13,23 @@
 // sample_common.h).  Direct differences, never the Gram identity |x|^2 + |y|^2 - 2 x.y, which cancels at coordinates of
 // 100 m; MMD^2 is a small difference of O(1) means, so float32 kernel values would cost three digits of it.
 //
-// Two launches, no float atomics.  (1) a 256-thread group owns a 64 x 64 tile of pairs of one block and one of the three
-// sums: a lane keeps its own i and 16 j (16 double accumulators of squared distance) and walks the block's columns in chunks
-// of 16; the i side is read coalesced from the column-major matrix, the j side is staged as a [16][64] double tile in LDS and
-// read by broadcast; then 16 exp, the lane's sum in j order, wave_sum, the four waves in order, one store to
-// partial[b][tile].  Sxx and Syy visit the upper triangle of tiles and count the off-diagonal ones twice (exact).  (2) one
-// wave per (block, sum) adds the tile partials in an order that depends on (m, n) alone.  The block index is blockIdx.y and
-// everything a block brings (its columns, bandwidth, scale, wrap flags) is wave-uniform.  Hence: two calls give the same
-// bits, and a block's sums are the same bits alone or among hundreds, wherever it stands in the table.
+// Two launches, no float atomics.  (1) a 256-thread group owns one tile of pairs (sample_pairs.h) of one block and one of the
+// three sums, 16 double accumulators of squared distance a lane, the i side from A and the j side from B through their own
+// row tables; then 16 exp, the lane's sum in j order, wave_sum, the four waves in order, one store to partial[b][tile].  Sxx
+// and Syy visit the upper triangle of tiles and count the off-diagonal ones twice (exact).  (2) one wave per (block, sum) adds
+// the tile partials in an order that depends on (m, n) alone.  The block index is blockIdx.y and everything a block brings
+// is wave-uniform.  Hence: two calls give the same bits, and a block's sums are the same bits alone or among hundreds,
+// wherever it stands in the table.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/nfisam_hip.h"
-#include "sample_common.h"
+#include "sample_pairs.h"
 
 namespace {
 
-using namespace sample_common;
-
-constexpr int TILE = 64;          // pairs tile: 64 i (one per lane) x 64 j (16 per wave-lane, 4 waves)
-constexpr int JPL = 16;           // j per lane
-constexpr int CH = 16;            // columns per staged chunk
+using namespace sample_pairs;
 
 // tiles of the upper triangle (tj >= ti) of a T x T grid are numbered row by row; row ti starts at tri_off(ti, T)
 __host__ __device__ __forceinline__ long long tri_off(long long ti, long long T) { return ti * T - ti * (ti - 1) / 2; }
@@ -188,12 +183,9 @@ __global__ void __launch_bounds__(64) mmd_sum_kernel(const double* __restrict__ 
 }
 
 bool tile_counts(int m, int n, int* Tx, int* Ty, long long* total) {
-    if (m < 1 || n < 1) return false;
-    const long long tx = ((long long)m + TILE - 1) / TILE, ty = ((long long)n + TILE - 1) / TILE;
-    const long long tot = tri_off(tx, tx) + tri_off(ty, ty) + tx * ty;
-    if (tot > 2147483647LL) return false;                          // the grid's first dimension
-    *Tx = (int)tx, *Ty = (int)ty, *total = tot;
-    return true;
+    if (!tile_count(m, Tx) || !tile_count(n, Ty)) return false;
+    *total = tri_off(*Tx, *Tx) + tri_off(*Ty, *Ty) + (long long)*Tx * *Ty;
+    return *total <= 2147483647LL;                                 // the grid's first dimension (65536 tiles a side are past it)
 }
 
 }  // namespace
@@ -209,7 +201,6 @@ extern "C" int nfisam_sample_mmd(const float* Xt, int x_rows, int m, const float
                                  const nfisam_mmd_block* blocks, const nfisam_mmd_block* blocks_dev, int n_blocks,
                                  const int32_t* xcols, const int32_t* ycols, int n_entries, const double* scale,
                                  const uint8_t* wrap, double* sums, double* scratch, nfisam_stream_t stream) {
-    static_assert(sizeof(nfisam_mmd_block) == 16, "nfisam_mmd_block is 16 bytes");
     if (Xt == nullptr || Yt == nullptr || blocks == nullptr || blocks_dev == nullptr || xcols == nullptr || ycols == nullptr || sums == nullptr ||
         scratch == nullptr)
         return NFISAM_ERR_ARG;
@@ -217,10 +208,7 @@ extern "C" int nfisam_sample_mmd(const float* Xt, int x_rows, int m, const float
     int Tx, Ty;
     long long total;
     if (!tile_counts(m, n, &Tx, &Ty, &total)) return NFISAM_ERR_ARG;
-    for (int b = 0; b < n_blocks; ++b) {                           // `blocks` is the HOST copy of the table: read here only
-        const double v = blocks[b].inv_two_sigma2;
-        if (blocks[b].d < 1 || !(v > 0.0) || !isfinite(v)) return NFISAM_ERR_ARG;
-    }
+    if (!check_block_table(blocks, n_blocks)) return NFISAM_ERR_ARG;   // `blocks` is the HOST copy of the table
     hipStream_t s = (hipStream_t)stream;
     double* partial = scratch;
     hipLaunchKernelGGL(mmd_tile_kernel, dim3((unsigned)total, n_blocks), dim3(256), 0, s, blocks_dev, Xt, x_rows, m, Yt, y_rows, n,

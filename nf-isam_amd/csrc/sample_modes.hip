@@ -32,11 +32,11 @@
 #include <stdint.h>
 
 #include "../../include/nfisam_hip.h"
-#include "sample_common.h"
+#include "sample_pairs.h"
 
 namespace {
 
-using namespace sample_common;
+using namespace sample_pairs;
 
 constexpr int MAX_D = NFISAM_MODES_MAX_D;
 constexpr int MAX_MODES = NFISAM_MODES_MAX_MODES;
@@ -339,13 +339,7 @@ __global__ void __launch_bounds__(256) modes_merge_kernel(const nfisam_mmd_block
 
 namespace {
 
-bool table_ok(const nfisam_mmd_block* blocks, int n_blocks) {      // `blocks` is the HOST copy of the table: read here only
-    for (int b = 0; b < n_blocks; ++b) {
-        const double v = blocks[b].inv_two_sigma2;
-        if (blocks[b].d < 1 || blocks[b].d > MAX_D || !(v > 0.0) || !isfinite(v)) return false;
-    }
-    return true;
-}
+bool table_ok(const nfisam_mmd_block* blocks, int n_blocks) { return check_block_table(blocks, n_blocks, MAX_D); }
 
 bool merge_args_ok(double merge, int max_modes) {
     return merge > 0.0 && isfinite(merge) && max_modes >= 1 && max_modes <= MAX_MODES;
@@ -369,7 +363,6 @@ extern "C" int nfisam_sample_modes(const float* Xt, int x_rows, int n, const nfi
                                    double merge, int max_modes, double* pos, double* dens, int32_t* iters, int32_t* labels,
                                    int32_t* n_modes, double* mode_pos, double* mode_dens, double* mode_mass, int32_t* unlabelled,
                                    nfisam_stream_t stream) {
-    static_assert(sizeof(nfisam_mmd_block) == 16, "nfisam_mmd_block is 16 bytes");
     if (Xt == nullptr || blocks == nullptr || blocks_dev == nullptr || cols == nullptr || pos == nullptr || dens == nullptr ||
         iters == nullptr || labels == nullptr || n_modes == nullptr || mode_pos == nullptr || mode_dens == nullptr ||
         mode_mass == nullptr || unlabelled == nullptr)

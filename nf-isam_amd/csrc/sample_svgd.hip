@@ -17,17 +17,16 @@
 // Numerics: the contract of sample_common.h -- float32 points in; differences, products, exp and every sum float64; direct
 // differences.
 //
-// Two launches, no float atomics.  (1) grid (T tiles of j, T tiles of i, blocks), a 256-thread group per 64 x 64 tile of pairs
-// and block, a lane owning one i and 16 j.  Pass 1 walks the block's columns in staged chunks of 16 (the j side as a [16][64]
-// double tile in LDS read by broadcast, the i side coalesced) to the 16 squared distances, then the 16 k, which stay in
-// registers (zero for a pair outside the n x n square).  Pass 2 walks the columns again, points and scores of the j side staged,
-// and forms per column the lane's sum over its 16 j in j order; the four waves' sums of a chunk are parked in LDS and combined
-// in wave order (waves_in_order), one store to partial[tj][e][i].  The block width has no limit: nothing is kept per column
-// beyond the chunk.  (2) phi[e][i] = the partials of (e, i) in tile order, divided by n.  Everything but i and j is
-// wave-uniform, and the split of the j range depends on n alone.  Hence: two calls give the same bits, a block's rows are the
-// same bits alone or among hundreds, wherever it stands in the table.  A pair's two terms are mirror images to the bit (k_ij = k_ji,
-// d_ji = -d_ij) and enter the sums as rounded products: swapping the two points of a two-point set swaps their phi rows bit for
-// bit (among more points the terms are the same bits and only the order of the sum differs).
+// Two launches, no float atomics.  (1) grid (T tiles of j, T tiles of i, blocks), a 256-thread group per tile of pairs
+// (sample_pairs.h) and block.  Pass 1 walks the block's columns, points alone, to the 16 squared distances, then the 16 k, which
+// stay in registers (zero for a pair outside the n x n square).  Pass 2 walks the columns again, points and scores of the j
+// side staged, and forms per column the lane's sum over its 16 j in j order; the four waves' sums of a chunk are parked in LDS
+// and combined in wave order, one store to partial[tj][e][i].  The block width has no limit: nothing is kept per column
+// beyond the chunk.  (2) phi[e][i] = the partials of (e, i) in tile order, divided by n.  The split of the j range depends on
+// n alone.  Hence: two calls give the same bits, a block's rows are the same bits alone or among hundreds, wherever it stands
+// in the table.  A pair's two terms are mirror images to the bit (k_ij = k_ji, d_ji = -d_ij) and enter the sums as rounded
+// products: swapping the two points of a two-point set swaps their phi rows bit for bit (among more points the terms are the
+// same bits and only the order of the sum differs).
 // LDS: 2 x 8 KiB staged tiles + 32 KiB of wave sums = 48 KiB a group, three groups a CU; the partials take
 // T x n_entries x 64 T doubles (nfisam_sample_svgd_scratch_count).
 //
@@ -47,20 +46,11 @@
 #include <vector>
 
 #include "../../include/nfisam_hip.h"
-#include "sample_common.h"
+#include "sample_pairs.h"
 
 namespace {
 
-using namespace sample_common;
-
-constexpr int TILE = 64;          // pairs tile: 64 i (one per lane) x 64 j (16 per wave-lane, 4 waves)
-constexpr int JPL = 16;           // j per lane
-constexpr int CH = 16;            // columns per staged chunk
-
-__device__ __forceinline__ double signed_wrap(double d) {          // sign(d) wrap(|d|): antisymmetric to the bit
-    const double m = wrap_pi_near(fabs(d));
-    return (d < 0.0) ? -m : m;
-}
+using namespace sample_pairs;
 
 template <bool WRAP>
 __device__ __forceinline__ void distance_step(double (&acc)[JPL], double xi, const double* __restrict__ xrow, double sc) {
@@ -257,14 +247,6 @@ __global__ void __launch_bounds__(256) svgd_step_kernel(float* __restrict__ Xt, 
     Xt[xi] = f;
 }
 
-bool tile_count(int n, int* T) {
-    if (n < 1) return false;
-    const long long t = ((long long)n + TILE - 1) / TILE;
-    if (t > 65535) return false;                                       // the grid's second dimension
-    *T = (int)t;
-    return true;
-}
-
 }  // namespace
 
 extern "C" size_t nfisam_sample_svgd_scratch_count(int n, int n_blocks, int n_entries) {
@@ -276,17 +258,15 @@ extern "C" size_t nfisam_sample_svgd_scratch_count(int n, int n_blocks, int n_en
 extern "C" int nfisam_sample_svgd(const float* Xt, int x_rows, int n, const double* Gt, const nfisam_mmd_block* blocks,
                                   const nfisam_mmd_block* blocks_dev, int n_blocks, const int32_t* cols, int n_entries,
                                   const double* scale, const uint8_t* wrap, double* phi, double* scratch, nfisam_stream_t stream) {
-    static_assert(sizeof(nfisam_mmd_block) == 16, "nfisam_mmd_block is 16 bytes");
     if (Xt == nullptr || Gt == nullptr || blocks == nullptr || blocks_dev == nullptr || cols == nullptr || phi == nullptr ||
         scratch == nullptr)
         return NFISAM_ERR_ARG;
     int T;
     if (x_rows < 1 || n_entries < 1 || n_blocks < 1 || n_blocks > 65535 || !tile_count(n, &T)) return NFISAM_ERR_ARG;
+    if (!check_block_table(blocks, n_blocks)) return NFISAM_ERR_ARG;   // `blocks` is the HOST copy of the table
     long long max_d = 1;
     std::vector<std::pair<long long, long long>> runs((size_t)n_blocks);
-    for (int b = 0; b < n_blocks; ++b) {                               // `blocks` is the HOST copy of the table: read here only
-        const double v = blocks[b].inv_two_sigma2;
-        if (blocks[b].d < 1 || !(v > 0.0) || !isfinite(v)) return NFISAM_ERR_ARG;
+    for (int b = 0; b < n_blocks; ++b) {
         max_d = std::max<long long>(max_d, blocks[b].d);
         runs[(size_t)b] = {blocks[b].col_off, (long long)blocks[b].col_off + blocks[b].d};
     }

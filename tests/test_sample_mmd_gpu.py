@@ -110,6 +110,23 @@ def test_sums_match_the_float64_oracle(m, n):
         assert np.all(dev[:, 1] == 1.0)
 
 
+def test_chunk_boundary_widths_at_a_tile_boundary():
+    """Blocks of 16, 17 and 33 columns -- one staged chunk of 16, a chunk plus one column, two chunks plus one -- at
+    m = n = 65, one point past the 64-point tile on both sides; with a scale and a wrapped column, and without.  The 14-block
+    table above reaches widths 16, 17 and 40 but not 33, and n = 65 on the x side only."""
+    x, y = _data()
+    x, y = x[:65], y[:65]
+    r = lambda a, b: list(range(a, b))                                                        # noqa: E731
+    rng = np.random.RandomState(13)
+    plain = [(r(a, a + d), r(a, a + d), float(np.sqrt(d)), None, None) for a, d in ((3, 16), (20, 17), (7, 33))]
+    wrapped = [(r(26, 59), r(26, 59), float(np.sqrt(33)), list(rng.uniform(0.5, 2.0, 33)), [0] * 32 + [1])]     # 58: the heading
+    for table in (plain, plain + wrapped):
+        dev = nh.mmd_sums(x, y, *_arrays(table), device=DEV).cpu().numpy()
+        ref = _oracle(x, y, table)
+        print("widths %s: largest relative deviation %.3g" % ([len(b[0]) for b in table], (np.abs(dev - ref) / ref).max()))
+        assert np.all(np.isfinite(dev)) and _excess(dev, ref) <= 1.0, (dev, ref)
+
+
 def test_second_call_single_blocks_and_reversed_table_give_the_same_bits():
     x, y = _data()
     x, y = x[:M_MAX], y[:N_MAX]
