@@ -69,15 +69,16 @@ __device__ __forceinline__ Se2Relative se2_relative_residual(double ax, double a
 
 // log N(Log(dT); 0, Sigma) + log|det dLog| for dT = (tx, ty, w); p[3..8] = upper triangle of the precision, p[9] = log normaliser.
 // Log: v = V^-1(w) t with V^-1 = [[a, w/2], [-w/2, a]], a = (w/2) cot(w/2) (the half-angle form of
-// geometry/TwoDimension.py:405-418; identity for |w| < 1e-10); det dLog = w^2 / (4 sin^2(w/2)), 1 for |w| < 1e-5 (:437-441).
+// geometry/TwoDimension.py:405-418); det dLog = w^2 / (4 sin^2(w/2)), 1 for |w| < 1e-5 (:437-441).  Below |w| = 1e-10 only a
+// is set to 1 (it is 1 - w^2 / 12 there); the off-diagonal w/2 stays: the reference's identity drops a term of |w| |t| / 2,
+// 1e-10 relative and 7e4 roundings against tests/golden/factor_exact.npz (profiles/factor_exact.json).
 __device__ __forceinline__ double se2_tangent_log_pdf(double tx, double ty, double w, const double* __restrict__ p) {
     const double h = 0.5 * w;
     double sh, ch;
     sincos(h, &sh, &ch);
     const bool small = fabs(w) < 1e-10;
     const double a = small ? 1.0 : h * ch / sh;
-    const double b = small ? 0.0 : h;
-    const double vx = a * tx + b * ty, vy = a * ty - b * tx;
+    const double vx = a * tx + h * ty, vy = a * ty - h * tx;
     const double q = p[3] * vx * vx + p[6] * vy * vy + p[8] * w * w + 2.0 * (p[4] * vx * vy + p[5] * vx * w + p[7] * vy * w);
     const double log_det = (fabs(w) < 1e-5) ? 0.0 : 2.0 * log(fabs(h / sh));
     return p[9] - 0.5 * q + log_det;

@@ -154,10 +154,10 @@ def _sym_upper(precision: np.ndarray) -> List[float]:
 def _se2_tangent_log_pdf(tx, ty, w, precision, log_norm) -> np.ndarray:
     """log N(Log(dT); 0, Sigma) + log|det dLog/d(x, y, theta)| for dT = (tx, ty, w), w in [-pi, pi)
     (reference geometry/TwoDimension.py:405-418 log_map, :437-441 det_grad_x_logmap)."""
-    small = np.abs(w) < 1e-10
-    half = 0.5 * np.where(small, 1.0, w)
+    small = np.abs(w) < 1e-10                    # a = 1 - w^2 / 12 is 1 there; the off-diagonal w / 2 of V^-1 is kept (the
+    half = 0.5 * np.where(small, 1.0, w)         # reference's identity drops |w| |t| / 2: 1e-10 relative, csrc/factor_model.h)
     a = np.where(small, 1.0, half * np.cos(half) / np.sin(half))
-    b = np.where(small, 0.0, half)
+    b = 0.5 * w
     v = np.stack([a * tx + b * ty, -b * tx + a * ty, w], axis=1)
     flat = np.abs(w) < 1e-5
     h = 0.5 * np.where(flat, 1.0, w)

@@ -11,9 +11,11 @@ measured over every value it covers (both sides are float64 evaluations at the s
     not a different formula: its log map divides by cos(w) - 1 and sin(w) (geometry/TwoDimension.py:410-417), and cos(w) - 1
     has lost all but ~2 digits at the heading residuals |w| ~ 1e-7 that part (a) contains on purpose (inside the 1e-5
     branch of the Jacobian); the error of v is ~1e-16 |t| / |w|, times precision x residual (1e6 x 1e-3) = 5e-8 in the term.
-    `log_pdf` uses the half-angle form (w/2) cot(w/2), which does not cancel: against an 80-bit evaluation of the same
-    case it is within 4e-13 where the reference is off by 3.5e-10 .. 7e-9.  Every SE(2) case with |w| > 1e-4 and every other
-    class agrees to 2e-9 or better (ranges, mixtures, R2 classes: 1e-15)."""
+    `log_pdf` uses the half-angle form (w/2) cot(w/2), which does not cancel: against the 60-digit values of the same
+    cases (tests/golden/factor_exact.npz, made by tests/golden/make_factor_exact_fixture.py; held by
+    tests/test_factor_exact_cpu.py and tests/test_factor_exact_gpu.py) it is within a few roundings of the value's own error
+    scale where the reference is off by 3.5e-10 .. 7e-9.  Every SE(2) case with |w| > 1e-4 and every other class agrees to
+    2e-9 or better (ranges, mixtures, R2 classes: 1e-15)."""
 import ctypes as C
 import os
 import re

@@ -9,10 +9,11 @@ Bounds, |ours - ref| <= TOL (|ref| + 1) on the rows the fixture's masks cover, e
     These two are the REFERENCE's error, not this code's.  Its SE(2) `grad_x_log_pdf` builds d Log / d theta from
     logmap / w + (w / 2) x / (cos w - 1) (geometry/TwoDimension.py:431-435): two terms of size |t| / w that cancel, with
     cos w - 1 correct to 1e-16 / w^2 relative -- an O(1) error at the |w| ~ 1e-5 rows part (a) holds on purpose -- and it
-    switches to a first-order form below 1e-5.  Against 60-digit derivatives of the same density (mpmath, central differences
-    of the smooth formula, every SE(2) value of part (a)) the reference is off by up to 0.43 and `grad_x_log_pdf` here by at
-    most 3.8e-10 (the tightest prior, covariance 1e-12; 2.5e-12 otherwise).  The finite difference the fixture also stores
-    agrees with this code, not with the reference's analytic value, on those rows.
+    switches to a first-order form below 1e-5.  The exact yardstick of these rows is tests/golden/factor_exact.npz (60-digit
+    values and gradients of the smooth density, made by tests/golden/make_factor_exact_fixture.py): `grad_x_log_pdf` is held
+    to it, every SE(2) value of part (a) included, within 256 roundings of the value's own error scale by
+    tests/test_factor_exact_cpu.py (the device: tests/test_factor_exact_gpu.py), where the reference is off by up to 0.43.  The
+    finite difference the fixture also stores agrees with this code, not with the reference's analytic value, on those rows.
   * so the same comparison is also made where the reference does not cancel, with the bound the same rule gives there:
       ranges and mixtures (reference analytic)                   measured 3.8e-16  -> TOL_EXACT = 6.1e-15
       the three R2 classes (Richardson differences, step 1e-3 sigma) measured 7.4e-11  -> TOL_FD = 1.2e-9
