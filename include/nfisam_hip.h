@@ -287,6 +287,25 @@ int nfisam_factor_graph_score(const nfisam_factor_term* terms, int n_terms, cons
                               const int32_t* slot_off, int n_slots, const int32_t* row_off, const int32_t* row_slot, double* Gt,
                               double* scratch, nfisam_stream_t stream);
 
+/* ---- Hessian-vector products of the joint density (factor_hessian.hip) -----------------------------------------------------
+ * Ht[r][p] = sum_c d^2 log p / dx_r dx_c (X_p) * Vt[c][p]: the derivative of the score entry's smooth float64 formula along the
+ * direction Vt, at the float32 point (not in the reference; matrix-free Newton steps and Laplace covariances need nothing
+ * denser).  Small-angle series of a''(w) and l''(w) below |w| = 0.6; the zero vector at a range of exactly 0, like the score;
+ * mixtures: sum_j r_j (H_j v + g_j (g_j . v)) - g (g . v) with the score's softmax weights (finite far from every component).
+ *   The table, St, slot_off / n_slots / row_off / row_slot: those of nfisam_factor_graph_score, unchanged (a factor's share of
+ *   H v is one number per row it touches: the same slots, the same ordered gather).  Vt[total_dim][n], Ht[total_dim][n] double;
+ *   Gt[total_dim][n] double or NULL: with Gt the same first pass also evaluates the score's slots, and Gt is
+ *   nfisam_factor_graph_score's result BIT FOR BIT (a Newton step needs g and H v at one point); Ht is the same bits with and
+ *   without Gt.  scratch: nfisam_factor_graph_hvp_scratch_count(n_slots, n, Gt != NULL) doubles on the device.
+ * Two launches (three with Gt), no float atomics: two calls give the same bits, and a point's column does not depend on n or
+ * on its tile.  n == 0: nothing is done; n_terms == 0: a zero Ht (and Gt).
+ * NFISAM_ERR_ARG: the score entry's refusals, and a NULL Vt.  A bad record reads nothing of St or Vt and yields NaN in its
+ * slots, as there.  (Additive: ABI 1600.)                                                                              */
+size_t nfisam_factor_graph_hvp_scratch_count(int n_slots, int n, int with_score);
+int nfisam_factor_graph_hvp(const nfisam_factor_term* terms, int n_terms, const float* St, const double* Vt, int total_dim, int n,
+                            const int32_t* slot_off, int n_slots, const int32_t* row_off, const int32_t* row_slot, double* Ht,
+                            double* Gt, double* scratch, nfisam_stream_t stream);
+
 /* ---- two-sample MMD: the kernel sums of many column blocks in one launch (sample_mmd.hip) ---------------------------------
  * The reference grades a posterior against a reference sample set with an RBF-kernel MMD (src/utils/Statistics.py:13-84).
  * Block b of the table compares the entries col_off .. col_off + d of the row lists: entry e pairs row xcols[e] of Xt with

@@ -1,4 +1,5 @@
-// factor_model.h — the factor model that factor_density.hip (the value) and factor_score.hip (its gradient) share, once each:
+// factor_model.h — the factor model that factor_density.hip (the value), factor_score.hip (its gradient) and factor_hessian.hip
+// (its Hessian-vector product) share, once each:
 // what a record of the table (nfisam_factor_term, the seven NFISAM_FAC_* codes) reads, the ONE guard in front of every read,
 // the residuals and the per-term formulas.  A new evaluator of the factors starts here.  Numerics and layout: the contract of
 // sample_common.h.  `t` and `p` are wave-uniform (the factor index depends on the block index alone) and `const __restrict__`:
@@ -125,6 +126,61 @@ __device__ __forceinline__ void se2_tangent_score(double tx, double ty, double w
     *gw = gvw + gvx * (da * tx + 0.5 * ty) + gvy * (da * ty - 0.5 * tx) + dl;
 }
 
+// The second derivatives in w: a''(w) = (a - 1) / (2 sin^2 h) and l''(w) = (1 / sin^2 h - 1 / h^2) / 2.  Both are differences
+// of two terms of size 1 / h^2 that leave -1/6 resp. 1/6: the plain forms lose 3 eps / h^2 resp. 6 eps / h^2 relative, twice
+// and four times what a' and l' lose, so at SERIES_H = 0.1 they would have lost 300 and 600 roundings, and l'' is the whole
+// heading-heading entry of a loose prior.  The series (the derivatives of the series above, coefficients 2^2k |B_2k| / (2k)!
+// times 2k (2k - 1) / 4 resp. (2k - 1) / 2) converge like (h / pi)^2k, so the switch moves OUT and the series grow: through
+// h^16, below SERIES2_H = 0.3.  There the plain forms have lost 3 eps / h^2 = 33 and 6 eps / h^2 = 67 roundings, and the first
+// dropped terms, 2.2e-8 h^18 and 2.2e-9 h^18 against 1/6, are 5e-17 and 5e-18 relative (under half a rounding): the plain side
+// is the worse one at the switch and only improves beyond it, and a switch further out (h = 0.5: 12 and 24 roundings) would
+// need the series through h^22 for the same balance.
+constexpr double SERIES2_H = 0.3;
+
+__device__ __forceinline__ void log_map_curvature(double w, double a, double* dda_dw, double* ddlogdet_dw) {
+    const double h = 0.5 * w;
+    if (fabs(h) < SERIES2_H) {
+        const double h2 = h * h;
+        *dda_dw = -(1.0 / 6.0 + h2 * (1.0 / 15.0 + h2 * (1.0 / 63.0 + h2 * (2.0 / 675.0 + h2 * (1.0 / 2079.0 + h2 * (1382.0 / 19348875.0 +
+                  h2 * (2.0 / 200475.0 + h2 * (14468.0 / 10854718875.0 + h2 * (43867.0 / 254766637125.0)))))))));
+        *ddlogdet_dw = 1.0 / 6.0 + h2 * (1.0 / 30.0 + h2 * (1.0 / 189.0 + h2 * (1.0 / 1350.0 + h2 * (1.0 / 10395.0 + h2 * (691.0 / 58046625.0 +
+                       h2 * (2.0 / 1403325.0 + h2 * (3617.0 / 21709437750.0 + h2 * (43867.0 / 2292899734125.0))))))));
+    } else {
+        const double sh = sin(h);
+        const double is2 = 1.0 / (sh * sh);
+        *dda_dw = 0.5 * (a - 1.0) * is2;
+        *ddlogdet_dw = 0.5 * (is2 - 1.0 / (h * h));
+    }
+}
+
+// The gradient (gtx, gty: what the chain rule of a relative pose needs again) and the Hessian-vector product of
+// se2_tangent_log_pdf along (vtx, vty, vw): the derivative of se2_tangent_score along that direction, term by term.  With
+// v = (a tx + h ty, a ty - h tx, w), j = dv/dw = (a' tx + ty / 2, a' ty - tx / 2), gv = -P v:
+//   dv = A (vtx, vty) + j vw,   dgv = -P (dv, vw),   d gt = A' dgv_xy + A'(w)' gv_xy vw,
+//   d gw = dgv_w + dgv_xy . j + gv_xy . (a'' vw t + A'(w) (vtx, vty)) + l'' vw
+__device__ __forceinline__ void se2_tangent_hvp(double tx, double ty, double w, const double* __restrict__ p, double vtx,
+                                                double vty, double vw, double* gtx, double* gty, double* htx, double* hty,
+                                                double* hw) {
+    double a, da, dl, dda, ddl;
+    log_map_terms(w, &a, &da, &dl);
+    log_map_curvature(w, a, &dda, &ddl);
+    const double h = 0.5 * w;
+    const double vx = a * tx + h * ty, vy = a * ty - h * tx;
+    const double gvx = -(p[3] * vx + p[4] * vy + p[5] * w);
+    const double gvy = -(p[4] * vx + p[6] * vy + p[7] * w);
+    *gtx = a * gvx - h * gvy;
+    *gty = h * gvx + a * gvy;
+    const double jx = da * tx + 0.5 * ty, jy = da * ty - 0.5 * tx;
+    const double dvx = a * vtx + h * vty + jx * vw, dvy = a * vty - h * vtx + jy * vw;
+    const double dgvx = -(p[3] * dvx + p[4] * dvy + p[5] * vw);
+    const double dgvy = -(p[4] * dvx + p[6] * dvy + p[7] * vw);
+    const double dgvw = -(p[5] * dvx + p[7] * dvy + p[8] * vw);
+    *htx = a * dgvx - h * dgvy + (da * gvx - 0.5 * gvy) * vw;
+    *hty = h * dgvx + a * dgvy + (0.5 * gvx + da * gvy) * vw;
+    *hw = dgvw + dgvx * jx + dgvy * jy + gvx * (dda * vw * tx + da * vtx + 0.5 * vty) + gvy * (dda * vw * ty + da * vty - 0.5 * vtx) +
+          ddl * vw;
+}
+
 // ---- the range term log N(|a - b| - d; 0, 1 / inv_var), and its d/da (d/db is the negative): the zero vector at |a - b| = 0,
 // where the range has no direction
 __device__ __forceinline__ double range_log_pdf(double ax, double ay, double bx, double by, double d, double inv_var,
@@ -139,6 +195,22 @@ __device__ __forceinline__ void range_score(double ax, double ay, double bx, dou
     const double r = sqrt(dx * dx + dy * dy);
     const double c = (r > 0.0) ? -(r - d) * inv_var / r : 0.0;
     *gx = c * dx, *gy = c * dy;
+}
+
+// The a-a block of the range term's Hessian times q: with r = |a - b|, u = (a - b) / r, delta = r - d it is
+// -inv_var [u u' + (delta / r) (I - u u')] q  (the b-b block is the same, the a-b block its negative: q = v_a - v_b gives the
+// rows of a, the negative those of b); the zero vector at r = 0, like the score.
+__device__ __forceinline__ void range_hvp(double ax, double ay, double bx, double by, double d, double inv_var, double qx,
+                                          double qy, double* hx, double* hy) {
+    const double dx = ax - bx, dy = ay - by;
+    const double r = sqrt(dx * dx + dy * dy);
+    *hx = 0.0, *hy = 0.0;
+    if (r > 0.0) {
+        const double ux = dx / r, uy = dy / r;
+        const double uq = ux * qx + uy * qy, k = (r - d) / r;
+        *hx = -inv_var * (ux * uq + k * (qx - ux * uq));
+        *hy = -inv_var * (uy * uq + k * (qy - uy * uq));
+    }
 }
 
 // ---- the R2 Gaussian of the residual (dx, dy), and its d/d(dx, dy): p[2..4] = upper triangle of the precision, p[5] = log norm

@@ -201,6 +201,49 @@ def _se2_tangent_score(tx, ty, w, precision):
             gvw + gvx * (da * tx + 0.5 * ty) + gvy * (da * ty - 0.5 * tx) + dl)
 
 
+_SERIES2_H = 0.3
+
+
+def _log_map_curvature(w, a):
+    """The second derivatives in w of a = h cot h and of the log-det term: a'' = (a - 1) / (2 sin^2 h) and
+    l'' = (1 / sin^2 h - 1 / h^2) / 2, differences of terms of size 1 / h^2 that leave -1/6 and 1/6: the plain forms lose
+    3 eps / h^2 and 6 eps / h^2 relative.  Below |h| = 0.3 the Taylor series through h^16 replace them: there the plain
+    forms have lost 33 and 67 roundings and the first dropped series terms are under half a rounding (the same switch and
+    the same balance as csrc/factor_model.h)."""
+    h = 0.5 * np.asarray(w, dtype=np.float64)
+    ser = np.abs(h) < _SERIES2_H
+    h2 = np.where(ser, h * h, 0.0)
+    dda_s = -(1.0 / 6.0 + h2 * (1.0 / 15.0 + h2 * (1.0 / 63.0 + h2 * (2.0 / 675.0 + h2 * (1.0 / 2079.0 + h2 * (
+        1382.0 / 19348875.0 + h2 * (2.0 / 200475.0 + h2 * (14468.0 / 10854718875.0 + h2 * (43867.0 / 254766637125.0)))))))))
+    ddl_s = 1.0 / 6.0 + h2 * (1.0 / 30.0 + h2 * (1.0 / 189.0 + h2 * (1.0 / 1350.0 + h2 * (1.0 / 10395.0 + h2 * (
+        691.0 / 58046625.0 + h2 * (2.0 / 1403325.0 + h2 * (3617.0 / 21709437750.0 + h2 * (43867.0 / 2292899734125.0))))))))
+    hp = np.where(ser, 1.0, h)
+    is2 = 1.0 / np.sin(hp) ** 2
+    return np.where(ser, dda_s, 0.5 * (a - 1.0) * is2), np.where(ser, ddl_s, 0.5 * (is2 - 1.0 / (hp * hp)))
+
+
+def _se2_tangent_hvp(tx, ty, w, precision, vtx, vty, vw):
+    """(gtx, gty, and the derivative of `_se2_tangent_score` along (vtx, vty, vw)): the Hessian of the tangent density times
+    a direction, line by line the derivative of the score (csrc/factor_model.h: se2_tangent_hvp)."""
+    a, da, dl = _log_map_terms(w)
+    dda, ddl = _log_map_curvature(w, a)
+    h = 0.5 * w
+    P = 0.5 * (precision + precision.T)
+    vx, vy = a * tx + h * ty, a * ty - h * tx
+    gvx = -(P[0, 0] * vx + P[0, 1] * vy + P[0, 2] * w)
+    gvy = -(P[0, 1] * vx + P[1, 1] * vy + P[1, 2] * w)
+    jx, jy = da * tx + 0.5 * ty, da * ty - 0.5 * tx
+    dvx, dvy = a * vtx + h * vty + jx * vw, a * vty - h * vtx + jy * vw
+    dgvx = -(P[0, 0] * dvx + P[0, 1] * dvy + P[0, 2] * vw)
+    dgvy = -(P[0, 1] * dvx + P[1, 1] * dvy + P[1, 2] * vw)
+    dgvw = -(P[0, 2] * dvx + P[1, 2] * dvy + P[2, 2] * vw)
+    return (a * gvx - h * gvy, h * gvx + a * gvy,
+            a * dgvx - h * dgvy + (da * gvx - 0.5 * gvy) * vw,
+            h * dgvx + a * dgvy + (0.5 * gvx + da * gvy) * vw,
+            dgvw + dgvx * jx + dgvy * jy + gvx * (dda * vw * tx + da * vtx + 0.5 * vty)
+            + gvy * (dda * vw * ty + da * vty - 0.5 * vtx) + ddl * vw)
+
+
 def _range_log_pdf(r, d, sigma):
     delta = r - d
     return _gaussian_log_norm(sigma ** 2) - 0.5 * delta * delta * (1.0 / sigma ** 2)
@@ -213,6 +256,19 @@ def _range_score(diff, r, d, sigma):
     ok = r > 0
     c[ok] = -(r[ok] - d) / (sigma ** 2 * r[ok])
     return c[:, None] * diff
+
+
+def _range_hess(diff, r, d, sigma):
+    """The block in ta of the Hessian of log N(|ta - tb| - d; 0, sigma^2), [n, 2, 2]: with u = (ta - tb) / r and
+    delta = r - d it is -[u u' + (delta / r) (I - u u')] / sigma^2 (the tb-tb block is the same, the ta-tb block its
+    negative), and the zero block at r = 0 exactly, like the score."""
+    out = np.zeros((r.shape[0], 2, 2))
+    ok = r > 0
+    u = diff[ok] / r[ok][:, None]
+    uu = u[:, :, None] * u[:, None, :]
+    k = ((r[ok] - d) / r[ok])[:, None, None]
+    out[ok] = -(uu + k * (np.eye(2) - uu)) / sigma ** 2
+    return out
 
 
 def _as_points(x, width: int) -> np.ndarray:
@@ -293,6 +349,16 @@ class UnarySE2ApproximateGaussianPriorFactor(ExplicitPriorFactor, UnaryFactor):
         tx, ty, w, c, s = self._residual(x)
         gtx, gty, gw = _se2_tangent_score(tx, ty, w, self._precision)
         return np.stack([c * gtx - s * gty, s * gtx + c * gty, gw], 1)
+
+    def hess_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """d^2 log_pdf / d(x, y, theta)^2, [n, 3, 3] float64: column k is the derivative of `grad_x_log_pdf` along e_k."""
+        tx, ty, w, c, s = self._residual(x)
+        one, zero = np.ones_like(w), np.zeros_like(w)
+        out = np.empty((w.shape[0], 3, 3))
+        for k, (vx, vy, vw) in enumerate(((one, zero, zero), (zero, one, zero), (zero, zero, one))):
+            _, _, htx, hty, hw = _se2_tangent_hvp(tx, ty, w, self._precision, c * vx + s * vy, c * vy - s * vx, vw)
+            out[:, :, k] = np.stack([c * htx - s * hty, s * htx + c * hty, hw], 1)
+        return out
 
     def density_record(self) -> dict:
         return dict(code="PRIOR_SE2", a=self.var, b=None, cand=[],
@@ -413,6 +479,24 @@ class SE2RelativeGaussianLikelihoodFactor(LikelihoodFactor, BinaryFactor, OdomFa
         gx, gy = ci * grx - si * gry, si * grx + ci * gry           # d/d(x_j, y_j)
         return np.stack([-gx, -gy, grx * uy - gry * ux - gw, gx, gy, gw], 1)
 
+    def hess_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """d^2 log_pdf / d[T_i | T_j]^2, [n, 6, 6] float64: column k is the derivative of `grad_x_log_pdf` along e_k
+        (d u / d th_i = (uy, -ux); the rotation back into the world frame turns with th_i)."""
+        tx, ty, w, co, so, ci, si, ux, uy = self._residual(x)
+        out = np.empty((w.shape[0], 6, 6))
+        for k in range(6):
+            v = [np.full_like(w, float(j == k)) for j in range(6)]
+            ddx, ddy = v[3] - v[0], v[4] - v[1]
+            dux, duy = ci * ddx + si * ddy + uy * v[2], ci * ddy - si * ddx - ux * v[2]
+            gtx, gty, htx, hty, hw = _se2_tangent_hvp(tx, ty, w, self._precision, co * dux + so * duy, co * duy - so * dux,
+                                                      v[5] - v[2])
+            grx, gry = co * gtx - so * gty, so * gtx + co * gty
+            hrx, hry = co * htx - so * hty, so * htx + co * hty
+            hx = ci * hrx - si * hry - (si * grx + ci * gry) * v[2]
+            hy = si * hrx + ci * hry + (ci * grx - si * gry) * v[2]
+            out[:, :, k] = np.stack([-hx, -hy, hrx * uy + grx * duy - hry * ux - gry * dux - hw, hx, hy, hw], 1)
+        return out
+
     def density_record(self) -> dict:
         return dict(code="REL_SE2", a=self.var1, b=self.var2, cand=[],
                     p=[float(t) for t in self.observation] + _sym_upper(self._precision) + [self._log_norm])
@@ -515,6 +599,16 @@ class SE2R2RangeGaussianLikelihoodFactor(LikelihoodFactor, BinaryFactor):
         g = _range_score(diff, r, self._observation[0], self._sigma)
         out = np.zeros_like(x)
         out[:, i1], out[:, i2] = g, -g
+        return out
+
+    def hess_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """d^2 log_pdf / d[var1 | var2]^2, [n, w, w] float64: the range block on the two ends' positions (negated across
+        them), 0 in a heading row or column, and the zero block at a range of exactly 0."""
+        x, i1, i2, diff, r = self._residual(x)
+        h = _range_hess(diff, r, self._observation[0], self._sigma)
+        out = np.zeros((x.shape[0], x.shape[1], x.shape[1]))
+        out[:, i1[:, None], i1[None, :]], out[:, i2[:, None], i2[None, :]] = h, h
+        out[:, i1[:, None], i2[None, :]], out[:, i2[:, None], i1[None, :]] = -h, -h
         return out
 
     def density_record(self) -> dict:
@@ -624,6 +718,26 @@ class BinaryFactorMixture(LikelihoodFactor):
         out = np.zeros_like(x)
         for k, c in enumerate(self.components):
             out[:, self.comp2idx[c]] += r[k][:, None] * c.grad_x_log_pdf(x[:, self.comp2idx[c]])
+        return out
+
+    def hess_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """d^2 log_pdf / dx^2 = sum_k r_k (H_k + g_k g_k') - g g' with the softmax weights r of `grad_x_log_pdf`, the
+        components' gradients g_k and Hessians H_k in the factor's columns and g = sum_k r_k g_k, [n, w, w] float64.  Evaluated
+        as sum_k r_k (H_k + (g_k - g)(g_k - g)'), the same matrix (sum_k r_k = 1) without the cancellation of |g|^2 where one
+        component carries the weight."""
+        x, terms = self._terms(x)
+        e = np.exp(terms - terms.max(0))
+        r = e / e.sum(0)
+        out = np.zeros((x.shape[0], x.shape[1], x.shape[1]))
+        gs = np.zeros((len(self.components),) + x.shape)
+        for k, c in enumerate(self.components):
+            idx = self.comp2idx[c]
+            gs[k][:, idx] = c.grad_x_log_pdf(x[:, idx])
+            out[:, idx[:, None], idx[None, :]] += r[k][:, None, None] * c.hess_x_log_pdf(x[:, idx])
+        g = (r[:, :, None] * gs).sum(0)
+        for k in range(len(self.components)):
+            d = gs[k] - g
+            out += r[k][:, None, None] * (d[:, :, None] * d[:, None, :])
         return out
 
     def density_record(self) -> dict:
@@ -773,6 +887,11 @@ class UnaryR2GaussianPriorFactor(ExplicitPriorFactor, UnaryFactor):
         P = np.linalg.inv(self._covariance)
         return -self._residual(x) @ (0.5 * (P + P.T))
 
+    def hess_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """-precision at every point, [n, 2, 2] float64."""
+        P = np.linalg.inv(self._covariance)
+        return np.broadcast_to(-0.5 * (P + P.T), (_as_points(x, 2).shape[0], 2, 2)).copy()
+
     def density_record(self) -> dict:
         return dict(code="PRIOR_R2", a=self.var, b=None, cand=[],
                     p=[float(self._mu[0]), float(self._mu[1])] + _sym_upper(np.linalg.inv(self._covariance)) +
@@ -841,6 +960,10 @@ class UnaryR2RangeGaussianPriorFactor(ExplicitPriorFactor, UnaryFactor):
     def grad_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
         """d log_pdf / dx, [n, 2] float64: the range term's derivative with one end at the centre; 0 at the centre itself."""
         return _range_score(*self._residual(x), self._mu, self._sigma)
+
+    def hess_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """d^2 log_pdf / dx^2, [n, 2, 2] float64: the range block with one end at the centre; 0 at the centre itself."""
+        return _range_hess(*self._residual(x), self._mu, self._sigma)
 
     def density_record(self) -> dict:
         return dict(code="PRIOR_R2_RANGE", a=self.var, b=None, cand=[],
@@ -929,6 +1052,12 @@ class R2RelativeGaussianLikelihoodFactor(LikelihoodFactor, BinaryFactor, OdomFac
         P = np.linalg.inv(self._covariance)
         g = -self._residual(x) @ (0.5 * (P + P.T))
         return np.concatenate([-g, g], 1)
+
+    def hess_x_log_pdf(self, x: np.ndarray) -> np.ndarray:
+        """d^2 log_pdf / d[var1 | var2]^2, [n, 4, 4] float64: -precision on both diagonal blocks, +precision across."""
+        P = np.linalg.inv(self._covariance)
+        P = 0.5 * (P + P.T)
+        return np.broadcast_to(np.block([[-P, P], [P, -P]]), (_as_points(x, 4).shape[0], 4, 4)).copy()
 
     def density_record(self) -> dict:
         return dict(code="REL_R2", a=self.var1, b=self.var2, cand=[],

@@ -32,6 +32,7 @@ EXPORTS = [
     "nfisam_sample_moments", "nfisam_sample_quantiles",
     "nfisam_sample_modes", "nfisam_sample_modes_merge",
     "nfisam_factor_graph_score", "nfisam_factor_graph_score_scratch_count",
+    "nfisam_factor_graph_hvp", "nfisam_factor_graph_hvp_scratch_count",
     "nfisam_sample_ksd", "nfisam_sample_ksd_scratch_count",
     "nfisam_sample_svgd", "nfisam_sample_svgd_scratch_count", "nfisam_sample_step",
 ]
@@ -120,6 +121,7 @@ def lib():
         _lib.nfisam_nsf_train_plan_enqueued.restype = C.c_long
         _lib.nfisam_sample_mmd_scratch_count.restype = C.c_size_t
         _lib.nfisam_factor_graph_score_scratch_count.restype = C.c_size_t
+        _lib.nfisam_factor_graph_hvp_scratch_count.restype = C.c_size_t
         _lib.nfisam_sample_ksd_scratch_count.restype = C.c_size_t
         _lib.nfisam_sample_svgd_scratch_count.restype = C.c_size_t
         for name in EXPORTS:
@@ -1160,6 +1162,58 @@ def factor_graph_score_t(terms: np.ndarray, St, device, terms_dev=None, gather=N
                                                    _ptr(dev["row_off"]), _ptr(dev["row_slot"]), _ptr(Gt), _ptr(vals),
                                                    _stream()), "nfisam_factor_graph_score")
     return (Gt, vals) if slots else Gt
+
+
+# ---- Hessian-vector products of the joint density (nfisam_factor_graph_hvp) ------------------------------------------------------
+def factor_graph_hvp(terms: np.ndarray, S, V, device, terms_dev=None, gather=None, score=False, slots=False):
+    """H v at the n rows of S along the rows of V (nfisam_factor_graph_hvp): row p of the result is
+    (d^2 log p / dx dx')(S_p) V_p.  `terms`, S, `terms_dev`, `gather`: as `factor_graph_score` takes them; V [n, total_dim]
+    (tensor or numpy, brought to float64).  Launched on the current stream.
+    -> H v [n, total_dim] float64 device tensor (a view of the column-major result); with score=True: (H v, G), G being
+    `factor_graph_score`'s result bit for bit, from the same first pass; with slots=True the slot values [n_slots, n] of H v
+    are appended."""
+    total_dim = _points_width(S)
+    if not (torch.is_tensor(V) or isinstance(V, np.ndarray)) or tuple(V.shape) != tuple(S.shape):
+        raise ValueError("V must be a [n, total_dim] tensor or array of S's shape")
+    if gather is None:
+        gather = pack_score_gather(terms, total_dim)                   # (checks the table)
+    Vt = V.to(device=device, dtype=torch.float64).t().contiguous() if torch.is_tensor(V) else \
+        torch.from_numpy(np.ascontiguousarray(V.T, dtype=np.float64)).to(device)
+    out = factor_graph_hvp_t(terms, _columns(S, device), Vt, device, terms_dev=terms_dev, gather=gather, score=score, slots=slots)
+    if not (score or slots):
+        return out.t()
+    return tuple(o.t() if i < 1 + bool(score) else o for i, o in enumerate(out))
+
+
+def factor_graph_hvp_t(terms: np.ndarray, St, Vt, device, terms_dev=None, gather=None, score=False, slots=False):
+    """`factor_graph_hvp` on the COLUMN-major matrices St [total_dim, n] (contiguous float32 device tensor) and Vt (contiguous
+    float64 tensor of St's shape on St's device: ValueError otherwise, before any launch).
+    -> Ht [total_dim, n] float64; with score=True: (Ht, Gt); with slots=True the slot values of H v are appended."""
+    total_dim, n = _points_shape_t(St)
+    if not torch.is_tensor(Vt) or Vt.dtype != torch.float64 or not Vt.is_contiguous() or tuple(Vt.shape) != (total_dim, n):
+        raise ValueError("Vt must be a contiguous float64 [total_dim, n] tensor of St's shape")
+    if Vt.device != St.device:
+        raise ValueError("St and Vt must be on the same device")
+    if gather is None:
+        gather = pack_score_gather(terms, total_dim)                   # (checks the table)
+    elif gather["row_off"].shape[0] != total_dim + 1 or gather["slot_off"].shape[0] != terms.shape[0]:
+        raise ValueError("gather was packed for another table or another total_dim")
+    if total_dim > 65535:
+        raise ValueError("factor_graph_hvp: at most 65535 rows are supported, got %d" % total_dim)
+    nt, ns = int(terms.shape[0]), int(gather["n_slots"])
+    Ht = torch.zeros(total_dim, n, dtype=torch.float64, device=device)
+    Gt = torch.zeros(total_dim, n, dtype=torch.float64, device=device) if score else None
+    vals = torch.empty((2 if score else 1) * ns, n, dtype=torch.float64, device=device)      # the scratch: H v's slots, then G's
+    if nt > 0 and n > 0:
+        with torch.cuda.device(device):
+            dev = _factor_tables(device, terms, terms_dev, slot_off=gather["slot_off"], row_off=gather["row_off"],
+                                 row_slot=gather["row_slot"])
+            assert int(lib().nfisam_factor_graph_hvp_scratch_count(ns, n, int(bool(score)))) == vals.numel()
+            _check(lib().nfisam_factor_graph_hvp(_ptr(dev["terms"]), nt, _ptr(St), _ptr(Vt), total_dim, n, _ptr(dev["slot_off"]),
+                                                 ns, _ptr(dev["row_off"]), _ptr(dev["row_slot"]), _ptr(Ht),
+                                                 _ptr(Gt) if score else None, _ptr(vals), _stream()), "nfisam_factor_graph_hvp")
+    out = (Ht,) + ((Gt,) if score else ()) + ((vals[:ns],) if slots else ())
+    return out if len(out) > 1 else Ht
 
 
 # ---- kernel Stein discrepancy: the pairwise Stein sums (nfisam_sample_ksd) ----------------------------------------------------------

@@ -1,7 +1,8 @@
 """slam.PosteriorEvaluation -- what a trained NFiSAM solver says about its posterior, not in the reference: densities
 (`posterior_log_pdf`, `joint_log_pdf`, `joint_score`), the solver grading itself (`posterior_diagnostics`, `map_estimate`,
-`posterior_ksd`, `posterior_mmd`), what the posterior holds (`posterior_summary`, `posterior_modes`) and its samples moved
-along the joint score (`posterior_refine`, `map_refine`).
+`posterior_ksd`, `posterior_mmd`), what the posterior holds (`posterior_summary`, `posterior_modes`), its samples moved
+along the joint score (`posterior_refine`, `map_refine`) and the joint density's curvature (`joint_hessian_product`,
+`map_newton`, `laplace_approximation`).
 
 A mixin of `slam.NFiSAM.NFiSAM`: the walk (`posterior_launch`, `_post_columns`, `_posterior_table`) and the solver's state
 are reached through `self`.  Every public method goes through ONE front, `_eval_points`, which makes the checks that need no
@@ -459,6 +460,178 @@ class PosteriorEvaluation:
         return dict(map_sample={v: row[pcol[v]:pcol[v] + v.dim].copy() for v in self._elimination_ordering}, log_p=out_lp,
                     start_log_p=start_log_p, improved=bool(out_lp > start_log_p), climbers=best_lp.cpu().numpy(),
                     steps=res["steps"], top=top, n=pts.rows)
+
+    # ---- curvature: Hessian-vector products, truncated-Newton MAP ascent, the Laplace approximation at a mode ---------------------
+    def _hvp_launch(self, pts: EvalPoints, Vt, score: bool = False):
+        """Ht (and, with `score`, Gt) [total_dim, n] float64 on the device: the table and gather lists of `_score_launch`."""
+        cache = self._joint_terms(pts.pcol)
+        g = cache.get("gather")
+        if g is None or g["row_off"].shape[0] != pts.total_dim + 1:
+            g = cache["gather"] = _nh.pack_score_gather(cache["terms"], pts.total_dim)
+        on = cache.setdefault("gather_dev", {})                        # (the cache is made anew whenever the table grows)
+        if pts.rows and (pts.device not in on or on[pts.device]["row_off"].shape[0] != pts.total_dim + 1):
+            so, ro, rs = _nh.upload(g["slot_off"], g["row_off"], g["row_slot"], device=pts.device, cached=True)
+            on[pts.device] = dict(slot_off=so, row_off=ro, row_slot=rs, n_slots=g["n_slots"])
+        # a Newton step is dozens of these calls on one table: the lists stay on the device (Plaza1's are past the staging ring)
+        return _nh.factor_graph_hvp_t(cache["terms"], pts.St, Vt, pts.device, gather=on.get(pts.device, g), score=score,
+                                      terms_dev=self._joint_terms_dev(cache, pts.device, pts.rows))
+
+    def _hvp_colours(self, pts: EvalPoints):
+        """The column classes of `Statistics.probe_colours` for the joint Hessian's sparsity (columns coupled by one factor),
+        kept next to the cached table: diag(H) then costs one product per class.  No device."""
+        from utils import Statistics as ST
+        cache = self._joint_terms(pts.pcol)
+        c = cache.get("colours")
+        if c is None or c[0] != pts.total_dim:
+            slot_off, rows = _nh._slot_rows(cache["terms"])
+            ends = list(slot_off[1:]) + [rows.size]
+            c = cache["colours"] = (pts.total_dim, ST.probe_colours([rows[a:b] for a, b in zip(slot_off, ends)], pts.total_dim))
+        return c[1]
+
+    def joint_hessian_product(self, samples, vectors) -> np.ndarray:
+        """H v of the joint density's Hessian H = d^2 log p(X, Z) / dx dx' at n points along one direction per point, on the
+        device in float64 at the float32 points (nfisam_factor_graph_hvp: the derivative of `joint_score`'s smooth formula;
+        nothing of size total_dim^2 is formed).  Not in the reference.
+
+        samples: as `joint_log_pdf`.  vectors: mapping variable -> [n, dim] (every variable of the ordering), or an
+        [n, total_dim] array in the columns of `_post_columns`.  -> np.ndarray [n, total_dim] float64 in those columns.
+        Raises what `joint_score` raises, and ValueError for vectors of a wrong shape -- before anything is launched."""
+        what = "joint_hessian_product"
+        pts = self._eval_points(what, samples, factors=True)
+        if isinstance(vectors, dict) or hasattr(vectors, "keys"):
+            values, rows = self._check_points(vectors, what, nouns=("vectors lack", "vectors", "ragged vectors", "n"), host=True)
+            if rows != pts.rows:
+                raise ValueError("%s: vectors have %d rows, the samples %d" % (what, rows, pts.rows))
+            V = np.zeros((pts.rows, pts.total_dim))
+            for v, a in values.items():
+                V[:, pts.pcol[v]:pts.pcol[v] + v.dim] = a
+        else:
+            V = vectors.detach().cpu().numpy() if torch.is_tensor(vectors) else np.asarray(vectors)
+            if V.ndim != 2 or V.shape != (pts.rows, pts.total_dim):
+                raise ValueError("%s: vectors must be [n, total_dim] = %s, got %s" % (what, (pts.rows, pts.total_dim), tuple(V.shape)))
+        Vt = torch.from_numpy(np.ascontiguousarray(V.T, dtype=np.float64)).to(pts.device)
+        return self._hvp_launch(pts, Vt).t().cpu().numpy()
+
+    def map_newton(self, samples=None, n: int = None, top: int = 8, steps: int = 20, cg_iters: int = None, rtol: float = 1e-8,
+                   damping: float = 0.0, standardise: bool = True, gtol: float = None, backtracks: int = None) -> dict:
+        """A MAP estimate by truncated-Newton ascent: the `top` points of highest joint density log p(X, Z) among `samples` (or
+        a fresh posterior draw of `n`) each take up to `steps` Newton steps (`Statistics.newton_refine_t`): the score and the
+        Hessian-vector products come from one kernel (nfisam_factor_graph_hvp), the step solves (-H + damping) d = g by
+        matrix-free conjugate gradients (at most `cg_iters` products; None: TWICE the number of columns in use), preconditioned
+        with diag(H) at the points (one product per class of columns that no factor couples: 6 on the small range graph, 12 on Plaza1), and backtracks
+        by halving with one log p launch per trial.  (In exact arithmetic as many products as columns end the solve; in float64
+        they do not on a graph that knows one pose to millimetres and a landmark to metres: on the small range problem,
+        cond(-H) = 1.5e7 and 2e4 with the diagonal scaled out, 22 products leave the step so inexact that 20 Newton steps are
+        needed where 44 products need 4.)  A point only ever moves upwards, so the result is never below `map_estimate`
+        on the same points; unlike `map_refine` (which is not changed) the ascent knows when it has arrived: `grad_norm` and
+        `converged`.  damping: added to -H's diagonal, in units of 1 / spread^2 of every column with `standardise` (the spreads
+        of ALL the given points, `_column_scale`), else in the column's own 1 / unit^2.  gtol, backtracks: None = the defaults
+        `newton_refine_t` derives from the float32 floor of the points (1e-3 of the standardised score; 10 halvings).
+        -> dict: map_sample (variable -> [dim] float32), log_p (its joint log density), start_log_p (the best of the input:
+        `map_estimate`'s), improved, climbers ([top] float64: the log p every climber reached, by falling start), steps (taken),
+        grad_norm ([top]: max_c |g_c| spread_c at every climber's point, |g_c| without `standardise`), converged ([top] bool:
+        grad_norm <= gtol), negative_curvature ([top] bool: the last step's conjugate gradients met a direction along which
+        H is not negative), top (min(top, n)), n.
+        No solver state changes; random numbers are drawn only when `samples` is None.  Raises what `joint_score` raises, and
+        ValueError naming this method for a bad option -- before anything is launched."""
+        from utils import Statistics as ST
+        what = "map_newton"
+        pts = self._eval_points(what, samples, n, factors=True, nonempty=True)
+        flags, cols = self._column_flags(pts)
+        try:
+            if isinstance(top, bool) or int(top) != top or int(top) < 1:
+                raise ValueError("top must be an integer >= 1, got %r" % (top,))
+            if np.ndim(damping) != 0:
+                raise ValueError("damping is one finite value >= 0")
+            opt = ST.check_newton_options(pts.total_dim, steps, 2 * int(cols.size) if cg_iters is None else cg_iters, rtol, damping,
+                                          ST.NEWTON_GTOL if gtol is None else gtol,
+                                          ST.NEWTON_BACKTRACKS if backtracks is None else backtracks, circular=flags)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (what, e)) from None
+        scale = self._column_scale(pts, flags, cols, bool(standardise))
+        top = min(int(top), pts.rows)
+        log_p = self._joint_launch(pts)
+        start_lp, idx = torch.topk(log_p, top)                         # by falling log p
+        work = pts.over(pts.St[:, idx].contiguous())                   # a copy: never the walk's own tensor
+        res = ST.newton_refine_t(work.St, lambda Xt, Vt: self._hvp_launch(work, Vt, score=True), lambda Xt: self._joint_launch(
+            work.over(Xt)), opt["steps"], opt["cg_iters"], opt["rtol"], float(damping) * scale * scale, opt["gtol"],
+            opt["backtracks"], scale=scale, circular=flags, colours=self._hvp_colours(pts))
+        k = int(torch.argmax(res["log_p"]).item())
+        row, pcol = work.St[:, k].cpu().numpy(), pts.pcol
+        out_lp, start_log_p = float(res["log_p"][k].item()), float(start_lp[0].item())
+        return dict(map_sample={v: row[pcol[v]:pcol[v] + v.dim].copy() for v in self._elimination_ordering}, log_p=out_lp,
+                    start_log_p=start_log_p, improved=bool(out_lp > start_log_p), climbers=res["log_p"].cpu().numpy(),
+                    steps=res["steps"], grad_norm=res["grad_norm"].cpu().numpy(), converged=res["converged"].cpu().numpy(),
+                    negative_curvature=res["negative_curvature"].cpu().numpy(), top=top, n=pts.rows)
+
+    def laplace_approximation(self, point=None, variables=None, pairs=None, cg_iters: int = None, rtol: float = 1e-8,
+                              max_columns: int = 256, **newton) -> dict:
+        """The Gaussian summary of a mode: marginal blocks of the covariance -H^-1 of the Laplace approximation of p(X, Z) at
+        `point` (variable -> [dim]; None: `map_newton(**newton)`'s map_sample) -- what a Gaussian SLAM back end reports, and
+        the companion of `posterior_modes`: that says where the hypotheses are, this how wide the joint density is at one.
+        Every requested column c is one right-hand side e_c: the point is replicated once per requested column and ONE
+        batched conjugate-gradient run (`Statistics.conjugate_gradient_t` on nfisam_factor_graph_hvp, preconditioned with
+        diag(H) from one product per class of columns that no factor couples; at most `cg_iters` products, None: twice the
+        number of columns in use, see `map_newton`) solves -H x = e_c for all of them; nothing of size total_dim^2 is formed.  `residual` says how far
+        the run came: on the small range problem as many products as columns leave it at 158 and the blocks 28 % off, twice as
+        many reach 8e-9 and the blocks agree with the dense inverse of the host Hessian to 3.5e-11.
+        variables: whose [dim, dim] blocks (None: all); pairs: (a, b) tuples whose joint [dim_a + dim_b] blocks, as
+        `posterior_summary` takes them.  At most `max_columns` (default 256) columns may be requested: ValueError beyond.
+        -> dict: point (variable -> [dim] float32), log_p (at the point), cov (variable -> [dim, dim], symmetrised), pair_cov
+        ((a, b) -> [dim_a + dim_b, dim_a + dim_b]), residual (the largest |r| / |b| the runs ended with), negative_curvature
+        (bool: some run met a direction along which H is not negative definite -- the point is no strict mode and the blocks
+        are then no covariance; reported, not raised).  `log_evidence` is left out: it needs log det(-H), which products
+        alone do not give cheaply.
+        No solver state changes; random numbers are drawn only for point=None with newton's samples=None.  Raises what
+        `joint_score` raises, and ValueError naming this method for a bad point or option -- before anything is launched."""
+        from utils import Statistics as ST
+        what = "laplace_approximation"
+        if point is None:
+            point = self.map_newton(**newton)["map_sample"]
+        elif newton:
+            raise ValueError("%s: %s only apply when the point is found by map_newton (point=None)" % (what, sorted(newton)))
+        pts = self._eval_points(what, {v: (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).reshape(1, -1)
+                                       for v, a in point.items()}, factors=True, nonempty=True)
+        known = set(self._elimination_ordering)
+        variables = list(self._elimination_ordering) if variables is None else list(variables)
+        pairs = [tuple(p) for p in pairs] if pairs is not None else []
+        for p in pairs:
+            if len(p) != 2:
+                raise ValueError("%s: a pair is a tuple (a, b) of two variables" % what)
+        for v in variables + [v for p in pairs for v in p]:
+            if v not in known:
+                raise ValueError("%s: variable %s is not in the elimination ordering" % (what, getattr(v, "name", v)))
+        flags, used = self._column_flags(pts)
+        want = sorted(set(pts.pcol[v] + c for v in variables + [v for p in pairs for v in p] for c in range(v.dim)))
+        try:
+            if isinstance(max_columns, bool) or int(max_columns) != max_columns or int(max_columns) < 1:
+                raise ValueError("max_columns must be an integer >= 1, got %r" % (max_columns,))
+            if not want:
+                raise ValueError("no variable to summarise")
+            if len(want) > int(max_columns):
+                raise ValueError("%d columns are requested, max_columns is %d" % (len(want), int(max_columns)))
+            opt = ST.check_newton_options(pts.total_dim, 0, 2 * int(used.size) if cg_iters is None else cg_iters, rtol)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (what, e)) from None
+        at = {c: j for j, c in enumerate(want)}
+        work = pts.over(pts.St[:, :1].expand(pts.total_dim, len(want)).contiguous())
+        Bt = torch.zeros(pts.total_dim, len(want), dtype=torch.float64, device=pts.device)
+        Bt[torch.as_tensor(want, device=pts.device), torch.arange(len(want), device=pts.device)] = 1.0
+        hvp = lambda Vt: self._hvp_launch(work, Vt)
+        diag = ST.hessian_diagonal_t(hvp, self._hvp_colours(pts), pts.total_dim, len(want), pts.device)
+        cg = ST.conjugate_gradient_t(hvp, Bt, opt["cg_iters"], opt["rtol"], precond=ST.inverse_diagonal(diag, None))
+        X = cg["x"].cpu().numpy()
+
+        def block(vs):
+            rows = [pts.pcol[v] + c for v in vs for c in range(v.dim)]
+            m = X[np.ix_(rows, [at[c] for c in rows])]
+            return 0.5 * (m + m.T)
+
+        row = pts.St[:, 0].cpu().numpy()
+        return dict(point={v: row[pts.pcol[v]:pts.pcol[v] + v.dim].copy() for v in self._elimination_ordering},
+                    log_p=float(self._joint_launch(pts)[0].item()), cov={v: block((v,)) for v in variables},
+                    pair_cov={p: block(p) for p in pairs}, residual=float(cg["residual"].max().item()),
+                    negative_curvature=bool(cg["negative_curvature"].any().item()))
 
     # ---- the solver graded against a reference sample set --------------------------------------------------------
     def posterior_mmd(self, reference, samples=None, n: int = None, variables=None, blocks=None, columns: str = "xy",

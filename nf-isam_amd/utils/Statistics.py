@@ -700,3 +700,223 @@ def stein_variational_refine(x, score, blocks, steps, step_size, sigma=None, sca
     hist = np.zeros((n, D))
     hist[:, res["cols"]] = res["hist"].cpu().numpy().T
     return dict(x=Xt.t().cpu().numpy().copy(), hist=hist, steps=res["steps"])
+
+
+# ---- curvature: matrix-free conjugate gradients on Hessian-vector products, truncated Newton ascent (nfisam_factor_graph_hvp) ----
+NEWTON_GTOL, NEWTON_BACKTRACKS = 1e-3, 10
+
+
+def check_newton_options(width, steps=0, cg_iters=None, rtol=1e-8, damping=0.0, gtol=NEWTON_GTOL, backtracks=NEWTON_BACKTRACKS,
+                         scale=None, circular=None):
+    """Every option of `conjugate_gradient_t` / `newton_refine_t`, checked with no device: steps an integer >= 0; cg_iters an
+    integer >= 1 (None: width, the exact solve of a quadratic); rtol in (0, 1); damping one finite value >= 0 or one per
+    column; gtol positive and finite; backtracks an integer in 0..60; scale one finite value >= 0 per column (None: ones; 0: a
+    column that does not count in the gradient norm); circular one flag per column.
+    -> dict(steps, cg_iters, rtol, damping [width], gtol, backtracks, scale [width], flags [width])."""
+    def whole(name, v, lo, hi=None):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
+            raise ValueError("%s must be an integer %s, got %r" % (name, ">= %d" % lo if hi is None else "in %d..%d" % (lo, hi), v))
+        return int(v)
+    width = whole("width", width, 1)
+    steps = whole("steps", steps, 0)
+    cg_iters = width if cg_iters is None else whole("cg_iters", cg_iters, 1)
+    backtracks = whole("backtracks", backtracks, 0, 60)
+    if np.ndim(rtol) != 0 or not (np.isfinite(rtol) and 0.0 < rtol < 1.0):
+        raise ValueError("rtol must lie in (0, 1), got %r" % (rtol,))
+    if np.ndim(gtol) != 0 or not (np.isfinite(gtol) and gtol > 0.0):
+        raise ValueError("gtol must be positive and finite, got %r" % (gtol,))
+    damp = np.asarray(0.0 if damping is None else damping, dtype=np.float64).reshape(-1)
+    damp = np.broadcast_to(damp, (width,)).copy() if damp.size == 1 else damp
+    if damp.size != width or not np.all(np.isfinite(damp) & (damp >= 0)):
+        raise ValueError("damping is one finite value >= 0, or one per column (%d)" % width)
+    sc = np.ones(width) if scale is None else np.asarray(scale, dtype=np.float64).reshape(-1)
+    if sc.size != width or not np.all(np.isfinite(sc) & (sc >= 0)):
+        raise ValueError("scale: one finite value >= 0 per column (%d)" % width)
+    return dict(steps=steps, cg_iters=cg_iters, rtol=float(rtol), damping=damp, gtol=float(gtol), backtracks=backtracks, scale=sc,
+                flags=_column_flags(circular, width))
+
+
+def conjugate_gradient_t(hvp, Bt, iters, rtol, damping=None, precond=None):
+    """Solves (-H_p + diag(damping)) d_p = b_p for every column p of Bt [D, n] (float64 tensor) at once by conjugate
+    gradients with per-point scalars, never forming a matrix: `hvp(Vt)` returns Ht with Ht[:, p] = H_p Vt[:, p] (float64, the
+    layout of `nfisam_hip.factor_graph_hvp_t`, which is the hot path; the vector work is torch float64 where Bt lies).  H is the
+    Hessian of a log density: at a mode -H is positive definite.  damping: None, one value or one per row of Bt.
+    A point stops when its residual is <= rtol |b|, after `iters` products, or when it meets a direction p with
+    p'(-H + damping) p <= 0 (or not a number): it then keeps what it has (Steihaug's rule), b itself on the first iteration.
+    A stopped point's columns are frozen by masks: the batch keeps its shape, so the others' bits are those of a run without it.
+    precond: None, or a positive float64 tensor [D, n] (or [D, 1]) M^-1, the inverse of a diagonal that resembles -H + damping
+    (`hessian_diagonal_t`): the iteration is then the preconditioned one -- a SLAM Hessian holds 1 / sigma^2 of millimetres
+    next to 1 / sigma^2 of metres, and without its diagonal scaled out conjugate gradients do not arrive within D products.
+    The stopping rule stays the plain residual's, and a first-iteration refusal keeps M^-1 b.
+    -> dict(x [D, n], residual [n]: |r| / |b| of the iterate by the recurrence (0 for b = 0; a point that kept b itself reports
+    1), iters [n] int64: products used, negative_curvature [n] bool)."""
+    import torch
+    if not torch.is_tensor(Bt) or Bt.ndim != 2 or Bt.dtype != torch.float64:
+        raise ValueError("Bt must be a float64 [columns, points] tensor")
+    D, n = int(Bt.shape[0]), int(Bt.shape[1])
+    opt = check_newton_options(max(D, 1), cg_iters=iters, rtol=rtol, damping=damping)
+    damp = torch.from_numpy(opt["damping"]).to(Bt.device).unsqueeze(1) if opt["damping"].any() else None
+    if precond is not None and not (torch.is_tensor(precond) and precond.dtype == torch.float64 and precond.ndim == 2
+                                    and tuple(precond.shape) in ((D, n), (D, 1))):
+        raise ValueError("precond must be a float64 [columns, points] or [columns, 1] tensor")
+    X, Rt = torch.zeros_like(Bt), Bt.clone()
+    P = Bt.clone() if precond is None else precond * Bt
+    bnorm = torch.linalg.vector_norm(Bt, dim=0)
+    rs = (Rt * P).sum(0)                                              # r'z, z = M^-1 r (r'r without a preconditioner)
+    active = bnorm > 0
+    used = torch.zeros(n, dtype=torch.int64, device=Bt.device)
+    neg = torch.zeros(n, dtype=torch.bool, device=Bt.device)
+    for k in range(opt["cg_iters"]):
+        if not bool(active.any()):
+            break
+        AP = -hvp(P)
+        if damp is not None:
+            AP = AP + damp * P
+        pAp = (P * AP).sum(0)
+        bad = active & ~(pAp > 0)
+        if k == 0:
+            X = torch.where(bad.unsqueeze(0), P, X)
+        neg |= bad
+        active = active & ~bad
+        used += active
+        alpha = torch.where(active, rs / pAp, torch.zeros_like(rs))
+        X = torch.where(active.unsqueeze(0), X + alpha * P, X)
+        Rt = torch.where(active.unsqueeze(0), Rt - alpha * AP, Rt)
+        Z = Rt if precond is None else precond * Rt
+        rs_new = (Rt * Z).sum(0)
+        go = active & ~(torch.linalg.vector_norm(Rt, dim=0) <= opt["rtol"] * bnorm)
+        P = torch.where(go.unsqueeze(0), Z + (rs_new / rs) * P, P)
+        rs = torch.where(active, rs_new, rs)
+        active = go
+    ratio = torch.where(bnorm > 0, torch.linalg.vector_norm(Rt, dim=0) / bnorm, torch.zeros_like(bnorm))
+    return dict(x=X, residual=ratio, iters=used, negative_curvature=neg)
+
+
+def probe_colours(row_groups, width):
+    """Column classes for probing a sparse symmetric matrix's diagonal: `row_groups` lists, per factor, the columns the factor
+    couples (every pair inside a group may hold an entry); two columns share a class only if no group holds both, so a product
+    with a class's indicator vector shows H_cc alone in the rows c of that class.  Greedy, columns in ascending order.
+    -> list of int64 arrays that partition range(width).  No device."""
+    near = [set() for _ in range(width)]
+    for g in row_groups:
+        g = [int(c) for c in g]
+        if g and (min(g) < 0 or max(g) >= width):
+            raise ValueError("a group names a column outside the %d columns" % width)
+        for c in g:
+            near[c].update(g)
+    colour = np.full(width, -1, dtype=np.int64)
+    for c in range(width):
+        taken = {int(colour[o]) for o in near[c] if colour[o] >= 0}
+        k = 0
+        while k in taken:
+            k += 1
+        colour[c] = k
+    return [np.flatnonzero(colour == k) for k in range(int(colour.max()) + 1 if width else 0)]
+
+
+def hessian_diagonal_t(hvp, colours, width, n, device):
+    """diag(H_p) for every point p, [width, n] float64 on `device`, from len(colours) Hessian-vector products: one per class of
+    `probe_colours`, along the class's indicator vector."""
+    import torch
+    diag = torch.zeros(width, n, dtype=torch.float64, device=device)
+    for cols in colours:
+        idx = torch.as_tensor(cols, device=device)
+        V = torch.zeros(width, n, dtype=torch.float64, device=device)
+        V[idx] = 1.0
+        diag[idx] = hvp(V)[idx]
+    return diag
+
+
+def inverse_diagonal(diag_h, damp):
+    """M^-1 for `conjugate_gradient_t` from diag(H): 1 / (-H_cc + damping_c) where that is positive, else 1 (a column
+    without curvature of the right sign is left unscaled)."""
+    import torch
+    m = -diag_h if damp is None else -diag_h + damp
+    return torch.where(m > 0, 1.0 / torch.where(m > 0, m, torch.ones_like(m)), torch.ones_like(m))
+
+
+def _wrapped_step(Xt, Dt, s, flags_t):
+    """float32(x + s d) with the heading rows brought into [-pi, pi) the way `nfisam_hip.sample_step_t` does it."""
+    import torch
+    y = Xt.to(torch.float64) + s * Dt
+    f = y.to(torch.float32)
+    if flags_t is not None:
+        w = (torch.remainder(y + np.pi, 2.0 * np.pi) - np.pi).to(torch.float32)
+        inside = (w.to(torch.float64) < np.pi) & (w.to(torch.float64) >= -np.pi)
+        w = torch.where(inside | torch.isnan(y), w, torch.full_like(w, -3.1415925))      # +-float32(pi) lies outside
+        f = torch.where(flags_t, w, f)
+    return f
+
+
+def newton_refine_t(Xt, score_hvp, log_p, steps, cg_iters=None, rtol=1e-8, damping=0.0, gtol=NEWTON_GTOL,
+                    backtracks=NEWTON_BACKTRACKS, scale=None, circular=None, colours=None) -> dict:
+    """Truncated-Newton ascent of log p for every point of the COLUMN-major matrix Xt [D, n] (contiguous float32) at once, IN
+    PLACE, each point alone.  `score_hvp(Xt, Vt)` -> (Ht, Gt): the Hessian-vector products along Vt [D, n] float64 and the
+    score at Xt from one pass (`nfisam_hip.factor_graph_hvp_t(..., score=True)`); `log_p(Xt)` -> [n] float64.
+    A step: ONE `score_hvp` call with a zero direction gives g; `conjugate_gradient_t` solves (-H + diag(damping)) d = g with
+    at most `cg_iters` (None: D) further products; then the step length backtracks from 1 by halving, at most `backtracks`
+    times, every trial one `log_p` launch: the first trial with log p above the point's present value is taken, into the
+    float32 point, headings (`circular` [D]) wrapped as `sample_step_t` wraps them.  A point whose trials all fail stays, so a
+    point never falls and its present position is its best iterate.  colours: the classes of `probe_colours` for H's
+    sparsity; with them every step first reads diag(H) at the points (one product per class) and the conjugate gradients are
+    preconditioned with it.  A step is 1 + (classes) + (products) + (trials) launches, at most 2 + classes + cg_iters +
+    backtracks.  A point is converged when the scaled infinity norm of its score, max_c |g_c| / scale_c (scale
+    [D]: 1 / spread standardises, as in `stein_variational_refine_t`; 0 leaves a column out; None: ones), is <= gtol; converged
+    points take no further steps, and the loop ends when every point is.
+    The float32 floor the defaults are chosen from: next to a mode the score at a float32 point is about |H| times half the
+    float32 spacing of the coordinate.  In standardised units (|H| spread^2 about (spread / sigma)^2, about 1 when the points
+    are spread like the mode is wide) that is spacing / (2 sigma): 3.8e-4 for a coordinate of 100 m (spacing 2^-17 m) and a mode
+    1 cm wide.  gtol = 1e-3 is the next power of ten above it -- below the floor `converged` could never be reported.  A
+    Newton step is at most about one spread; a spread of 1 cm is 2^10.4 spacings at 100 m, so the 11th halving moves such a
+    coordinate by less than its spacing: backtracks = 10.
+    -> dict(log_p [n] float64 at the final points, start_log_p [n], grad_norm [n] (at the final points), converged [n] bool,
+    negative_curvature [n] bool (met by the CG of the last step a point took), steps: steps taken).  steps = 0 leaves every
+    bit alone.  Every option is checked (`check_newton_options`) before anything is launched."""
+    import torch
+    if not callable(score_hvp) or not callable(log_p):
+        raise ValueError("score_hvp and log_p must be callables")
+    if not torch.is_tensor(Xt) or Xt.ndim != 2 or Xt.dtype != torch.float32 or not Xt.is_contiguous():
+        raise ValueError("Xt must be a contiguous float32 [columns, points] tensor")
+    D, n = int(Xt.shape[0]), int(Xt.shape[1])
+    if D < 1 or n < 1:
+        raise ValueError("newton_refine: no points")
+    opt = check_newton_options(D, steps, cg_iters, rtol, damping, gtol, backtracks, scale, circular)
+    dev = Xt.device
+    inv_scale = torch.from_numpy(np.where(opt["scale"] > 0, 1.0 / np.where(opt["scale"] > 0, opt["scale"], 1.0), 0.0)).to(dev).unsqueeze(1)
+    flags_t = torch.from_numpy(opt["flags"]).to(dev).unsqueeze(1) if opt["flags"].any() else None
+    zero = torch.zeros(D, n, dtype=torch.float64, device=dev)
+    damp_t = torch.from_numpy(opt["damping"]).to(dev).unsqueeze(1) if opt["damping"].any() else None
+
+    def gradient():
+        Gt = score_hvp(Xt, zero)[1]
+        return Gt, (Gt.abs() * inv_scale).amax(0)
+
+    lp = log_p(Xt).clone()
+    start = lp.clone()
+    neg = torch.zeros(n, dtype=torch.bool, device=dev)
+    taken = 0
+    Gt, gnorm = gradient()
+    for t in range(opt["steps"]):
+        moving = ~(gnorm <= opt["gtol"])
+        if not bool(moving.any()):
+            break
+        hvp = lambda Vt: score_hvp(Xt, Vt)[0]
+        minv = None if colours is None else inverse_diagonal(hessian_diagonal_t(hvp, colours, D, n, dev), damp_t)
+        cg = conjugate_gradient_t(hvp, torch.where(moving.unsqueeze(0), Gt, zero), opt["cg_iters"], opt["rtol"], opt["damping"],
+                                  precond=minv)
+        neg = torch.where(moving, cg["negative_curvature"], neg)
+        pending, s = moving.clone(), 1.0
+        for b in range(opt["backtracks"] + 1):
+            trial = torch.where(pending.unsqueeze(0), _wrapped_step(Xt, cg["x"], s, flags_t), Xt)
+            lp_t = log_p(trial)
+            ok = pending & (lp_t > lp)
+            Xt.copy_(torch.where(ok.unsqueeze(0), trial, Xt))
+            lp = torch.where(ok, lp_t, lp)
+            pending = pending & ~ok
+            if not bool(pending.any()):
+                break
+            s *= 0.5
+        taken += 1
+        Gt, gnorm = gradient()
+    return dict(log_p=lp, start_log_p=start, grad_norm=gnorm, converged=gnorm <= opt["gtol"], negative_curvature=neg, steps=taken)
+
