@@ -397,6 +397,42 @@ int nfisam_sample_svgd(const float* Xt, int x_rows, int n, const double* Gt, con
 int nfisam_sample_step(float* Xt, int x_rows, int n, const int32_t* cols, int n_entries, const uint8_t* wrap, const double* phi,
                        double* hist, const double* eps, double alpha, double fudge, int first, nfisam_stream_t stream);
 
+/* ---- Metropolis-corrected moves: the Langevin / random-walk proposal and the accept step of n chains (sample_mcmc.hip) --------
+ * Not in the reference.  A chain is a column of Xt; h[x_rows] double >= 0 is the step length of a row in its own unit (0 freezes
+ * the row), wrap[x_rows] uint8 (nullable) marks angles: DEVICE arrays.  Xt, Yt [x_rows][n]: COLUMN-major float32 device
+ * matrices; Gx, Gy [x_rows][n]: COLUMN-major float64 (what nfisam_factor_graph_score writes).  All arithmetic float64.
+ *
+ * THE GENERATOR (a contract: DESIGN.md 3.3k): Philox4x32-10, the constants of nfisam_simulate_clique; key (seed & 0xffffffff,
+ * seed >> 32); counter (chain i, row r >> 2, step t, tag), tag 0 the normals, tag 1 the accept uniform with row word 0;
+ * u = (word + 0.5) 2^-32 in float64, inside (0, 1) exactly; the four normals of a counter block are Box-Muller (cos, sin) of
+ * (u0, u1) -> rows 4g, 4g + 1 and of (u2, u3) -> rows 4g + 2, 4g + 3.  A chain's draws depend on (seed, i, r, t) alone.
+ *
+ * nfisam_sample_propose:  Yt[r][i] = x + (h_r^2 / 2) Gx[r][i] + h_r z  (Gx NULL: the random walk x + h_r z), wrapped into
+ * [-pi, pi) where wrap[r] is set and rounded to float32 by nfisam_sample_step's rule (a wrapped value that rounds to
+ * +-float32(pi) becomes the float32 just inside -pi).  A row with h_r == 0 is copied bit for bit.  Xt is not written.  One
+ * launch, elementwise: the same bits on every call, at any n.
+ * NFISAM_ERR_ARG: a NULL pointer (Gx and wrap excepted), x_rows or n < 1, n > 65535 * 64, x_rows > 65535 * 32.
+ *
+ * nfisam_sample_accept:  per chain i, with d_r = (double)Xt[r][i] - (double)Yt[r][i] -- the values actually stored, so the ratio
+ * is exact for the move that was made -- brought into [-pi, pi] as sign(d) wrap(|d|) where wrap[r] is set (the nearest image of
+ * the wrapped normal; the caller bounds h on such rows), and a_r = h_r^2 / 2:
+ *     log_alpha[i] = (lp_y[i] - lp_x[i]) + sum_{r: h_r > 0} [ 1/2 ((-d_r - a_r Gx[r][i]) / h_r)^2 - 1/2 ((d_r - a_r Gy[r][i]) / h_r)^2 ]
+ * (Gx and Gy both NULL: no sum, a symmetric proposal -- the random walk, or an independence step with lp = log p - log q).
+ * accepted[i] = log(u) < log_alpha[i]: a NaN log_alpha rejects, lp_y = -inf rejects, lp_x = -inf with a finite lp_y accepts.  On
+ * accept column i of Yt replaces column i of Xt, column i of Gy that of Gx and lp_y[i] replaces lp_x[i]; a rejected chain keeps
+ * every bit.  Two launches, no float atomics: the row sum is taken in an order that depends on x_rows alone (a thread's rows
+ * ascending, the four waves in order, slabs of 32 rows in slab order through `scratch`), so log_alpha[i] is the same bits on
+ * every call, at any n and in any tile.  scratch: nfisam_sample_accept_scratch_count(x_rows, n) doubles on the device.
+ * NFISAM_ERR_ARG: a NULL pointer (Gx and Gy together, and wrap, excepted), Gx without Gy or the reverse, x_rows or n < 1,
+ * n > 65535 * 64, x_rows > 65535 * 32.  h is not read on the host: the Python binding refuses negative or non-finite entries
+ * before upload.  (Additive: ABI 1600.) */
+int nfisam_sample_propose(const float* Xt, const double* Gx, float* Yt, int x_rows, int n, const double* h, const uint8_t* wrap,
+                          uint64_t seed, uint32_t t, nfisam_stream_t stream);
+size_t nfisam_sample_accept_scratch_count(int x_rows, int n);           /* 0 for arguments the entry refuses */
+int nfisam_sample_accept(float* Xt, const float* Yt, double* Gx, const double* Gy, double* lp_x, const double* lp_y, int x_rows,
+                         int n, const double* h, const uint8_t* wrap, uint64_t seed, uint32_t t, double* log_alpha,
+                         uint8_t* accepted, double* scratch, nfisam_stream_t stream);
+
 /* ---- sample summaries: means, resultant lengths, covariances and quantiles of many column blocks (sample_summary.hip) -------
  * The reference summarises a draw on the host: `sample_mean` (src/utils/Statistics.py:151-171: np.mean, and scipy's
  * circmean(high = pi, low = -pi) for headings) and, built on it, `rmse` (:142-148), `geodesic_distance` (:179-191) and

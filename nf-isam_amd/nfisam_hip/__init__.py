@@ -35,6 +35,7 @@ EXPORTS = [
     "nfisam_factor_graph_hvp", "nfisam_factor_graph_hvp_scratch_count",
     "nfisam_sample_ksd", "nfisam_sample_ksd_scratch_count",
     "nfisam_sample_svgd", "nfisam_sample_svgd_scratch_count", "nfisam_sample_step",
+    "nfisam_sample_propose", "nfisam_sample_accept", "nfisam_sample_accept_scratch_count",
 ]
 
 
@@ -124,6 +125,7 @@ def lib():
         _lib.nfisam_factor_graph_hvp_scratch_count.restype = C.c_size_t
         _lib.nfisam_sample_ksd_scratch_count.restype = C.c_size_t
         _lib.nfisam_sample_svgd_scratch_count.restype = C.c_size_t
+        _lib.nfisam_sample_accept_scratch_count.restype = C.c_size_t
         for name in EXPORTS:
             getattr(_lib, name)   # raises AttributeError if the ABI is incomplete
     return _lib
@@ -1395,6 +1397,128 @@ def sample_step_t(Xt, cols, Phi, hist, eps, wrap=None, alpha=0.9, fudge=1e-6, fi
         _check(lib().nfisam_sample_step(_ptr(Xt), x_rows, n, _ptr(t["cols"]), ne, _ptr(t["wrap"]), _ptr(Phi), _ptr(hist),
                                         _ptr(t["eps"]), C.c_double(float(alpha)), C.c_double(float(fudge)), C.c_int(int(bool(first))),
                                         _stream()), "nfisam_sample_step")
+
+
+# ---- Metropolis-corrected moves: the Langevin / random-walk proposal and the accept step (nfisam_sample_propose / _accept) -----
+MCMC_SLAB = 32                                                        # rows per slab of the accept step's row sum (sample_mcmc.hip)
+MCMC_MAX_N, MCMC_MAX_ROWS = 65535 * 64, 65535 * MCMC_SLAB
+
+
+def check_mcmc_args(x_rows: int, n: int, h, wrap=None, seed=0, t=0) -> None:
+    """ValueError for what nfisam_sample_propose / nfisam_sample_accept refuse (no rows, no chains, more than 65535 * 64 chains or
+    65535 * 32 rows) and for what they do not read on the host: `h` must hold one finite step length >= 0 per row (a device tensor's
+    length alone is checked: checking its values would read it back), `wrap` one flag per row; `seed` an integer in [0, 2^64), `t`
+    one in [0, 2^32): the words of the generator's key and counter."""
+    if not (1 <= int(x_rows) <= MCMC_MAX_ROWS and 1 <= int(n) <= MCMC_MAX_N):
+        raise ValueError("1..%d rows and 1..%d chains are supported, got %d and %d" % (MCMC_MAX_ROWS, MCMC_MAX_N, x_rows, n))
+    if h is None:
+        raise ValueError("h must have one value per row (%d)" % x_rows)
+    for name, a in (("h", h), ("wrap", wrap)):
+        if a is not None and (tuple(a.shape) if torch.is_tensor(a) else np.shape(a)) != (int(x_rows),):
+            raise ValueError("%s must have one %s per row (%d)" % (name, "flag" if name == "wrap" else "value", x_rows))
+    if not (torch.is_tensor(h) and h.is_cuda):
+        hv = np.asarray(h, dtype=np.float64)
+        if not np.all(np.isfinite(hv) & (hv >= 0)):
+            raise ValueError("h must be finite and >= 0 (0 freezes a row)")
+    for name, v, top in (("seed", seed, 1 << 64), ("t", t, 1 << 32)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < top:
+            raise ValueError("%s must be an integer in [0, 2^%d), got %r" % (name, 64 if name == "seed" else 32, v))
+
+
+def mcmc_tables(device, h, wrap=None) -> dict:
+    """The per-row arrays of `sample_propose_t` / `sample_accept_t` on `device`, one upload, to reuse over the steps of a chain:
+    {"h": float64 [x_rows], "wrap": uint8 [x_rows] or None}."""
+    return _upload_named(device, h=_entry_f64(h), wrap=_flags(wrap))
+
+
+def _mcmc_front(Xt, mats, h, wrap, seed, t, checked, tables):
+    """What the two bindings share: the points, every other matrix of `mats` ({name: (tensor or None, dtype)}) of their shape on
+    their device, the argument checks -> (x_rows, n)."""
+    x_rows, n = _column_major_front("Xt", Xt)
+    for name, (M, dtype) in mats.items():
+        if M is None:
+            continue
+        if dtype == torch.float32:
+            _column_major_front(name, M)
+            if M.device != Xt.device:
+                raise ValueError("Xt and %s must be on the same device" % name)
+        else:
+            _score_front(name, M, Xt)
+        if tuple(M.shape) != (x_rows, n):
+            raise ValueError("%s must have the shape of the points: %s, got %s" % (name, (x_rows, n), tuple(M.shape)))
+    if not checked:
+        check_mcmc_args(x_rows, n, tables["h"] if tables is not None else h, tables["wrap"] if tables is not None else wrap,
+                        seed, t)
+    return x_rows, n
+
+
+def sample_propose_t(Xt, Gx, h, wrap=None, seed=0, t=0, Yt=None, checked=False, tables=None):
+    """The Metropolis proposal of the n chains in the COLUMN-major device matrix Xt [x_rows, n] (contiguous float32)
+    (nfisam_sample_propose, on the current stream): y = x + (h_r^2 / 2) g + h_r z in float64 with Gx [x_rows, n] (float64, as
+    `factor_graph_score_t` returns it; None: the random walk y = x + h_r z), h [x_rows] the step length of a row in its own
+    unit (0: the row is copied bit for bit), wrap [x_rows] marks angles (brought into [-pi, pi)).  z are the normals of the
+    generator contract: Philox4x32-10 keyed by `seed`, counter (chain, row >> 2, `t`, 0) -- the same for a chain at any n.
+    `Yt`: the matrix to write (default: a new one); `tables`: the result of `mcmc_tables` to reuse.  Xt is not written.
+    -> Yt [x_rows, n] float32."""
+    x_rows, n = _mcmc_front(Xt, {"Gx": (Gx, torch.float64), "Yt": (Yt, torch.float32)}, h, wrap, seed, t, checked, tables)
+    device = Xt.device
+    with torch.cuda.device(device):
+        tb = tables if tables is not None else mcmc_tables(device, h, wrap)
+        if Yt is None:
+            Yt = torch.empty_like(Xt)
+        _check(lib().nfisam_sample_propose(_ptr(Xt), _ptr(Gx), _ptr(Yt), x_rows, n, _ptr(tb["h"]), _ptr(tb["wrap"]),
+                                           C.c_uint64(int(seed)), C.c_uint32(int(t)), _stream()), "nfisam_sample_propose")
+    return Yt
+
+
+def sample_accept_scratch(x_rows: int, n: int, device):
+    """The scratch of `sample_accept_t` for this shape (nfisam_sample_accept_scratch_count doubles), to reuse over the steps."""
+    count = int(lib().nfisam_sample_accept_scratch_count(int(x_rows), int(n)))
+    if count < 1:
+        raise ValueError("sample_accept: %d rows and %d chains exceed the grid" % (x_rows, n))
+    return torch.empty(count, dtype=torch.float64, device=device)
+
+
+def sample_accept_t(Xt, Yt, Gx, Gy, lp_x, lp_y, h, wrap=None, seed=0, t=0, checked=False, tables=None, scratch=None):
+    """The accept / reject step of the n chains Xt [x_rows, n] against their proposals Yt (nfisam_sample_accept, on the current
+    stream), IN PLACE: log alpha = (lp_y - lp_x) + the log ratio of the Langevin proposal densities there and back, from the
+    float32 values stored in Xt and Yt and the scores Gx, Gy [x_rows, n] float64 at them (both None: a symmetric proposal, no
+    ratio -- the random walk, or an independence step with lp = log p - log q); lp_x, lp_y [n] float64.  A chain accepts iff
+    log(u) < log alpha, u the uniform of counter (chain, 0, `t`, 1) under `seed`; then its column of Yt, Gy and its lp_y replace
+    those of Xt, Gx and lp_x.  A rejected chain keeps every bit; a NaN log alpha or lp_y = -inf rejects.
+    -> (log_alpha [n] float64, accepted [n] uint8) on the device."""
+    x_rows, n = _mcmc_front(Xt, {"Yt": (Yt, torch.float32), "Gx": (Gx, torch.float64), "Gy": (Gy, torch.float64)}, h, wrap, seed,
+                            t, checked, tables)
+    if (Gx is None) != (Gy is None):
+        raise ValueError("Gx and Gy go together: both scores, or neither (a symmetric proposal)")
+    for name, v in (("lp_x", lp_x), ("lp_y", lp_y)):
+        if not torch.is_tensor(v) or not v.is_cuda:
+            raise RuntimeError("%s must be a tensor on a ROCm device (no CPU path exists)" % name)
+        if v.dtype != torch.float64 or tuple(v.shape) != (n,) or not v.is_contiguous() or v.device != Xt.device:
+            raise ValueError("%s must be a contiguous float64 [n] = (%d,) tensor on Xt's device" % (name, n))
+    device = Xt.device
+    with torch.cuda.device(device):
+        tb = tables if tables is not None else mcmc_tables(device, h, wrap)
+        if scratch is None:
+            scratch = sample_accept_scratch(x_rows, n, device)
+        log_alpha = torch.empty(n, dtype=torch.float64, device=device)
+        accepted = torch.empty(n, dtype=torch.uint8, device=device)
+        _check(lib().nfisam_sample_accept(_ptr(Xt), _ptr(Yt), _ptr(Gx), _ptr(Gy), _ptr(lp_x), _ptr(lp_y), x_rows, n, _ptr(tb["h"]),
+                                          _ptr(tb["wrap"]), C.c_uint64(int(seed)), C.c_uint32(int(t)), _ptr(log_alpha),
+                                          _ptr(accepted), _ptr(scratch), _stream()), "nfisam_sample_accept")
+    return log_alpha, accepted
+
+
+def sample_propose(X, G, h, wrap=None, seed=0, t=0, device=None):
+    """`sample_propose_t` for row-major points X [n, x_cols] (tensor or numpy) and scores G [n, x_cols] (or None)
+    -> Y [n, x_cols] float32 device tensor."""
+    mats = dict(X=X) if G is None else dict(X=X, G=G)
+    device = _row_major_front("sample_propose", device, **mats)
+    if G is not None and tuple(G.shape) != tuple(X.shape):
+        raise ValueError("the score matrix must have the shape of the points: %s, got %s" % (tuple(X.shape), tuple(G.shape)))
+    check_mcmc_args(int(X.shape[1]), int(X.shape[0]), h, wrap, seed, t)
+    Gt = None if G is None else _f64(G, device).t().contiguous()
+    return sample_propose_t(_columns(X, device), Gt, h, wrap, seed, t, checked=True).t().contiguous()
 
 
 # ---- sample summaries: means, resultant lengths, covariances, quantiles (nfisam_sample_moments, nfisam_sample_quantiles) --------

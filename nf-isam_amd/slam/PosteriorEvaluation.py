@@ -1,8 +1,8 @@
 """slam.PosteriorEvaluation -- what a trained NFiSAM solver says about its posterior, not in the reference: densities
 (`posterior_log_pdf`, `joint_log_pdf`, `joint_score`), the solver grading itself (`posterior_diagnostics`, `map_estimate`,
 `posterior_ksd`, `posterior_mmd`), what the posterior holds (`posterior_summary`, `posterior_modes`), its samples moved
-along the joint score (`posterior_refine`, `map_refine`) and the joint density's curvature (`joint_hessian_product`,
-`map_newton`, `laplace_approximation`).
+along the joint score (`posterior_refine`, `map_refine`), the joint density's curvature (`joint_hessian_product`,
+`map_newton`, `laplace_approximation`) and Metropolis chains that make the samples asymptotically exact (`posterior_mcmc`).
 
 A mixin of `slam.NFiSAM.NFiSAM`: the walk (`posterior_launch`, `_post_columns`, `_posterior_table`) and the solver's state
 are reached through `self`.  Every public method goes through ONE front, `_eval_points`, which makes the checks that need no
@@ -460,6 +460,85 @@ class PosteriorEvaluation:
         return dict(map_sample={v: row[pcol[v]:pcol[v] + v.dim].copy() for v in self._elimination_ordering}, log_p=out_lp,
                     start_log_p=start_log_p, improved=bool(out_lp > start_log_p), climbers=best_lp.cpu().numpy(),
                     steps=res["steps"], top=top, n=pts.rows)
+
+    # ---- the samples made exact: Metropolis-adjusted Langevin chains started at the flow's draws, with flow jumps -----------------
+    def posterior_mcmc(self, samples=None, n: int = None, steps: int = 200, warmup: int = 100, step_size: float = 0.5,
+                       kernel: str = "mala", independence_every: int = 0, frozen=None, standardise: bool = True,
+                       seed=None) -> dict:
+        """Posterior samples whose stationary distribution is the factor graph's own posterior p(X | Z): n parallel
+        Metropolis chains, one per sample, on the device where the sample matrix lies (nfisam_sample_propose,
+        nfisam_sample_accept between nfisam_factor_graph_log_density and nfisam_factor_graph_score: float32 points, float64
+        arithmetic).  Not in the reference.  The chains start at the flow's draws, so every mode the flow found is populated.
+
+        samples=None draws `n` (default posterior_sample_num) points through the tree walk; otherwise the chains start at
+        `samples` (as `joint_log_pdf` accepts it) and nothing is drawn.  kernel: "mala" (Langevin proposals along the joint
+        score) or "rw" (a random walk: no score launch).  `steps` steps in all, of which the first `warmup` scale one multiplier
+        on the step lengths towards the optimal acceptance rate (0.574 / 0.234); after them the step lengths are fixed.
+        standardise: a column's step is `step_size` times its spread over the STARTING points (the circular spread for a
+        heading; `step_size` itself for a column without spread), else `step_size` in every column's own unit; a heading's step
+        is at most Statistics.WRAP_STEP_MAX.  independence_every = k > 0: every k-th step proposes fresh draws of the flow
+        (the tree walk, from a generator of its own seeded by `seed` and the step) and accepts them with the weights p / q --
+        global jumps between modes; 1 makes every step a jump.  frozen: variables held at their given values (their step is 0):
+        the chains then sample p(rest | frozen, Z); not together with jumps, which propose every variable.
+        seed: the key of the chains' generator (None: one below 2^62 from numpy's global RNG).
+        -> dict: samples (variable -> [n, dim] float32: valid input to every other evaluation), log_p ([n] float64:
+        `joint_log_pdf` of them), accept_rate (accepted local proposals / proposed, over chains and steps; None without local
+        steps), jump_accept_rate (None without jumps), step_size (variable -> [dim]: the final step lengths), steps, warmup,
+        kernel, n, seed.
+        A copy of the sample matrix is moved: no solver state changes and the result is not fed back.  With `samples` and `seed`
+        given no random stream is touched.  Raises RuntimeError when there is no graph / tree yet, NotImplementedError naming a
+        factor class without a device code, ValueError for bad points or options -- before anything is launched."""
+        from utils import Statistics as ST
+        what, every = "posterior_mcmc", independence_every
+        count = not isinstance(every, bool) and isinstance(every, (int, np.integer)) and every >= 0
+        pts = self._eval_points(what, samples, n, factors=True, log_q=bool(count and every > 0), nonempty=True)
+        flags, cols = self._column_flags(pts)
+        order, pcol = list(self._elimination_ordering), pts.pcol
+        try:
+            if not count:
+                raise ValueError("independence_every must be an integer >= 0, got %r" % (every,))
+            if np.ndim(step_size) != 0 or not (np.isfinite(step_size) and step_size > 0):
+                raise ValueError("step_size is one positive finite step")
+            held = list(frozen) if frozen is not None else []
+            if any(v not in pcol or v not in order for v in held):
+                raise ValueError("frozen names a variable that is not in the graph")
+            if held and every:
+                raise ValueError("independence steps propose every variable: not together with frozen variables")
+            opt = ST.check_metropolis_options(pts.total_dim, steps, float(step_size), None, kernel, warmup, None, seed)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (what, e)) from None
+        scale = self._column_scale(pts, flags, cols, bool(standardise))
+        h = np.zeros(pts.total_dim)
+        h[cols] = float(step_size)
+        if standardise:
+            h[scale > 0] = float(step_size) / scale[scale > 0]
+        h[flags] = np.minimum(h[flags], ST.WRAP_STEP_MAX)
+        for v in held:
+            h[pcol[v]:pcol[v] + v.dim] = 0.0
+        seed = int(np.random.randint(0, 2 ** 62)) if opt["seed"] is None else opt["seed"]
+        work = pts.over(pts.St.clone())                                # never the walk's own tensor
+
+        def draw_t(rows, t):
+            tb = pts.table
+            K, H, B, L = tb["cfg"]
+            gen = torch.Generator(device=pts.device)
+            gen.manual_seed((seed ^ (0x9E3779B97F4A7C15 * (t + 1))) & (2 ** 63 - 1))
+            Zt = torch.randn(tb["total_dim"], rows, dtype=torch.float32, device=pts.device, generator=gen)
+            Y = _nh.posterior_walk_raw(tb["table"], tb["cols"], tb["obs"], tb["total_dim"], rows, tb["max_D"], K, H, B, L,
+                                       tb["device"], Zt=Zt).t().contiguous()
+            return Y, self._log_q_launch(pts.over(Y))
+
+        res = ST.metropolis_refine_t(work.St, lambda Xt: self._joint_launch(pts.over(Xt)),
+                                     lambda Xt: self._score_launch(pts.over(Xt)), opt["steps"], h, circular=flags, kernel=kernel,
+                                     warmup=opt["warmup"], seed=seed, independence=(int(every), draw_t) if every else None,
+                                     log_q_t=(lambda Xt: self._log_q_launch(pts.over(Xt))) if every else None)
+        h_end = res["h"].cpu().numpy()
+        local, jump = res["local_steps"], res["jump_steps"]
+        return dict(samples=self._samples_of(work.St, pcol), log_p=res["log_p"].cpu().numpy(),
+                    accept_rate=float(res["accepts"].sum().item()) / (local * pts.rows) if local else None,
+                    jump_accept_rate=float(res["jump_accepts"].sum().item()) / (jump * pts.rows) if jump else None,
+                    step_size={v: h_end[pcol[v]:pcol[v] + v.dim].copy() for v in order}, steps=res["steps"],
+                    warmup=res["warmup"], kernel=kernel, n=pts.rows, seed=seed)
 
     # ---- curvature: Hessian-vector products, truncated-Newton MAP ascent, the Laplace approximation at a mode ---------------------
     def _hvp_launch(self, pts: EvalPoints, Vt, score: bool = False):

@@ -702,6 +702,191 @@ def stein_variational_refine(x, score, blocks, steps, step_size, sigma=None, sca
     return dict(x=Xt.t().cpu().numpy().copy(), hist=hist, steps=res["steps"])
 
 
+# ---- Metropolis-corrected chains: MALA / random walk with independence jumps (nfisam_sample_propose / nfisam_sample_accept) ----
+METROPOLIS_TARGET = {"mala": 0.574, "rw": 0.234}                      # the optimal-scaling acceptance rates (Roberts & Rosenthal 2001)
+# The accept step keeps the nearest image of the wrapped normal.  At a residual rho the next image weighs
+# exp(-2 pi (pi - |rho|) / h^2) of it: below 2^-53 while |rho| <= pi - 5.85 h^2, which for h <= 0.3 rad is 2.61 rad >= 8.7 h --
+# a normal draw beyond 8.7 sigma has probability 3e-18.  
+WRAP_STEP_MAX = 0.3
+
+
+def check_metropolis_options(width, steps=0, step_size=1.0, circular=None, kernel="mala", warmup=0, target_accept=None, seed=None,
+                             independence=None):
+    """Every option of the Metropolis functions, checked with no device: kernel "mala" or "rw"; steps an integer >= 0, warmup an
+    integer in [0, steps]; step_size one finite step >= 0 or one per column, in the column's own unit (0 freezes a column), at
+    most WRAP_STEP_MAX = 0.3 rad on a circular column (the nearest-image bound); circular one flag per column; target_accept in
+    (0, 1) (None: 0.574 for MALA, 0.234 for the random walk); seed None or an integer in [0, 2^64); independence None or
+    (every >= 1, draw_t callable), which needs every column free (no step of 0).
+    -> dict(h [width], flags [width] bool, steps, warmup, kernel, target, seed, every, draw_t)."""
+    if kernel not in ("mala", "rw"):
+        raise ValueError("kernel must be 'mala' or 'rw', got %r" % (kernel,))
+    for name, v in (("steps", steps), ("warmup", warmup)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 0:
+            raise ValueError("%s must be an integer >= 0, got %r" % (name, v))
+    if int(warmup) > int(steps):
+        raise ValueError("warmup (%d) counts among the steps (%d): it cannot exceed them" % (warmup, steps))
+    width = int(width)
+    if width < 1:
+        raise ValueError("at least one column is needed")
+    try:
+        h = np.asarray(step_size, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError("step_size is one finite step >= 0, or one per column (%d)" % width) from None
+    h = np.broadcast_to(h, (width,)).copy() if h.size == 1 else h
+    if h.size != width or not np.all(np.isfinite(h) & (h >= 0)):
+        raise ValueError("step_size is one finite step >= 0, or one per column (%d)" % width)
+    flags = _column_flags(circular, width)
+    if np.any(h[flags] > WRAP_STEP_MAX):
+        raise ValueError("step_size: a circular column's step is at most %g rad (the nearest-image bound), got %g"
+                         % (WRAP_STEP_MAX, float(h[flags].max())))
+    target = METROPOLIS_TARGET[kernel] if target_accept is None else target_accept
+    if np.ndim(target) != 0 or not (np.isfinite(target) and 0.0 < target < 1.0):
+        raise ValueError("target_accept must lie in (0, 1), got %r" % (target_accept,))
+    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64):
+        raise ValueError("seed must be None or an integer in [0, 2^64), got %r" % (seed,))
+    every, draw_t = 0, None
+    if independence is not None:
+        try:
+            every, draw_t = independence
+        except (TypeError, ValueError):
+            raise ValueError("independence is None or (every, draw_t)") from None
+        if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or int(every) < 1 or not callable(draw_t):
+            raise ValueError("independence is None or (every >= 1, a callable (n, t) -> (Yt, log_q_y))")
+        if np.any(h == 0):
+            raise ValueError("independence steps propose every column: no column may be frozen (step 0)")
+    return dict(h=h, flags=flags, steps=int(steps), warmup=int(warmup), kernel=kernel, target=float(target),
+                seed=None if seed is None else int(seed), every=int(every), draw_t=draw_t)
+
+
+def _lp64(v, n, what):
+    import torch
+    if not torch.is_tensor(v) or tuple(v.shape) != (n,):
+        raise ValueError("%s must return a [n] = (%d,) device tensor" % (what, n))
+    return v.to(torch.float64).contiguous()
+
+
+def metropolis_refine_t(Xt, log_p_t, score_t, steps, step_size, circular=None, kernel="mala", warmup=0, target_accept=None,
+                        seed=None, independence=None, after_step=None, log_q_t=None) -> dict:
+    """n parallel Metropolis chains, one per column of the COLUMN-major device matrix Xt [D, n] (contiguous float32), IN PLACE
+    and entirely on the device; their stationary distribution is exp(log p) itself.  log_p_t: a callable Xt -> log p [n]
+    (float64 device tensor, e.g. around `nfisam_hip.factor_graph_log_density_t`); score_t: a callable Xt -> grad log p [D, n]
+    (float64 column-major, e.g. around `nfisam_hip.factor_graph_score_t`; not called for kernel="rw").  A step proposes
+    y = x + (h^2 / 2) grad log p + h z (kernel="mala") or y = x + h z ("rw") with `nfisam_hip.sample_propose_t`, evaluates
+    log p (and the score) at y, and accepts or rejects every chain with `nfisam_hip.sample_accept_t`.  step_size: one step
+    length or one per column, in the column's own unit (0 freezes the column: the chains sample the rest given it); circular
+    [D]: columns that are angles.
+    The first `warmup` steps scale ONE multiplier on h towards the acceptance rate `target_accept` (default 0.574 / 0.234):
+    Robbins-Monro on log h, log m += (k + 1)^-0.6 (rate_k - target) with rate_k the fraction of chains that accepted step k,
+    in torch ops on the device array -- no step waits for the host; a circular column's step stays at most WRAP_STEP_MAX.  After
+    the warm-up h is fixed, which makes what follows a valid Markov chain.
+    independence=(every, draw_t): every `every`-th step proposes Yt, log_q_y = draw_t(n, t) ([D, n] float32, [n]) -- fresh draws
+    of a density q, e.g. the flow -- and accepts through the same entry with lp = log p - log q: a global jump between modes.
+    It needs `log_q_t`, a callable Xt -> log q [n] for the current state.  after_step: a callable (Xt, step index).
+    seed: the generator's key (None: one below 2^62 from numpy's global RNG, `DeviceSimulation`'s rule); step t uses counter
+    word t, so two runs with one seed give the same bits.
+    -> dict(accepts [n] int64: accepted local steps per chain; jump_accepts [n] int64; h [D] float64: the final step lengths;
+    log_p [n] float64 (device tensors); steps, local_steps, jump_steps, warmup, seed).  steps = 0 leaves every bit alone.  Every
+    option is checked before anything is launched."""
+    import nfisam_hip as _nh
+    import torch
+    if not callable(log_p_t) or (kernel == "mala" and not callable(score_t)):
+        raise ValueError("log_p_t (and, for kernel='mala', score_t) must be callables on Xt")
+    if np.ndim(Xt) != 2:
+        raise ValueError("Xt must be [columns, points]")
+    opt = check_metropolis_options(int(Xt.shape[0]), steps, step_size, circular, kernel, warmup, target_accept, seed, independence)
+    if opt["every"] and not callable(log_q_t):
+        raise ValueError("independence steps need log_q_t, a callable Xt -> log q at the current state")
+    if after_step is not None and not callable(after_step):
+        raise ValueError("after_step must be a callable (Xt, step index)")
+    D, n = _nh._column_major_front("Xt", Xt)
+    flags = opt["flags"]
+    _nh.check_mcmc_args(D, n, opt["h"], flags.astype(np.uint8) if flags.any() else None)
+    seed = int(np.random.randint(0, 2 ** 62)) if opt["seed"] is None else opt["seed"]
+    device, mala = Xt.device, kernel == "mala"
+    zeros = torch.zeros(n, dtype=torch.int64, device=device)
+    out = dict(accepts=zeros, jump_accepts=zeros.clone(), steps=opt["steps"], local_steps=0, jump_steps=0, warmup=opt["warmup"],
+               seed=seed)
+    with torch.cuda.device(device):
+        tables = _nh.mcmc_tables(device, opt["h"], flags.astype(np.uint8) if flags.any() else None)
+        h = tables["h"] = tables["h"].clone()                          # the loop's own array: the warm-up scales it in place
+        lp = _lp64(log_p_t(Xt), n, "log_p_t").clone()
+        if opt["steps"] == 0:
+            return dict(out, h=h, log_p=lp)
+        h0, log_m = h.clone(), torch.zeros((), dtype=torch.float64, device=device)
+        cap = None if tables["wrap"] is None else \
+            torch.full_like(h, float("inf")).masked_fill_(tables["wrap"] != 0, WRAP_STEP_MAX)
+        Gx = score_t(Xt) if mala else None
+        Yt = torch.empty_like(Xt)
+        scratch = _nh.sample_accept_scratch(D, n, device)
+        for t in range(opt["steps"]):
+            if opt["every"] and (t + 1) % opt["every"] == 0:           # a global jump: an independence proposal from q
+                Y, lq_y = opt["draw_t"](n, t)
+                wx = lp - _lp64(log_q_t(Xt), n, "log_q_t")
+                lp_y = _lp64(log_p_t(Y), n, "log_p_t")
+                wy = lp_y - _lp64(lq_y, n, "draw_t's log q")
+                _, acc = _nh.sample_accept_t(Xt, Y, None, None, wx, wy, None, seed=seed, t=t, checked=True, tables=tables,
+                                             scratch=scratch)
+                lp = torch.where(acc != 0, lp_y, lp)
+                if mala:
+                    Gx = score_t(Xt)
+                out["jump_accepts"] += acc
+                out["jump_steps"] += 1
+            else:
+                _nh.sample_propose_t(Xt, Gx, None, seed=seed, t=t, Yt=Yt, checked=True, tables=tables)
+                lp_y = _lp64(log_p_t(Yt), n, "log_p_t")
+                Gy = score_t(Yt) if mala else None
+                _, acc = _nh.sample_accept_t(Xt, Yt, Gx, Gy, lp, lp_y, None, seed=seed, t=t, checked=True, tables=tables,
+                                             scratch=scratch)
+                out["accepts"] += acc
+                out["local_steps"] += 1
+                if t < opt["warmup"]:
+                    log_m += (out["local_steps"] ** -0.6) * (acc.to(torch.float64).mean() - opt["target"])
+                    scaled = h0 * torch.exp(log_m)
+                    h.copy_(scaled if cap is None else torch.minimum(scaled, cap))
+            if after_step is not None:
+                after_step(Xt, t)
+    return dict(out, h=h, log_p=lp)
+
+
+def metropolis_refine(x, log_p, score, steps, step_size, circular=None, kernel="mala", warmup=0, target_accept=None, seed=None,
+                      device=None) -> dict:
+    """`metropolis_refine_t` for row-major points x [n, D] (numpy or torch) and a target given as callables on numpy:
+    log_p(points [n, D] float64) -> [n], score(points) -> [n, D] (unused for kernel="rw").  The proposal and the accept step run
+    on the device; the callables are called on the host once per step -- the convenience form.
+    -> dict(x [n, D] float32 numpy: the chains' final states, log_p [n], accepts [n], h [D], steps, warmup, seed)."""
+    import nfisam_hip as _nh
+    import torch
+    if not callable(log_p) or (kernel == "mala" and not callable(score)):
+        raise ValueError("log_p (and, for kernel='mala', score) must be callables points -> values")
+    if np.ndim(x) != 2:
+        raise ValueError("x must be [points, columns]")
+    n, D = int(x.shape[0]), int(x.shape[1])
+    if n < 1 or D < 1:
+        raise ValueError("at least one point and one column are needed")
+    check_metropolis_options(D, steps, step_size, circular, kernel, warmup, target_accept, seed)
+    device = _nh._row_major_front("metropolis_refine", device, x=x)
+    Xt = _nh._columns(x, device)
+
+    def host(Xt):
+        return Xt.t().cpu().numpy().astype(np.float64)
+
+    def log_p_t(Xt):
+        v = np.asarray(log_p(host(Xt)), dtype=np.float64)
+        if v.shape != (n,):
+            raise ValueError("log_p must return [n] = (%d,), got %s" % (n, v.shape))
+        return torch.from_numpy(v).to(Xt.device)
+
+    def score_t(Xt):
+        g = np.asarray(score(host(Xt)), dtype=np.float64)
+        if g.shape != (n, D):
+            raise ValueError("score must return the shape of x, %s, got %s" % ((n, D), g.shape))
+        return torch.from_numpy(np.ascontiguousarray(g.T)).to(Xt.device)
+
+    res = metropolis_refine_t(Xt, log_p_t, score_t, steps, step_size, circular, kernel, warmup, target_accept, seed)
+    return dict(x=Xt.t().cpu().numpy().copy(), log_p=res["log_p"].cpu().numpy(), accepts=res["accepts"].cpu().numpy(),
+                h=res["h"].cpu().numpy(), steps=res["steps"], warmup=res["warmup"], seed=res["seed"])
+
+
 # ---- curvature: matrix-free conjugate gradients on Hessian-vector products, truncated Newton ascent (nfisam_factor_graph_hvp) ----
 NEWTON_GTOL, NEWTON_BACKTRACKS = 1e-3, 10
 
