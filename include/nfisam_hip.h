@@ -433,6 +433,47 @@ int nfisam_sample_accept(float* Xt, const float* Yt, double* Gx, const double* G
                          int n, const double* h, const uint8_t* wrap, uint64_t seed, uint32_t t, double* log_alpha,
                          uint8_t* accepted, double* scratch, nfisam_stream_t stream);
 
+/* ---- chain diagnostics: split-R-hat, the blocking autocorrelation time and the within-chain variance per row (sample_chains.hip)
+ * Not in the reference.  The n chains are the columns of Xt[x_rows][n] (COLUMN-major float32, device); their history is never
+ * kept: one nfisam_chain_record per recorded state t = 0 ... T - 1, ASCENDING, folds it into `state`, and nfisam_chain_finish
+ * turns the state into per-row statistics.  T is even and >= 2; levels (the blocking levels, level 0 included) lies in
+ * [1, min(NFISAM_CHAIN_MAX_LEVELS, floor(log2 T))], so every level has at least two blocks.  center[x_rows] double (NULL: 0) and
+ * wrap[x_rows] uint8 (NULL: no angles) are DEVICE arrays, the same in every call of a run.  All arithmetic float64.
+ *
+ * The recorded value of row r, chain i:  v = (double)Xt[r][i] - center[r], wrapped into [-pi, pi) where wrap[r] is set.
+ * state: nfisam_chain_state_count(x_rows, n, levels) = (4 + 3 (levels - 1)) x_rows n doubles, slot-major [slot][row][chain], ZEROS
+ * before t = 0:  slots 0, 1: A1[w] = sum v;  slots 2, 3: A2[w] = sum v^2, w = 0 for t < T / 2 and 1 for t >= T / 2;  slots
+ * 4 + 3 (l - 1) + {0, 1, 2}: P_l, R_l, Q_l of level l = 1 ... levels - 1 (Flyvbjerg & Petersen 1989): the pending value, and the sums
+ * R_l = sum_j b_lj, Q_l = sum_j b_lj^2 over the means b_lj of the complete blocks of 2^l consecutive values.  Level 0 is the
+ * halves added up.
+ *
+ * nfisam_chain_record, the fold at index t:  A1[w] += v, A2[w] += v^2; carry = v; for l = 1 ... levels - 1: bit l - 1 of t clear
+ * -> P_l = carry, stop; set -> carry = (P_l + carry) / 2, R_l += carry, Q_l += carry^2, go on.  Xt is not written.  One launch,
+ * elementwise: the same bits on every call, at any n, for a row alone or inside a taller matrix.
+ * NFISAM_ERR_ARG before any launch: Xt or state NULL, x_rows or n < 1, n > 65535 * 64, T odd or < 2, t >= T, levels out of range.
+ *
+ * nfisam_chain_finish, per row over its n chains, with m_l = T >> l and s2_li = (Q_l - R_l^2 / m_l) / (m_l - 1):
+ *     mean[r]   = center[r] + sum_i (A1[0] + A1[1]) / (n T), wrapped where wrap[r] is set
+ *     within[r] = mean_i s2_0i                               the pooled within-chain variance of whole chains
+ *     tau[l][r] = 2^l mean_i s2_li / mean_i s2_0i            the blocking estimate of the integrated autocorrelation time at
+ *                                                            block length 2^l; tau[0] = 1 by construction
+ *     rhat[r]   = sqrt(((L - 1) / L W + B / L) / W)          split-R-hat (BDA3 11.4) over the 2 n half-chains of length L = T / 2:
+ *                 mu_k = A1 / L, s2_k = (A2 - A1^2 / L) / (L - 1), W = mean_k s2_k, B / L = sum_k (mu_k - mu_bar)^2 / (2 n - 1) with
+ *                 mu_bar taken first (two passes).  NaN for T < 4, and NaN where W = 0 and B = 0 (a row without spread): 0 / 0, no
+ *                 special case.  (A row frozen at a different constant per chain has W = 0 only up to the rounding of its sums:
+ *                 the caller, who knows which rows are frozen, discards their rhat and tau.)
+ * mean, within, rhat [x_rows] and tau [levels][x_rows]: double, device.  One block per row, no float atomics: a thread adds its
+ * chains ascending, then the fixed wave tree, then the four waves in order -- the same bits on every call, for a row alone
+ * or inside a taller matrix.
+ * NFISAM_ERR_ARG before any launch: state or a result NULL, x_rows or n < 1, n > 65535 * 64, T odd or < 2, levels out of range.
+ * (Additive: ABI 1600.) */
+#define NFISAM_CHAIN_MAX_LEVELS 16
+size_t nfisam_chain_state_count(int x_rows, int n, int levels);         /* 0 for arguments the entries refuse */
+int nfisam_chain_record(const float* Xt, double* state, int x_rows, int n, int levels, const double* center, const uint8_t* wrap,
+                        uint32_t t, uint32_t T, nfisam_stream_t stream);
+int nfisam_chain_finish(const double* state, int x_rows, int n, int levels, uint32_t T, const double* center, const uint8_t* wrap,
+                        double* mean, double* within, double* rhat, double* tau /* [levels][x_rows] */, nfisam_stream_t stream);
+
 /* ---- sample summaries: means, resultant lengths, covariances and quantiles of many column blocks (sample_summary.hip) -------
  * The reference summarises a draw on the host: `sample_mean` (src/utils/Statistics.py:151-171: np.mean, and scipy's
  * circmean(high = pi, low = -pi) for headings) and, built on it, `rmse` (:142-148), `geodesic_distance` (:179-191) and

@@ -36,6 +36,7 @@ EXPORTS = [
     "nfisam_sample_ksd", "nfisam_sample_ksd_scratch_count",
     "nfisam_sample_svgd", "nfisam_sample_svgd_scratch_count", "nfisam_sample_step",
     "nfisam_sample_propose", "nfisam_sample_accept", "nfisam_sample_accept_scratch_count",
+    "nfisam_chain_record", "nfisam_chain_finish", "nfisam_chain_state_count",
 ]
 
 
@@ -126,6 +127,7 @@ def lib():
         _lib.nfisam_sample_ksd_scratch_count.restype = C.c_size_t
         _lib.nfisam_sample_svgd_scratch_count.restype = C.c_size_t
         _lib.nfisam_sample_accept_scratch_count.restype = C.c_size_t
+        _lib.nfisam_chain_state_count.restype = C.c_size_t
         for name in EXPORTS:
             getattr(_lib, name)   # raises AttributeError if the ABI is incomplete
     return _lib
@@ -1519,6 +1521,111 @@ def sample_propose(X, G, h, wrap=None, seed=0, t=0, device=None):
     check_mcmc_args(int(X.shape[1]), int(X.shape[0]), h, wrap, seed, t)
     Gt = None if G is None else _f64(G, device).t().contiguous()
     return sample_propose_t(_columns(X, device), Gt, h, wrap, seed, t, checked=True).t().contiguous()
+
+
+# ---- chain diagnostics: the streaming fold of the chains' states and the per-row finish (nfisam_chain_record / _finish) --------
+CHAIN_MAX_LEVELS = 16                                                 # NFISAM_CHAIN_MAX_LEVELS
+
+
+def chain_max_levels(T: int) -> int:
+    """The most blocking levels a run of T recorded states takes: min(16, floor(log2 T)), every level with at least two blocks."""
+    return min(CHAIN_MAX_LEVELS, int(T).bit_length() - 1)
+
+
+def check_chain_args(x_rows: int, n: int, levels, T, t=0, center=None, wrap=None) -> None:
+    """ValueError for what nfisam_chain_record / nfisam_chain_finish refuse (no rows, no chains, more than 65535 * 64 chains, an
+    odd T or one below 2, t outside [0, T), levels outside [1, min(16, floor(log2 T))]) and for what they do not read on the
+    host: `center` must hold one finite value per row (a device tensor's length alone is checked), `wrap` one flag per row."""
+    if not (int(x_rows) >= 1 and 1 <= int(n) <= MCMC_MAX_N):
+        raise ValueError("at least 1 row and 1..%d chains are supported, got %d and %d" % (MCMC_MAX_N, x_rows, n))
+    for name, v in (("T", T), ("t", t), ("levels", levels)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+    if not (2 <= int(T) < 1 << 32) or int(T) % 2:
+        raise ValueError("T, the number of recorded states, must be even and in [2, 2^32), got %d" % T)
+    if not 0 <= int(t) < int(T):
+        raise ValueError("t must lie in [0, T = %d), got %d" % (T, t))
+    if not 1 <= int(levels) <= chain_max_levels(T):
+        raise ValueError("levels must lie in [1, min(16, floor(log2 T)) = %d] for T = %d, got %d" % (chain_max_levels(T), T, levels))
+    for name, a in (("center", center), ("wrap", wrap)):
+        if a is not None and (tuple(a.shape) if torch.is_tensor(a) else np.shape(a)) != (int(x_rows),):
+            raise ValueError("%s must have one %s per row (%d)" % (name, "flag" if name == "wrap" else "value", x_rows))
+    if center is not None and not (torch.is_tensor(center) and center.is_cuda):
+        if not np.all(np.isfinite(np.asarray(center, dtype=np.float64))):
+            raise ValueError("center must be finite")
+
+
+def chain_tables(device, center=None, wrap=None) -> dict:
+    """The per-row arrays of `chain_record_t` / `chain_finish_t` on `device`, one upload, to reuse over the steps of a run:
+    {"center": float64 [x_rows] or None, "wrap": uint8 [x_rows] or None}."""
+    return _upload_named(device, center=_entry_f64(center), wrap=_flags(wrap))
+
+
+def chain_state(D: int, n: int, levels: int, device):
+    """The zeroed accumulators of `chain_record_t` for D rows, n chains and `levels` blocking levels: float64
+    [4 + 3 (levels - 1), D, n] on `device` (nfisam_chain_state_count doubles, slot-major)."""
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in (D, n, levels)):
+        raise ValueError("D, n and levels must be integers")
+    if not (int(D) >= 1 and 1 <= int(n) <= MCMC_MAX_N and 1 <= int(levels) <= CHAIN_MAX_LEVELS):
+        raise ValueError("chain_state: at least 1 row, 1..%d chains and 1..%d levels are supported, got %d, %d and %d"
+                         % (MCMC_MAX_N, CHAIN_MAX_LEVELS, D, n, levels))
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("chain_state needs a ROCm device (no CPU path exists)")
+    slots = 4 + 3 * (int(levels) - 1)
+    assert int(lib().nfisam_chain_state_count(int(D), int(n), int(levels))) == slots * int(D) * int(n)
+    return torch.zeros(slots, int(D), int(n), dtype=torch.float64, device=device)
+
+
+def _chain_state_front(state, x_rows, n, levels, device):
+    if not torch.is_tensor(state) or not state.is_cuda:
+        raise RuntimeError("state must be a tensor on a ROCm device (no CPU path exists)")
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)):
+        raise ValueError("levels must be an integer, got %r" % (levels,))
+    want = (4 + 3 * (int(levels) - 1), x_rows, n)
+    if state.dtype != torch.float64 or tuple(state.shape) != want or not state.is_contiguous() or state.device != device:
+        raise ValueError("state must be the contiguous float64 %s tensor of `chain_state` on the points' device" % (want,))
+
+
+def chain_record_t(state, Xt, t, T, levels, center=None, wrap=None, tables=None, checked=False):
+    """Fold the current state of the n chains in the COLUMN-major device matrix Xt [x_rows, n] (contiguous float32) into the
+    accumulators `state` of `chain_state` (nfisam_chain_record, on the current stream): recorded state number t of T, one call
+    per t = 0 ... T - 1, ascending.  The value recorded for row r is the float64 deviation x - center[r], wrapped into [-pi, pi)
+    where wrap[r] is set; center None: 0.  `tables`: the result of `chain_tables` to reuse.  Xt is not written.  -> state."""
+    x_rows, n = _column_major_front("Xt", Xt)
+    if not checked:
+        check_chain_args(x_rows, n, levels, T, t, tables["center"] if tables is not None else center,
+                         tables["wrap"] if tables is not None else wrap)
+    _chain_state_front(state, x_rows, n, levels, Xt.device)
+    device = Xt.device
+    with torch.cuda.device(device):
+        tb = tables if tables is not None else chain_tables(device, center, wrap)
+        _check(lib().nfisam_chain_record(_ptr(Xt), _ptr(state), x_rows, n, int(levels), _ptr(tb["center"]), _ptr(tb["wrap"]),
+                                         C.c_uint32(int(t)), C.c_uint32(int(T)), _stream()), "nfisam_chain_record")
+    return state
+
+
+def chain_finish_t(state, D, n, levels, T, center=None, wrap=None, tables=None):
+    """The per-row statistics of the T states recorded in `state` (nfisam_chain_finish, on the current stream), with the
+    `center` and `wrap` of the record calls (or their `tables`)
+    -> dict(mean [D], within [D], rhat [D], tau [levels, D]) of float64 device tensors: the mean over chains and states (the
+    centre added back, wrapped on a circular row), the pooled within-chain variance, split-R-hat over the 2 n half-chains
+    (NaN for T < 4 and on a row without spread) and the blocking estimates of the integrated autocorrelation time at block
+    lengths 1, 2, ..., 2^(levels - 1) (`Statistics.blocking_tau` picks the one to quote)."""
+    if not torch.is_tensor(state) or not state.is_cuda:
+        raise RuntimeError("state must be a tensor on a ROCm device (no CPU path exists)")
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in (D, n)):
+        raise ValueError("D and n must be integers")
+    device = state.device
+    _chain_state_front(state, int(D), int(n), levels, device)
+    check_chain_args(int(D), int(n), levels, T, 0, tables["center"] if tables is not None else center,
+                     tables["wrap"] if tables is not None else wrap)
+    with torch.cuda.device(device):
+        tb = tables if tables is not None else chain_tables(device, center, wrap)
+        out = torch.empty(3 + int(levels), int(D), dtype=torch.float64, device=device)
+        _check(lib().nfisam_chain_finish(_ptr(state), int(D), int(n), int(levels), C.c_uint32(int(T)), _ptr(tb["center"]),
+                                         _ptr(tb["wrap"]), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3:]), _stream()),
+               "nfisam_chain_finish")
+    return dict(mean=out[0], within=out[1], rhat=out[2], tau=out[3:])
 
 
 # ---- sample summaries: means, resultant lengths, covariances, quantiles (nfisam_sample_moments, nfisam_sample_quantiles) --------

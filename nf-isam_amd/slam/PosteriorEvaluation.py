@@ -464,7 +464,7 @@ class PosteriorEvaluation:
     # ---- the samples made exact: Metropolis-adjusted Langevin chains started at the flow's draws, with flow jumps -----------------
     def posterior_mcmc(self, samples=None, n: int = None, steps: int = 200, warmup: int = 100, step_size: float = 0.5,
                        kernel: str = "mala", independence_every: int = 0, frozen=None, standardise: bool = True,
-                       seed=None) -> dict:
+                       seed=None, diagnostics: bool = False) -> dict:
         """Posterior samples whose stationary distribution is the factor graph's own posterior p(X | Z): n parallel
         Metropolis chains, one per sample, on the device where the sample matrix lies (nfisam_sample_propose,
         nfisam_sample_accept between nfisam_factor_graph_log_density and nfisam_factor_graph_score: float32 points, float64
@@ -485,6 +485,14 @@ class PosteriorEvaluation:
         `joint_log_pdf` of them), accept_rate (accepted local proposals / proposed, over chains and steps; None without local
         steps), jump_accept_rate (None without jumps), step_size (variable -> [dim]: the final step lengths), steps, warmup,
         kernel, n, seed.
+        diagnostics=True: the state of every chain after every step t >= warmup is folded into streaming accumulators on the
+        device (nfisam_chain_record; the history itself is never kept), about the starting points' means, and the result gains
+        diagnostics (variable -> dict(mean, rhat, tau, ess, resolved), each [dim]: the mean over chains and recorded states,
+        split-R-hat over the 2 n half-chains, the blocking estimate of the integrated autocorrelation time in steps,
+        ess = n recorded / tau, and whether the blocking plateau was seen -- resolved False: tau is a LOWER bound and ess an upper
+        one, `Statistics.blocking_tau`), rhat_max and ess_min (over the columns that move; NaN if none does) and recorded (the
+        number of recorded states, even: of an odd steps - warmup the first post-warm-up state is left out; at least 4 are
+        needed).  A frozen variable's rhat, tau and ess are NaN.  The samples are the same bits with and without.
         A copy of the sample matrix is moved: no solver state changes and the result is not fed back.  With `samples` and `seed`
         given no random stream is touched.  Raises RuntimeError when there is no graph / tree yet, NotImplementedError naming a
         factor class without a device code, ValueError for bad points or options -- before anything is launched."""
@@ -505,6 +513,8 @@ class PosteriorEvaluation:
             if held and every:
                 raise ValueError("independence steps propose every variable: not together with frozen variables")
             opt = ST.check_metropolis_options(pts.total_dim, steps, float(step_size), None, kernel, warmup, None, seed)
+            if diagnostics:
+                ST.check_chain_options(pts.total_dim, opt["steps"], opt["warmup"], {}, least=4)
         except ValueError as e:
             raise ValueError("%s: %s" % (what, e)) from None
         scale = self._column_scale(pts, flags, cols, bool(standardise))
@@ -528,17 +538,27 @@ class PosteriorEvaluation:
                                        tb["device"], Zt=Zt).t().contiguous()
             return Y, self._log_q_launch(pts.over(Y))
 
+        record = dict(levels=None, center=None) if diagnostics else None    # (the centres: the starting points' means)
         res = ST.metropolis_refine_t(work.St, lambda Xt: self._joint_launch(pts.over(Xt)),
                                      lambda Xt: self._score_launch(pts.over(Xt)), opt["steps"], h, circular=flags, kernel=kernel,
                                      warmup=opt["warmup"], seed=seed, independence=(int(every), draw_t) if every else None,
-                                     log_q_t=(lambda Xt: self._log_q_launch(pts.over(Xt))) if every else None)
+                                     log_q_t=(lambda Xt: self._log_q_launch(pts.over(Xt))) if every else None, record=record)
         h_end = res["h"].cpu().numpy()
         local, jump = res["local_steps"], res["jump_steps"]
-        return dict(samples=self._samples_of(work.St, pcol), log_p=res["log_p"].cpu().numpy(),
-                    accept_rate=float(res["accepts"].sum().item()) / (local * pts.rows) if local else None,
-                    jump_accept_rate=float(res["jump_accepts"].sum().item()) / (jump * pts.rows) if jump else None,
-                    step_size={v: h_end[pcol[v]:pcol[v] + v.dim].copy() for v in order}, steps=res["steps"],
-                    warmup=res["warmup"], kernel=kernel, n=pts.rows, seed=seed)
+        out = dict(samples=self._samples_of(work.St, pcol), log_p=res["log_p"].cpu().numpy(),
+                   accept_rate=float(res["accepts"].sum().item()) / (local * pts.rows) if local else None,
+                   jump_accept_rate=float(res["jump_accepts"].sum().item()) / (jump * pts.rows) if jump else None,
+                   step_size={v: h_end[pcol[v]:pcol[v] + v.dim].copy() for v in order}, steps=res["steps"],
+                   warmup=res["warmup"], kernel=kernel, n=pts.rows, seed=seed)
+        if diagnostics:
+            ch = res["chains"]
+            moving = cols[h_end[cols] > 0]
+            rh, es = ch["rhat"][moving], ch["ess"][moving]
+            out.update(diagnostics={v: {k: ch[k][pcol[v]:pcol[v] + v.dim].copy() for k in ("mean", "rhat", "tau", "ess", "resolved")}
+                                    for v in order},
+                       rhat_max=float(np.max(rh[~np.isnan(rh)])) if np.any(~np.isnan(rh)) else float("nan"),
+                       ess_min=float(np.min(es[~np.isnan(es)])) if np.any(~np.isnan(es)) else float("nan"), recorded=ch["T"])
+        return out
 
     # ---- curvature: Hessian-vector products, truncated-Newton MAP ascent, the Laplace approximation at a mode ---------------------
     def _hvp_launch(self, pts: EvalPoints, Vt, score: bool = False):

@@ -708,6 +708,14 @@ METROPOLIS_TARGET = {"mala": 0.574, "rw": 0.234}                      # the opti
 # exp(-2 pi (pi - |rho|) / h^2) of it: below 2^-53 while |rho| <= pi - 5.85 h^2, which for h <= 0.3 rad is 2.61 rad >= 8.7 h --
 # a normal draw beyond 8.7 sigma has probability 3e-18.  
 WRAP_STEP_MAX = 0.3
+# The blocking plateau's conventions (`blocking_tau`).  A level counts once its pooled variance of block means rests on at least
+# BLOCKING_MIN_DOF degrees of freedom: the estimate's relative standard error is sqrt(2 / dof), 18 % at 64.  The estimate is called
+# resolved once the longest counted block spans at least BLOCKING_PLATEAU autocorrelation times: at b = 4 tau an AR(1) chain's
+# blocking estimate has reached about 1 - tau / (2 b) = 7/8 of its limit; below that the estimate is still growing with b and is
+# a LOWER bound.  Both are conventions, not theorems.
+BLOCKING_MIN_DOF = 64
+BLOCKING_PLATEAU = 4.0
+CHAIN_DEFAULT_LEVELS = 8                                              # record["levels"] = None: min(8, floor(log2 T))
 
 
 def check_metropolis_options(width, steps=0, step_size=1.0, circular=None, kernel="mala", warmup=0, target_accept=None, seed=None,
@@ -758,6 +766,87 @@ def check_metropolis_options(width, steps=0, step_size=1.0, circular=None, kerne
                 seed=None if seed is None else int(seed), every=int(every), draw_t=draw_t)
 
 
+def check_chain_options(width, steps, warmup, record, least=2):
+    """The `record` option of the Metropolis functions, checked with no device: None (nothing is recorded -> None), or a dict with
+    the optional keys `levels` (the blocking levels, block lengths 1 ... 2^(levels - 1); None: min(8, floor(log2 T))) and `center`
+    (one finite value per column, about which the deviations are taken; None: the starting points' means).  The states after the
+    steps t >= warmup are recorded; T of them, an even count: of an odd number of post-warm-up states the FIRST is not recorded.
+    ValueError for T < `least` (2 for the sums; `posterior_mcmc` asks for the 4 that split-R-hat needs) and for levels outside
+    [1, min(16, floor(log2 T))].
+    -> dict(T, first: the first recorded step, levels, center)."""
+    if record is None:
+        return None
+    if not isinstance(record, dict) or set(record) - {"levels", "center"}:
+        raise ValueError("record is None or a dict with the optional keys 'levels' and 'center', got %r" % (record,))
+    count = int(steps) - int(warmup)
+    T, first = count - (count & 1), int(warmup) + (count & 1)
+    if T < max(int(least), 2):
+        raise ValueError("at least %d recorded states are needed: steps - warmup = %d leaves %d" % (max(int(least), 2), count, max(T, 0)))
+    top = min(16, T.bit_length() - 1)
+    levels = record.get("levels")
+    if levels is None:
+        levels = min(CHAIN_DEFAULT_LEVELS, top)
+    elif isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 1 <= int(levels) <= top:
+        raise ValueError("record['levels'] must be an integer in [1, min(16, floor(log2 T)) = %d] for T = %d recorded states, got %r"
+                         % (top, T, levels))
+    center = record.get("center")
+    if center is not None:
+        on_device = hasattr(center, "is_cuda") and center.is_cuda
+        if tuple(center.shape if on_device else np.shape(center)) != (int(width),):
+            raise ValueError("record['center'] must have one value per column (%d)" % width)
+        if not on_device:
+            center = np.asarray(center, dtype=np.float64)
+            if not np.all(np.isfinite(center)):
+                raise ValueError("record['center'] must be finite")
+    return dict(T=T, first=first, levels=int(levels), center=center)
+
+
+def blocking_tau(tau_levels, T: int, n: int) -> dict:
+    """Which of the blocking estimates to quote.  tau_levels [levels] or [levels, columns]: the estimates of the integrated
+    autocorrelation time at block lengths 1, 2, ..., 2^(levels - 1) (`nfisam_hip.chain_finish_t`'s "tau"), from n chains of T
+    recorded states.  Level l has m_l = T >> l blocks per chain; it COUNTS when its pooled degrees of freedom n (m_l - 1) are at
+    least BLOCKING_MIN_DOF = 64.
+    -> dict(tau: the largest estimate among the levels that count (NaN where one of them is NaN: a column without spread);
+    ess = n T / tau; resolved: True iff the longest block that counts is at least BLOCKING_PLATEAU = 4 times tau; level: the
+    longest level that counts, -1 if none does -- then tau and ess are NaN and resolved is False).
+    The blocking estimate grows with the block length towards the autocorrelation time and flattens once blocks are
+    independent.  resolved = False therefore means that the plateau was NOT seen: tau is then a LOWER bound on the
+    autocorrelation time and ess an UPPER bound on the effective sample size -- run longer, or record more levels."""
+    tl = np.asarray(tau_levels, dtype=np.float64)
+    if tl.ndim not in (1, 2) or tl.shape[0] < 1:
+        raise ValueError("tau_levels must be [levels] or [levels, columns]")
+    for name, v in (("T", T), ("n", n)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+            raise ValueError("%s must be a positive integer, got %r" % (name, v))
+    T, n = int(T), int(n)
+    if T < 2 or T % 2 or tl.shape[0] > min(16, T.bit_length() - 1):
+        raise ValueError("T must be even and >= 2, with at most min(16, floor(log2 T)) levels: got T = %d and %d levels"
+                         % (T, tl.shape[0]))
+    counts = n * ((T >> np.arange(tl.shape[0])) - 1) >= BLOCKING_MIN_DOF
+    if not counts.any():
+        nan = np.full(tl.shape[1:], np.nan)
+        return dict(tau=nan, ess=nan.copy(), resolved=np.zeros(tl.shape[1:], dtype=bool), level=-1)
+    top = int(np.flatnonzero(counts).max())                           # (the counts fall with the level: levels 0 ... top count)
+    tau = np.max(tl[:top + 1], axis=0)                                # np.max keeps a NaN
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ess = n * T / tau
+    return dict(tau=tau, ess=ess, resolved=float(1 << top) >= BLOCKING_PLATEAU * tau, level=top)
+
+
+def chain_statistics_t(state, D, n, levels, T, center=None, wrap=None, tables=None) -> dict:
+    """The statistics of the T states that `nfisam_hip.chain_record_t` folded into `state`: `nfisam_hip.chain_finish_t` on the
+    device, then `blocking_tau` on the host.
+    -> dict of numpy arrays: mean [D], within [D] (the pooled within-chain variance), rhat [D] (split-R-hat; NaN on a column
+    without spread), tau_levels [levels, D], tau [D], ess [D], resolved [D] bool (False: tau is a lower bound, see
+    `blocking_tau`); T, n, levels."""
+    import nfisam_hip as _nh
+    res = _nh.chain_finish_t(state, D, n, levels, T, center, wrap, tables=tables)
+    host = {k: v.cpu().numpy() for k, v in res.items()}
+    pick = blocking_tau(host["tau"], int(T), int(n))
+    return dict(mean=host["mean"], within=host["within"], rhat=host["rhat"], tau_levels=host["tau"], tau=pick["tau"],
+                ess=pick["ess"], resolved=pick["resolved"], T=int(T), n=int(n), levels=int(levels))
+
+
 def _lp64(v, n, what):
     import torch
     if not torch.is_tensor(v) or tuple(v.shape) != (n,):
@@ -766,7 +855,7 @@ def _lp64(v, n, what):
 
 
 def metropolis_refine_t(Xt, log_p_t, score_t, steps, step_size, circular=None, kernel="mala", warmup=0, target_accept=None,
-                        seed=None, independence=None, after_step=None, log_q_t=None) -> dict:
+                        seed=None, independence=None, after_step=None, log_q_t=None, record=None) -> dict:
     """n parallel Metropolis chains, one per column of the COLUMN-major device matrix Xt [D, n] (contiguous float32), IN PLACE
     and entirely on the device; their stationary distribution is exp(log p) itself.  log_p_t: a callable Xt -> log p [n]
     (float64 device tensor, e.g. around `nfisam_hip.factor_graph_log_density_t`); score_t: a callable Xt -> grad log p [D, n]
@@ -782,6 +871,14 @@ def metropolis_refine_t(Xt, log_p_t, score_t, steps, step_size, circular=None, k
     independence=(every, draw_t): every `every`-th step proposes Yt, log_q_y = draw_t(n, t) ([D, n] float32, [n]) -- fresh draws
     of a density q, e.g. the flow -- and accepts through the same entry with lp = log p - log q: a global jump between modes.
     It needs `log_q_t`, a callable Xt -> log q [n] for the current state.  after_step: a callable (Xt, step index).
+    record: None, or dict(levels=None, center=None) (`check_chain_options`): the state after every step t >= warmup is folded
+    into streaming accumulators on the device (`nfisam_hip.chain_record_t`, after the caller's own after_step), and the result
+    gains `chains`, the dict of `chain_statistics_t`: per column the mean over chains and recorded states, split-R-hat, the
+    blocking autocorrelation time tau, ess = n T / tau and `resolved` (False: tau is a lower bound).  An even number of states
+    is recorded: of an odd number of post-warm-up steps the state after the FIRST is left out.  center None: the starting
+    points' means (the circular mean of a circular column).  A frozen column (step 0) keeps its mean and within; its rhat, tau
+    and ess are NaN and its resolved False.  Recording only reads Xt: the chains are the same bits with and without it, and
+    with record=None not one key of the result changes.
     seed: the generator's key (None: one below 2^62 from numpy's global RNG, `DeviceSimulation`'s rule); step t uses counter
     word t, so two runs with one seed give the same bits.
     -> dict(accepts [n] int64: accepted local steps per chain; jump_accepts [n] int64; h [D] float64: the final step lengths;
@@ -798,9 +895,12 @@ def metropolis_refine_t(Xt, log_p_t, score_t, steps, step_size, circular=None, k
         raise ValueError("independence steps need log_q_t, a callable Xt -> log q at the current state")
     if after_step is not None and not callable(after_step):
         raise ValueError("after_step must be a callable (Xt, step index)")
+    rec = check_chain_options(int(Xt.shape[0]), opt["steps"], opt["warmup"], record)
     D, n = _nh._column_major_front("Xt", Xt)
     flags = opt["flags"]
     _nh.check_mcmc_args(D, n, opt["h"], flags.astype(np.uint8) if flags.any() else None)
+    if rec is not None:
+        _nh.check_chain_args(D, n, rec["levels"], rec["T"], 0, rec["center"], flags.astype(np.uint8) if flags.any() else None)
     seed = int(np.random.randint(0, 2 ** 62)) if opt["seed"] is None else opt["seed"]
     device, mala = Xt.device, kernel == "mala"
     zeros = torch.zeros(n, dtype=torch.int64, device=device)
@@ -818,6 +918,14 @@ def metropolis_refine_t(Xt, log_p_t, score_t, steps, step_size, circular=None, k
         Gx = score_t(Xt) if mala else None
         Yt = torch.empty_like(Xt)
         scratch = _nh.sample_accept_scratch(D, n, device)
+        if rec is not None:
+            center = rec["center"]
+            if center is None:                                         # the starting points' means, as `posterior_summary` takes them
+                circ = flags.astype(np.uint8) if flags.any() else None
+                center = _nh.sample_moments_t(Xt, _nh.pack_moment_blocks(np.ones(D, dtype=np.int64)), np.arange(D), circ, None,
+                                              checked=True)[0]
+            chain_tb = _nh.chain_tables(device, center, flags.astype(np.uint8) if flags.any() else None)
+            chain_st = _nh.chain_state(D, n, rec["levels"], device)
         for t in range(opt["steps"]):
             if opt["every"] and (t + 1) % opt["every"] == 0:           # a global jump: an independence proposal from q
                 Y, lq_y = opt["draw_t"](n, t)
@@ -845,15 +953,25 @@ def metropolis_refine_t(Xt, log_p_t, score_t, steps, step_size, circular=None, k
                     h.copy_(scaled if cap is None else torch.minimum(scaled, cap))
             if after_step is not None:
                 after_step(Xt, t)
+            if rec is not None and t >= rec["first"]:
+                _nh.chain_record_t(chain_st, Xt, t - rec["first"], rec["T"], rec["levels"], checked=True, tables=chain_tb)
+        if rec is not None:
+            out["chains"] = ch = chain_statistics_t(chain_st, D, n, rec["levels"], rec["T"], tables=chain_tb)
+            frozen = opt["h"] == 0                                     # no spread within a chain: said by the step lengths, not left
+            for k in ("rhat", "tau", "ess"):                           # to the rounding of a variance that is zero
+                ch[k] = np.where(frozen, np.nan, ch[k])
+            ch["tau_levels"] = np.where(frozen[None, :], np.nan, ch["tau_levels"])
+            ch["resolved"] = ch["resolved"] & ~frozen
     return dict(out, h=h, log_p=lp)
 
 
 def metropolis_refine(x, log_p, score, steps, step_size, circular=None, kernel="mala", warmup=0, target_accept=None, seed=None,
-                      device=None) -> dict:
+                      device=None, record=None) -> dict:
     """`metropolis_refine_t` for row-major points x [n, D] (numpy or torch) and a target given as callables on numpy:
     log_p(points [n, D] float64) -> [n], score(points) -> [n, D] (unused for kernel="rw").  The proposal and the accept step run
-    on the device; the callables are called on the host once per step -- the convenience form.
-    -> dict(x [n, D] float32 numpy: the chains' final states, log_p [n], accepts [n], h [D], steps, warmup, seed)."""
+    on the device; the callables are called on the host once per step -- the convenience form.  record: as there.
+    -> dict(x [n, D] float32 numpy: the chains' final states, log_p [n], accepts [n], h [D], steps, warmup, seed; with `record`
+    also chains, the dict of `chain_statistics_t`)."""
     import nfisam_hip as _nh
     import torch
     if not callable(log_p) or (kernel == "mala" and not callable(score)):
@@ -863,7 +981,8 @@ def metropolis_refine(x, log_p, score, steps, step_size, circular=None, kernel="
     n, D = int(x.shape[0]), int(x.shape[1])
     if n < 1 or D < 1:
         raise ValueError("at least one point and one column are needed")
-    check_metropolis_options(D, steps, step_size, circular, kernel, warmup, target_accept, seed)
+    opt = check_metropolis_options(D, steps, step_size, circular, kernel, warmup, target_accept, seed)
+    check_chain_options(D, opt["steps"], opt["warmup"], record)
     device = _nh._row_major_front("metropolis_refine", device, x=x)
     Xt = _nh._columns(x, device)
 
@@ -882,9 +1001,10 @@ def metropolis_refine(x, log_p, score, steps, step_size, circular=None, kernel="
             raise ValueError("score must return the shape of x, %s, got %s" % ((n, D), g.shape))
         return torch.from_numpy(np.ascontiguousarray(g.T)).to(Xt.device)
 
-    res = metropolis_refine_t(Xt, log_p_t, score_t, steps, step_size, circular, kernel, warmup, target_accept, seed)
-    return dict(x=Xt.t().cpu().numpy().copy(), log_p=res["log_p"].cpu().numpy(), accepts=res["accepts"].cpu().numpy(),
-                h=res["h"].cpu().numpy(), steps=res["steps"], warmup=res["warmup"], seed=res["seed"])
+    res = metropolis_refine_t(Xt, log_p_t, score_t, steps, step_size, circular, kernel, warmup, target_accept, seed, record=record)
+    out = dict(x=Xt.t().cpu().numpy().copy(), log_p=res["log_p"].cpu().numpy(), accepts=res["accepts"].cpu().numpy(),
+               h=res["h"].cpu().numpy(), steps=res["steps"], warmup=res["warmup"], seed=res["seed"])
+    return dict(out, chains=res["chains"]) if record is not None else out
 
 
 # ---- curvature: matrix-free conjugate gradients on Hessian-vector products, truncated Newton ascent (nfisam_factor_graph_hvp) ----
