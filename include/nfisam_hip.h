@@ -602,6 +602,66 @@ int nfisam_sample_modes_merge(int x_rows, int n, const nfisam_mmd_block* blocks,
                               int32_t* n_modes, double* mode_pos, double* mode_dens, double* mode_mass, int32_t* unlabelled,
                               nfisam_stream_t stream);
 
+/* ---- k nearest neighbours and ball counts: a selection over pairs of points (sample_knn.hip) -------------------------------
+ * What differential entropy (Kozachenko-Leonenko), mutual information (Kraskov-Stoegbauer-Grassberger) and a two-sample KL
+ * divergence (Wang-Kulkarni-Verdu) of a sample set are estimated from, for posteriors whose marginals are rings or have two
+ * modes, where 1/2 log det(2 pi e Sigma) is wrong by nats.  They stand in for nothing of the reference: it has no entropy or
+ * information measure (its src/utils/Statistics.py stops at MMD, RMSE and KSD).  The estimators are formed on the host
+ * (utils/Statistics.py: knn_entropy, knn_mutual_information, knn_divergence) from what these two entries return.
+ * Xt[x_rows][m] holds the QUERIES and Yt[y_rows][n] the POINTS (COLUMN-major float32 device matrices, the layout of the tree
+ * walk's St; they may be the same matrix).  Entry e names row xcols[e] of Xt and row ycols[e] of Yt, as in nfisam_sample_mmd;
+ * block b is the run of entries col_off .. col_off + d, 1 <= d <= NFISAM_KNN_MAX_D.  Blocks may overlap and repeat entries.
+ * For query i and point j of block b
+ *     u_e  = scale_e * wrap_e((double)x_ie - (double)y_je)    (scale NULL: 1; wrap_e brings the difference into [-pi, pi) where
+ *                                                              wrap[e] is set -- wrap_pi, the sign convention of theta_to_pipi)
+ *     dist = max_e |u_e|  (NFISAM_KNN_NORM_MAX)   or   sqrt(sum_e u_e^2), the sum in ascending e  (NFISAM_KNN_NORM_L2).
+ * A NaN u_e makes the distance NaN under either norm.
+ *
+ * nfisam_sample_knn: for every query and block the k smallest distances to the n points, candidates ordered by (distance, j):
+ * on equal distances the lower j comes first.
+ *   dist [n_blocks][k][m] double, ascending in k;  idx [n_blocks][k][m] int32 (nullable): the j of each.
+ *   Slots with no candidate hold +inf and index -1.  exclude_self != 0 skips the pair j == i (it requires m == n).  A NaN
+ *   distance never enters a list -- a query with a NaN coordinate gets +inf / -1 throughout -- and neither does an infinite
+ *   one, which could not be told from an empty slot.
+ *   log_sum [n_blocks] double (nullable) = sum_i log(dist[b][k-1][i]) over the queries whose k-th distance is positive and
+ *   finite, n_used [n_blocks] int32 (nullable) = how many queries that was; by a second small launch in the family's fixed
+ *   order (thread t adds queries t, t + 256, ... ascending, wave_sum, waves_in_order; sample_common.h), no float atomics.
+ * nfisam_sample_ball_count: count [n_blocks][m] int32, count[b][i] = #{ j : dist_b(x_i, y_j) < radius[blocks[b].radius_row][i] },
+ *   radius [n_radius][m] double on the device.  The comparison is strict; a NaN or negative radius gives 0; exclude_self as
+ *   above.  (The marginal counts of KSG-1 inside the joint block's k-th distance.)
+ *   blocks[n_blocks]: HOST copy of the table (validated here), blocks_dev: DEVICE copy (what the kernels read); xcols, ycols
+ *   [n_entries] int32, scale [n_entries] double (nullable), wrap [n_entries] uint8 (nullable): DEVICE arrays.
+ * Float32 points in; the float64 difference of two float32 values is exact, so the max norm carries ONE rounding (by scale) and
+ * no sum; L2 adds d products and a square root.  A 256-thread group per (64 queries, block), one query per lane; the four
+ * waves each take 16 of every 64 points staged in LDS, a thread keeps its best k (distance, j) in registers, and the four
+ * lists of a query are merged through LDS by (distance, j).  Two calls give the same bits; a block's results do not depend on
+ * its place in the table, on other blocks or on repeated entries; a query's results do not depend on m.
+ * NFISAM_ERR_ARG, before any launch: a NULL pointer (scale, wrap, idx, log_sum and n_used excepted); m, n, x_rows, y_rows,
+ * n_entries or n_blocks < 1; more than 65535 blocks, or more than 65535 64-wide tiles of queries or of points; k outside
+ * 1 .. NFISAM_KNN_MAX_K; an unknown norm; a block of the host copy with d outside 1 .. 16; exclude_self with m != n; n_radius
+ * < 1 or a radius_row of the host copy outside [0, n_radius).  The device copy of the table is not trusted: a block whose
+ * entries leave [0, n_entries), that names a row outside its matrix or whose d is outside 1 .. 16 (for the count: or whose
+ * radius_row is outside [0, n_radius)) yields NaN dist, -1 idx, NaN log_sum, 0 n_used and -1 count; nothing is read out of
+ * bounds and every other block is untouched.  The Python binding refuses such tables before upload.  (Additive: ABI 1600.) */
+#define NFISAM_KNN_MAX_D     16   /* widest block */
+#define NFISAM_KNN_MAX_K     16   /* most neighbours per query */
+#define NFISAM_KNN_NORM_MAX  0    /* max_e |u_e| */
+#define NFISAM_KNN_NORM_L2   1    /* sqrt(sum_e u_e^2) */
+typedef struct nfisam_knn_block {
+    int32_t col_off;           /* first entry of the block in xcols / ycols / scale / wrap */
+    int32_t d;                 /* number of entries, 1 .. NFISAM_KNN_MAX_D */
+    int32_t radius_row;        /* row of `radius` the block's queries take (read by nfisam_sample_ball_count alone) */
+    int32_t reserved;
+} nfisam_knn_block;
+int nfisam_sample_knn(const float* Xt, int x_rows, int m, const float* Yt, int y_rows, int n, int exclude_self,
+                      const nfisam_knn_block* blocks, const nfisam_knn_block* blocks_dev, int n_blocks, const int32_t* xcols,
+                      const int32_t* ycols, int n_entries, const double* scale, const uint8_t* wrap, int k, int norm, double* dist,
+                      int32_t* idx, double* log_sum, int32_t* n_used, nfisam_stream_t stream);
+int nfisam_sample_ball_count(const float* Xt, int x_rows, int m, const float* Yt, int y_rows, int n, int exclude_self,
+                             const nfisam_knn_block* blocks, const nfisam_knn_block* blocks_dev, int n_blocks, const int32_t* xcols,
+                             const int32_t* ycols, int n_entries, const double* scale, const uint8_t* wrap, int norm,
+                             const double* radius, int n_radius, int32_t* count, nfisam_stream_t stream);
+
 /* ---- training -------------------------------------------------------------------------- */
 /* Vector-Jacobian product of the L-layer flow (what torch autograd computes for
  * `loss.backward()` in slam/NFiSAM.py:474): kgrad[L*kparam_count] += d<gz,z>/dtheta + d<gl,logdet>/dtheta,

@@ -37,6 +37,7 @@ EXPORTS = [
     "nfisam_sample_svgd", "nfisam_sample_svgd_scratch_count", "nfisam_sample_step",
     "nfisam_sample_propose", "nfisam_sample_accept", "nfisam_sample_accept_scratch_count",
     "nfisam_chain_record", "nfisam_chain_finish", "nfisam_chain_state_count",
+    "nfisam_sample_knn", "nfisam_sample_ball_count",
 ]
 
 
@@ -1909,3 +1910,175 @@ def sample_modes_merge_t(out, x_rows: int, blocks: np.ndarray, cols, scale=None,
                                                _ptr(pos), _ptr(dens), *[_ptr(res[k]) for k in MODE_KEYS[3:]], _stream()),
                "nfisam_sample_modes_merge")
     return res
+
+
+# ---- k nearest neighbours and ball counts: a selection over pairs (nfisam_sample_knn, nfisam_sample_ball_count) ---------------
+class KnnBlock(C.Structure):
+    _fields_ = [("col_off", C.c_int32), ("d", C.c_int32), ("radius_row", C.c_int32), ("reserved", C.c_int32)]
+
+
+KNN_BLOCK_DTYPE = np.dtype([("col_off", np.int32), ("d", np.int32), ("radius_row", np.int32), ("reserved", np.int32)])
+assert KNN_BLOCK_DTYPE.itemsize == C.sizeof(KnnBlock) == 16
+KNN_MAX_D, KNN_MAX_K = 16, 16                    # NFISAM_KNN_MAX_D, NFISAM_KNN_MAX_K
+KNN_NORMS = {"max": 0, "l2": 1}                  # NFISAM_KNN_NORM_MAX, NFISAM_KNN_NORM_L2
+KNN_KEYS = ("dist", "idx", "log_sum", "n_used")
+
+
+def pack_knn_blocks(dims, radius_rows=None) -> np.ndarray:
+    """The block table (numpy KNN_BLOCK_DTYPE) of consecutive blocks of `dims` entries; radius_rows: the row of `radius` each
+    block's queries take in `sample_ball_count` (default: all 0)."""
+    dims = np.asarray(dims, dtype=np.int64).reshape(-1)
+    t = np.zeros(dims.size, dtype=KNN_BLOCK_DTYPE)
+    t["d"] = dims
+    t["col_off"] = np.cumsum(dims) - dims
+    if radius_rows is not None:
+        t["radius_row"] = np.asarray(radius_rows, dtype=np.int64).reshape(-1)
+    return t
+
+
+def check_knn_blocks(blocks: np.ndarray, xcols, ycols, x_rows: int, y_rows: int, scale=None, wrap=None, n_radius: int = None) -> None:
+    """ValueError for tables the kernels must not see: no block or more than 65535, d outside 1..16, entries outside
+    [0, n_entries), a row outside [0, x_rows) / [0, y_rows), per-entry arrays of another length, a scale that is not finite
+    (a device tensor's length alone is checked), with `n_radius` a radius_row outside [0, n_radius)."""
+    cols = {"xcols": (xcols, x_rows), "ycols": (ycols, y_rows)}
+    _check_table_layout(blocks, KNN_BLOCK_DTYPE, "KNN_BLOCK_DTYPE", cols, dict(scale=scale, wrap=wrap), KNN_MAX_D)
+    _check_rows(cols)
+    if scale is not None and not (torch.is_tensor(scale) and scale.is_cuda):     # (a device tensor is taken as it is)
+        if not np.all(np.isfinite(np.asarray(scale, dtype=np.float64))):
+            raise ValueError("scale must be finite")
+    if n_radius is not None:
+        rr = blocks["radius_row"].astype(np.int64)
+        bad = (rr < 0) | (rr >= int(n_radius))
+        if np.any(bad):
+            b = int(np.argmax(bad))
+            raise ValueError("block %d: radius_row %d is out of range of the %d rows of radius" % (b, int(rr[b]), int(n_radius)))
+
+
+def check_knn_args(m: int, n: int, k=1, norm="max", exclude_self=False) -> int:
+    """ValueError for the scalar arguments nfisam_sample_knn / nfisam_sample_ball_count refuse -> the norm's code."""
+    if m < 1 or n < 1:
+        raise ValueError("both sample sets need at least one point")
+    if max(m, n) > 65535 * 64:
+        raise ValueError("%d x %d points are out of range of the grid (65535 tiles of 64)" % (m, n))
+    if int(k) != k or not 1 <= int(k) <= KNN_MAX_K:
+        raise ValueError("k must be an integer in 1..%d, got %r" % (KNN_MAX_K, k))
+    if norm not in KNN_NORMS:
+        raise ValueError("norm must be one of %s, got %r" % (sorted(KNN_NORMS), norm))
+    if exclude_self and m != n:
+        raise ValueError("exclude_self needs the two sets to be one (m = %d, n = %d)" % (m, n))
+    return KNN_NORMS[norm]
+
+
+def _knn_front(what, Xt, Yt):
+    """The head of the two column-major bindings: Yt None is Xt -> (Yt, x_rows, m, y_rows, n)."""
+    x_rows, m = _column_major_front("Xt", Xt)
+    if Yt is None:
+        Yt = Xt
+    y_rows, n = _column_major_front("Yt", Yt)
+    if Xt.device != Yt.device:
+        raise ValueError("Xt and Yt must be on the same device")
+    return Yt, x_rows, m, y_rows, n
+
+
+def _knn_upload(device, blocks, xcols, ycols, scale, wrap):
+    xc, yc = np.asarray(xcols, dtype=np.int32), np.asarray(ycols, dtype=np.int32)
+    return _upload_named(device, blocks=_table_bytes(blocks), xcols=xc, ycols=yc, scale=_entry_f64(scale), wrap=_flags(wrap)), int(xc.size)
+
+
+def sample_knn(X, Y, blocks: np.ndarray, xcols, ycols, k=4, norm="max", scale=None, wrap=None, exclude_self=False, device=None):
+    """The k nearest neighbours of every row of X [m, x_cols] among the rows of Y [n, y_cols] (tensor or numpy; Y None: X
+    itself), within every block of `blocks`: nfisam_sample_knn, all blocks in one launch on the current stream.  `blocks`:
+    numpy KNN_BLOCK_DTYPE (`pack_knn_blocks`: widths 1..16); entry e of a block pairs column xcols[e] of X with column
+    ycols[e] of Y; scale [n_entries] multiplies an entry's differences, wrap [n_entries] marks angles (differences brought
+    into [-pi, pi)); norm "max" or "l2"; exclude_self skips the pair j == i (m == n).
+    -> dict of device tensors: dist [n_blocks, k, m] float64 ascending in k (+inf where there is no candidate), idx
+    [n_blocks, k, m] int32 (-1 there; equal distances by ascending j), log_sum [n_blocks] float64 (the sum of log(k-th
+    distance) over the queries where that is positive and finite), n_used [n_blocks] int32 (how many those were)."""
+    mats = dict(X=X) if Y is None else dict(X=X, Y=Y)
+    device = _row_major_front("sample_knn", device, **mats)
+    other = X if Y is None else Y
+    check_knn_blocks(blocks, xcols, ycols, int(X.shape[1]), int(other.shape[1]), scale, wrap)
+    check_knn_args(int(X.shape[0]), int(other.shape[0]), k, norm, exclude_self)
+    Xt = _columns(X, device)
+    return sample_knn_t(Xt, None if Y is None else _columns(Y, device), blocks, xcols, ycols, k, norm, scale, wrap, exclude_self,
+                        checked=True)
+
+
+def sample_knn_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, k=4, norm="max", scale=None, wrap=None, exclude_self=False,
+                 checked=False, out=None):
+    """`sample_knn` on the COLUMN-major matrices Xt [x_rows, m], Yt [y_rows, n] (contiguous float32 device tensors, used in
+    place; Yt None: Xt): what the tree walk wrote.  `checked` skips the table and argument checks (the caller has made them);
+    `out`: the dict of an earlier call with the same shapes, written in place."""
+    Yt, x_rows, m, y_rows, n = _knn_front("sample_knn", Xt, Yt)
+    if not checked:
+        check_knn_blocks(blocks, xcols, ycols, x_rows, y_rows, scale, wrap)
+        check_knn_args(m, n, k, norm, exclude_self)
+    device, nb, kk = Xt.device, int(blocks.shape[0]), max(int(k), 1)
+    shapes = dict(dist=((nb, kk, m), torch.float64), idx=((nb, kk, m), torch.int32), log_sum=((nb,), torch.float64),
+                  n_used=((nb,), torch.int32))
+    if out is not None:
+        for key, (shape, dt) in shapes.items():
+            t = out.get(key)
+            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or t.device != device or not t.is_contiguous():
+                raise ValueError("out[%r] must be a contiguous %s tensor of shape %s on %s" % (key, dt, shape, device))
+    blocks = np.ascontiguousarray(blocks)
+    with torch.cuda.device(device):
+        dev, ne = _knn_upload(device, blocks, xcols, ycols, scale, wrap)
+        res = out if out is not None else {key: torch.empty(shape, dtype=dt, device=device) for key, (shape, dt) in shapes.items()}
+        _check(lib().nfisam_sample_knn(_ptr(Xt), x_rows, m, _ptr(Yt), y_rows, n, C.c_int(1 if exclude_self else 0),
+                                       blocks.ctypes.data_as(C.c_void_p), _ptr(dev["blocks"]), nb, _ptr(dev["xcols"]),
+                                       _ptr(dev["ycols"]), ne, _ptr(dev["scale"]), _ptr(dev["wrap"]), C.c_int(int(k)),
+                                       C.c_int(KNN_NORMS.get(norm, -1) if isinstance(norm, str) else int(norm)),
+                                       *[_ptr(res[key]) for key in KNN_KEYS], _stream()), "nfisam_sample_knn")
+    return res
+
+
+def sample_ball_count(X, Y, blocks: np.ndarray, xcols, ycols, radius, norm="max", scale=None, wrap=None, exclude_self=False,
+                      device=None):
+    """How many rows of Y [n, y_cols] (None: X itself) lie STRICTLY inside a radius of every row of X [m, x_cols], within every
+    block of `blocks`: nfisam_sample_ball_count, all blocks in one launch.  radius [n_radius, m] float64 (tensor or numpy):
+    block b's query i takes radius[blocks["radius_row"][b], i]; a NaN or negative radius counts nothing.  The other arguments
+    are those of `sample_knn`.  -> count [n_blocks, m] int32 device tensor."""
+    mats = dict(X=X) if Y is None else dict(X=X, Y=Y)
+    device = _row_major_front("sample_ball_count", device, **mats)
+    other = X if Y is None else Y
+    m = int(X.shape[0])
+    if not (torch.is_tensor(radius) or isinstance(radius, np.ndarray)) or radius.ndim != 2 or int(radius.shape[1]) != m or \
+            int(radius.shape[0]) < 1:
+        raise ValueError("radius must be [n_radius, m] = [>= 1, %d]" % m)
+    check_knn_blocks(blocks, xcols, ycols, int(X.shape[1]), int(other.shape[1]), scale, wrap, int(radius.shape[0]))
+    check_knn_args(m, int(other.shape[0]), 1, norm, exclude_self)
+    Xt = _columns(X, device)
+    return sample_ball_count_t(Xt, None if Y is None else _columns(Y, device), blocks, xcols, ycols, _f64(radius, device), norm,
+                               scale, wrap, exclude_self, checked=True)
+
+
+def sample_ball_count_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, radius, norm="max", scale=None, wrap=None, exclude_self=False,
+                        checked=False, out=None):
+    """`sample_ball_count` on the COLUMN-major matrices Xt [x_rows, m], Yt [y_rows, n] (Yt None: Xt); radius: a contiguous
+    float64 [n_radius, m] tensor on their device (rows of a `sample_knn_t` result's dist, for instance).  `out`: an int32
+    [n_blocks, m] device tensor written in place."""
+    Yt, x_rows, m, y_rows, n = _knn_front("sample_ball_count", Xt, Yt)
+    if not torch.is_tensor(radius) or not radius.is_cuda:
+        raise RuntimeError("radius must be a tensor on a ROCm device (no CPU path exists)")
+    if radius.ndim != 2 or radius.dtype != torch.float64 or not radius.is_contiguous() or int(radius.shape[1]) != m or \
+            int(radius.shape[0]) < 1 or radius.device != Xt.device:
+        raise ValueError("radius must be a contiguous float64 [n_radius, m] = [>= 1, %d] tensor on %s" % (m, Xt.device))
+    n_radius = int(radius.shape[0])
+    if not checked:
+        check_knn_blocks(blocks, xcols, ycols, x_rows, y_rows, scale, wrap, n_radius)
+        check_knn_args(m, n, 1, norm, exclude_self)
+    device, nb = Xt.device, int(blocks.shape[0])
+    if out is not None and (not torch.is_tensor(out) or tuple(out.shape) != (nb, m) or out.dtype != torch.int32 or
+                            out.device != device or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous int32 tensor of shape %s on %s" % ((nb, m), device))
+    blocks = np.ascontiguousarray(blocks)
+    with torch.cuda.device(device):
+        dev, ne = _knn_upload(device, blocks, xcols, ycols, scale, wrap)
+        count = out if out is not None else torch.empty(nb, m, dtype=torch.int32, device=device)
+        _check(lib().nfisam_sample_ball_count(_ptr(Xt), x_rows, m, _ptr(Yt), y_rows, n, C.c_int(1 if exclude_self else 0),
+                                              blocks.ctypes.data_as(C.c_void_p), _ptr(dev["blocks"]), nb, _ptr(dev["xcols"]),
+                                              _ptr(dev["ycols"]), ne, _ptr(dev["scale"]), _ptr(dev["wrap"]),
+                                              C.c_int(KNN_NORMS.get(norm, -1) if isinstance(norm, str) else int(norm)),
+                                              _ptr(radius), n_radius, _ptr(count), _stream()), "nfisam_sample_ball_count")
+    return count

@@ -1,6 +1,6 @@
 """slam.PosteriorEvaluation -- what a trained NFiSAM solver says about its posterior, not in the reference: densities
 (`posterior_log_pdf`, `joint_log_pdf`, `joint_score`), the solver grading itself (`posterior_diagnostics`, `map_estimate`,
-`posterior_ksd`, `posterior_mmd`), what the posterior holds (`posterior_summary`, `posterior_modes`), its samples moved
+`posterior_ksd`, `posterior_mmd`), what the posterior holds (`posterior_summary`, `posterior_modes`, `posterior_information`), its samples moved
 along the joint score (`posterior_refine`, `map_refine`), the joint density's curvature (`joint_hessian_product`,
 `map_newton`, `laplace_approximation`) and Metropolis chains that make the samples asymptotically exact (`posterior_mcmc`).
 
@@ -1019,4 +1019,87 @@ class PosteriorEvaluation:
             out["sigma"][key] = float(res["sigma"][b])
             out["not_converged"][key] = int(res["iterations"]["not_converged"][b])
             out["unlabelled"][key] = int(res["unlabelled"][b])
+        return out
+
+    # ---- how uncertain a variable is and how strongly two are coupled: entropies by k nearest neighbours -------------
+    def posterior_information(self, samples=None, n: int = None, variables=None, pairs=None, k: int = 4, standardise: bool = True,
+                              reference=None) -> dict:
+        """The differential entropy of every variable's marginal posterior and the mutual information of pairs of variables,
+        in nats, from the sample matrix the tree walk left on the device: the k nearest neighbours of every sample within
+        every block in one launch (nfisam_sample_knn / nfisam_sample_ball_count: float32 points, float64 arithmetic, max
+        norm), the Kozachenko-Leonenko and Kraskov-Stoegbauer-Grassberger formulas on the host
+        (utils.Statistics.knn_entropy_t, knn_mutual_information_t).  1/2 log det(2 pi e Sigma) from `posterior_summary`
+        overstates the uncertainty of a ring or of two modes by nats; the entropy here does not, and the difference of the
+        two -- the negentropy -- says how far from Gaussian a marginal is.
+
+        samples, n, variables and pairs are those of `posterior_summary` (samples=None draws `n`, default
+        posterior_sample_num, points and works on the device matrix where it lies).  k: 1..16 neighbours (more than k
+        samples are needed).  standardise: distances in columns divided by their spread (the circular standard deviation of
+        a heading, whose differences are wrapped), the entropy brought back to the original units; False: raw columns.
+        reference: mapping variable -> [m, dim] samples of another solution: adds `divergence`, the k-nearest-neighbour
+        estimate of KL(posterior || reference) of every variable that `reference` holds, over all its columns.
+        A joint block (a pair for the mutual information) wider than 16 columns is refused: the estimators' bias grows with
+        the dimension, and a k-nearest-neighbour entropy in hundreds of dimensions means nothing at n around 2000 -- which is
+        why there is no joint entropy of the whole graph here.
+        -> dict: entropy (variable -> nats; -inf for a variable with a column without spread, NaN when no sample could be
+        used), gaussian_entropy (variable -> 1/2 log det(2 pi e Sigma), Sigma the covariance `posterior_summary` reports for
+        the same points), negentropy (variable -> gaussian_entropy - entropy), mutual_information ((u, v) -> nats, for the
+        listed pairs; about 0, possibly slightly negative, for independent variables), divergence (variable -> nats; only with
+        `reference`), n, k, zeros (variable or pair -> samples left out because their k-th neighbour is at distance 0:
+        duplicates).
+        It consumes no random numbers (a draw apart), changes nothing in the solver, and raises what `posterior_summary`
+        raises, and ValueError for a bad k, too few samples, or a reference that lacks rows or has the wrong width -- before
+        anything is launched."""
+        from utils import Statistics as ST
+        what = "posterior_information"
+        pts, _, variables, pairs = self._summary_front(what, samples, n, variables, pairs, None)
+        rows = pts.rows
+        try:
+            ST.check_knn_options(pts.total_dim, k, "max", None, m=rows)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (what, e)) from None
+        graded, ref, rcol, width = [], None, {}, 0
+        if reference is not None:
+            graded = [v for v in variables if v in reference]
+            if not graded:
+                raise ValueError("%s: the reference holds none of the variables" % what)
+            ref, m_ref = self._check_points(reference, what, graded, _REFERENCE_NOUNS, host=True)
+            if m_ref < int(k):
+                raise ValueError("%s: the reference's %d points hold no %d-th neighbour" % (what, m_ref, int(k)))
+            for v in graded:
+                rcol[v] = width
+                width += v.dim
+
+        def cols_of(v):
+            return np.arange(pts.pcol[v], pts.pcol[v] + v.dim)
+
+        flags = np.zeros(pts.total_dim, dtype=bool)
+        for v in self._elimination_ordering:
+            flags[cols_of(v)] = [bool(c) for c in v.circular_dim_list]
+        scale = None if standardise else np.ones(pts.total_dim)
+        St = pts.St
+
+        ent = ST.knn_entropy_t(St, [cols_of(v) for v in variables], k, flags, scale, "max", checked=True)
+        table, cols, circ = self._summary_table(variables, [], pts.pcol)
+        blocks = _nh.pack_moment_blocks([v.dim for v in variables])
+        _, _, cov_d = _nh.sample_moments_t(St, blocks, cols, circ if circ.any() else None, None, checked=True)
+        cov = cov_d.cpu().numpy()
+        out = dict(entropy={}, gaussian_entropy={}, negentropy={}, mutual_information={}, n=rows, k=int(k), zeros={})
+        for b, (v, row) in enumerate(zip(variables, blocks)):
+            d, c = int(row["d"]), int(row["cov_off"])
+            sign, logdet = np.linalg.slogdet(cov[c:c + d * d].reshape(d, d))
+            gauss = 0.5 * (d * np.log(2.0 * np.pi * np.e) + logdet) if sign > 0 else float("-inf")
+            out["entropy"][v], out["gaussian_entropy"][v] = float(ent["entropy"][b]), float(gauss)
+            with np.errstate(invalid="ignore"):
+                out["negentropy"][v] = float(np.float64(gauss) - ent["entropy"][b])
+            out["zeros"][v] = int(ent["zeros"][b])
+        if pairs:
+            mi = ST.knn_mutual_information_t(St, [(cols_of(a), cols_of(b)) for a, b in pairs], k, flags, scale, checked=True)
+            for p, pair in enumerate(pairs):
+                out["mutual_information"][pair], out["zeros"][pair] = float(mi["mi"][p]), int(mi["zeros"][p])
+        if reference is not None:
+            Y = np.concatenate([ref[v] for v in graded], axis=1).astype(np.float32)
+            div = ST.knn_divergence_t(St, _nh._columns(Y, pts.device), [(cols_of(v), np.arange(rcol[v], rcol[v] + v.dim)) for v in graded],
+                                      k, flags, scale, "max", checked=True)
+            out["divergence"] = {v: float(div["divergence"][b]) for b, v in enumerate(graded)}
         return out

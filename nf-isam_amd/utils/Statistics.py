@@ -5,7 +5,12 @@ example/slam/small_range_gaussian_problem/icra_paper/mmd_rmse_time_da_plot_grid.
 sample set (reference: src/utils/Statistics.py:142-214): means with circular means for headings, covariances, resultant
 lengths and quantiles on the device, the modes of a multi-modal sample set (mean-shift on the device), `rmse`,
 `translation_distance` and `geodesic_distance` on the host; and the Gaussian kernel Stein discrepancy of a sample set
-against the density's own score (reference: src/utils/Statistics.py:193-245), its pairwise sums on the device."""
+against the density's own score (reference: src/utils/Statistics.py:193-245), its pairwise sums on the device; and -- not
+in the reference -- differential entropy, mutual information and a two-sample KL divergence by k nearest neighbours, the
+neighbour search on the device."""
+import functools
+import math
+
 import numpy as np
 
 
@@ -343,6 +348,291 @@ def sample_modes(x, blocks, circular=None, weights=None, sigma=None, scale=None,
     if not on_device:
         out["labels"] = out["labels"].cpu().numpy()
     return out
+
+
+# ---- how uncertain, how coupled: k-nearest-neighbour entropy, mutual information, divergence (nfisam_sample_knn) -------------
+EULER_GAMMA = 0.57721566490153286061
+
+
+def digamma_table(n: int) -> np.ndarray:
+    """psi(j) for j = 1 .. n as a float64 table t[j] (t[0] is NaN), by psi(1) = -gamma, psi(j + 1) = psi(j) + 1 / j.  The
+    running sum carries its rounding error along (Neumaier's compensation), so every entry is the float64 nearest to the sum
+    of the ROUNDED terms up to O(n u^2): within u (|psi(j)| + H_(j-1) / 2) of psi(j), not the n u / 2 of a plain recurrence."""
+    t = np.full(int(n) + 1, np.nan)
+    s, c = -EULER_GAMMA, 0.0
+    for j in range(1, int(n) + 1):
+        t[j] = s + c
+        term = 1.0 / j
+        r = s + term
+        c += (s - r) + term if abs(s) >= term else (term - r) + s
+        s = r
+    return t
+
+
+@functools.lru_cache(maxsize=8)
+def _psi(n: int) -> np.ndarray:
+    """`digamma_table(n)`, kept and read-only: the estimators ask for the same n block after block."""
+    t = digamma_table(n)
+    t.setflags(write=False)
+    return t
+
+
+def knn_log_unit_ball(d, norm: str):
+    """log of the volume of the unit ball of `norm` in d dimensions: d log 2 (max), (d / 2) log pi - lgamma(d / 2 + 1) (l2)."""
+    d = np.asarray(d, dtype=np.float64)
+    if norm == "max":
+        return d * math.log(2.0)
+    if norm == "l2":
+        return 0.5 * d * math.log(math.pi) - np.vectorize(math.lgamma)(0.5 * d + 1.0)
+    raise ValueError("norm must be 'max' or 'l2', got %r" % (norm,))
+
+
+def entropy_from_log_sum(log_sum, n_used, d, k: int, norm: str = "max", log_scale_sum=0.0) -> np.ndarray:
+    """Kozachenko-Leonenko, per block, on the host:
+        H = psi(n_used) - psi(k) + log c_d + (d / n_used) * log_sum - log_scale_sum
+    with log_sum the sum of log(eps_i) over the n_used queries whose k-th neighbour distance eps_i (a RADIUS, in the scaled
+    coordinates) is positive and finite, c_d the unit ball's volume and log_scale_sum = sum_e log scale_e, which brings the
+    entropy back to the original units.  NaN where n_used = 0.  -> float64 [n_blocks] nats."""
+    log_sum, ls = np.atleast_1d(np.asarray(log_sum, dtype=np.float64)), np.asarray(log_scale_sum, dtype=np.float64)
+    nu, d = np.atleast_1d(np.asarray(n_used, dtype=np.int64)), np.asarray(d, dtype=np.float64)
+    psi = _psi(max(int(nu.max(initial=1)), int(k), 1))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        h = psi[np.maximum(nu, 0)] - psi[int(k)] + knn_log_unit_ball(d, norm) + (d / nu) * log_sum - ls
+    return np.where(nu > 0, h, np.nan)
+
+
+def ksg_from_counts(n_a, n_b, k: int) -> float:
+    """Kraskov-Stoegbauer-Grassberger estimator 1 on the host: I = psi(k) + psi(n) - mean_i[psi(n_a_i + 1) + psi(n_b_i + 1)],
+    n_a_i / n_b_i the number of OTHER points strictly inside eps_i (the k-th max-norm distance in the joint space) in either
+    marginal space; psi from `digamma_table`, the 2 n terms added by math.fsum.  -> nats."""
+    n_a, n_b = np.asarray(n_a, dtype=np.int64).reshape(-1), np.asarray(n_b, dtype=np.int64).reshape(-1)
+    n = int(n_a.size)
+    if n < 1 or n_b.size != n or min(int(n_a.min()), int(n_b.min())) < 0:
+        raise ValueError("n_a and n_b are two lists of n >= 1 counts >= 0")
+    psi = _psi(max(int(n_a.max()) + 1, int(n_b.max()) + 1, n, int(k)))
+    return psi[int(k)] + psi[n] - math.fsum(np.concatenate([psi[n_a + 1], psi[n_b + 1]]).tolist()) / n
+
+
+def check_knn_options(width, k=4, norm="max", scale=None, m=None, n=None, norms=("max", "l2")):
+    """ValueError for a bad k (an integer in 1..16), norm (one of `norms`), scale (one finite value >= 0 per column) or too few
+    points (a query needs k neighbours: m > k within one set, n >= k in another) -> scale [width] or None."""
+    import nfisam_hip as _nh
+    if norm not in norms:
+        raise ValueError("norm must be %s, got %r" % (" or ".join(repr(v) for v in norms), norm))
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= _nh.KNN_MAX_K:
+        raise ValueError("k must be an integer in 1..%d, got %r" % (_nh.KNN_MAX_K, k))
+    if m is not None and m <= int(k):
+        raise ValueError("%d points have no %d-th neighbour among themselves (more than k points are needed)" % (m, int(k)))
+    if n is not None and n < int(k):
+        raise ValueError("%d points hold no %d-th neighbour (at least k points are needed)" % (n, int(k)))
+    if scale is not None:
+        scale = np.asarray(scale, dtype=np.float64).reshape(-1)
+        if scale.size != width or not np.all(np.isfinite(scale)) or np.any(scale < 0):
+            raise ValueError("scale: one finite value >= 0 per column of x (%d)" % width)
+    return scale
+
+
+def _knn_scale(Xt, used, flags, scale, width):
+    """scale [width]: the given one, or `mode_scale` of the columns `used` from nfisam_hip.sample_moments_t (0 elsewhere)."""
+    import nfisam_hip as _nh
+    if scale is not None:
+        return np.asarray(scale, dtype=np.float64).reshape(-1)
+    used = np.unique(used)
+    mean, res, cov = _nh.sample_moments_t(Xt, _nh.pack_moment_blocks(np.ones(used.size, dtype=np.int64)), used,
+                                          flags[used].astype(np.uint8) if flags[used].any() else None, None, checked=True)
+    scale = np.zeros(width)
+    scale[used] = mode_scale(cov.cpu().numpy(), res.cpu().numpy(), flags[used])
+    return scale
+
+
+def _log_scale_sums(scale, cols):
+    """sum_e log scale_e per block; -inf marks a block with a column without spread."""
+    with np.errstate(divide="ignore"):
+        return np.array([math.fsum(np.log(scale[c]).tolist()) if np.all(scale[c] > 0) else -np.inf for c in cols])
+
+
+def _knn_front(x, device):
+    if np.ndim(x) != 2:
+        raise ValueError("x must be [points, columns]")
+    if device is None:
+        device = x.device if hasattr(x, "is_cuda") and x.is_cuda else "cuda"
+    return device
+
+
+def knn_entropy_t(Xt, blocks, k=4, circular=None, scale=None, norm="max", checked=False) -> dict:
+    """`knn_entropy` on the COLUMN-major device matrix Xt [x_cols, n] (contiguous float32, used in place: what the tree walk
+    wrote); `blocks` name rows of Xt, `circular` and `scale` have one value per row.  `checked`: the caller has made every
+    check."""
+    import nfisam_hip as _nh
+    width, n = int(Xt.shape[0]), int(Xt.shape[1])
+    if checked:
+        cols = [np.asarray(b, dtype=np.int64) for b in blocks]
+        flags = np.zeros(width, dtype=bool) if circular is None else np.asarray(circular, dtype=bool).reshape(-1)
+    else:
+        cols = _column_blocks(blocks, width)
+        flags = _column_flags(circular, width)
+        scale = check_knn_options(width, k, norm, scale, m=n)
+    flat = np.concatenate(cols)
+    dims = np.array([c.size for c in cols])
+    scale = _knn_scale(Xt, flat, flags, scale, width)
+    wrap = flags[flat].astype(np.uint8)
+    raw = _nh.sample_knn_t(Xt, None, _nh.pack_knn_blocks(dims), flat, flat, int(k), norm, scale[flat], wrap if wrap.any() else None,
+                           exclude_self=True, checked=True)
+    n_used, log_sum = raw["n_used"].cpu().numpy(), raw["log_sum"].cpu().numpy()
+    zeros = (raw["dist"][:, int(k) - 1, :] == 0).sum(dim=1).cpu().numpy()
+    ls = _log_scale_sums(scale, cols)
+    with np.errstate(invalid="ignore"):
+        h = np.where(np.isfinite(ls), entropy_from_log_sum(log_sum, n_used, dims, int(k), norm, np.where(np.isfinite(ls), ls, 0.0)),
+                     -np.inf)
+    return dict(entropy=h, n_used=n_used, zeros=zeros, log_sum=log_sum, scale=scale, n=n, k=int(k), raw=raw)
+
+
+def knn_entropy(x, blocks, k=4, circular=None, scale=None, norm="max", device=None) -> dict:
+    """The differential entropy, in nats, of the sample set x [n, x_cols] (numpy or torch) restricted to each of `blocks` (lists
+    of at most 16 column indices), by the Kozachenko-Leonenko k-nearest-neighbour estimator -- the neighbour search of all
+    blocks in ONE device call (nfisam_hip.sample_knn_t: float32 points, float64 arithmetic), the formula
+    (`entropy_from_log_sum`) on the host.  Unlike 1/2 log det(2 pi e Sigma) it stays meaningful on a ring or on two modes.
+
+    circular [x_cols]: columns that are angles (differences wrapped into [-pi, pi)).  scale [x_cols]: the factor on a column's
+    differences; None: 1 / spread from `nfisam_hip.sample_moments_t` (`mode_scale`: standardised coordinates); the estimate is
+    brought back to the original units by - sum log scale.  A block with a column without spread (scale 0) has entropy -inf.
+    norm: "max" or "l2".  Queries whose k-th distance is 0 (duplicated points) are left out and counted in `zeros`; a block
+    without a usable query gives NaN.  The estimator is consistent, not exact: at n = 2000, k = 4 it is within some 0.05 nats.
+    -> dict: entropy [n_blocks], n_used [n_blocks], zeros [n_blocks], log_sum [n_blocks], scale [x_cols], n, k, raw (the
+    device tensors of nfisam_hip.sample_knn_t).  Every ValueError is raised before anything is launched.  No CPU path."""
+    import nfisam_hip as _nh
+    device = _knn_front(x, device)
+    n, width = int(x.shape[0]), int(x.shape[1])
+    cols = _column_blocks(blocks, width)
+    flags = _column_flags(circular, width)
+    scale = check_knn_options(width, k, norm, scale, m=n)
+    return knn_entropy_t(_nh._columns(x, device), cols, k, flags, scale, norm, checked=True)
+
+
+def _pair_blocks(pairs_of_blocks, width):
+    out = []
+    for p, pair in enumerate(pairs_of_blocks):
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+            raise ValueError("pair %d: a pair is (columns of A, columns of B)" % p)
+        a, b = _column_blocks(pair, width)
+        if a.size + b.size > 16:
+            raise ValueError("pair %d: %d columns; a joint block holds at most 16" % (p, a.size + b.size))
+        out.append((a, b))
+    if not out:
+        raise ValueError("no pairs")
+    return out
+
+
+def knn_mutual_information_t(Xt, pairs_of_blocks, k=4, circular=None, scale=None, norm="max", checked=False) -> dict:
+    """`knn_mutual_information` on the COLUMN-major device matrix Xt [x_cols, n]; see `knn_entropy_t`."""
+    import nfisam_hip as _nh
+    width, n = int(Xt.shape[0]), int(Xt.shape[1])
+    if checked:
+        pairs = [(np.asarray(a, dtype=np.int64), np.asarray(b, dtype=np.int64)) for a, b in pairs_of_blocks]
+        flags = np.zeros(width, dtype=bool) if circular is None else np.asarray(circular, dtype=bool).reshape(-1)
+    else:
+        pairs = _pair_blocks(pairs_of_blocks, width)
+        flags = _column_flags(circular, width)
+        scale = check_knn_options(width, k, norm, scale, m=n, norms=("max",))
+    joint = [np.concatenate(p) for p in pairs]
+    flat = np.concatenate(joint)
+    scale = _knn_scale(Xt, flat, flags, scale, width)
+    wrap = flags[flat].astype(np.uint8)
+    raw = _nh.sample_knn_t(Xt, None, _nh.pack_knn_blocks([c.size for c in joint]), flat, flat, int(k), "max", scale[flat],
+                           wrap if wrap.any() else None, exclude_self=True, checked=True)
+    eps = raw["dist"][:, int(k) - 1, :].contiguous()
+    sides = [c for p in pairs for c in p]                          # A and B of pair p: blocks 2 p and 2 p + 1, radius row p
+    sflat = np.concatenate(sides)
+    swrap = flags[sflat].astype(np.uint8)
+    count = _nh.sample_ball_count_t(Xt, None, _nh.pack_knn_blocks([c.size for c in sides], np.repeat(np.arange(len(pairs)), 2)),
+                                    sflat, sflat, eps, "max", scale[sflat], swrap if swrap.any() else None, exclude_self=True,
+                                    checked=True)
+    cnt = count.cpu().numpy()
+    mi = np.array([ksg_from_counts(cnt[2 * p], cnt[2 * p + 1], int(k)) for p in range(len(pairs))])
+    return dict(mi=mi, zeros=(eps == 0).sum(dim=1).cpu().numpy(), scale=scale, n=n, k=int(k), raw=dict(raw, eps=eps, count=count))
+
+
+def knn_mutual_information(x, pairs_of_blocks, k=4, circular=None, scale=None, norm="max", device=None) -> dict:
+    """The mutual information, in nats, between the column blocks A and B of each pair of `pairs_of_blocks` ([(columns of A,
+    columns of B)], at most 16 columns together) over the sample set x [n, x_cols], by estimator 1 of Kraskov, Stoegbauer and
+    Grassberger: eps_i is the k-th max-norm distance of point i in the joint block (nfisam_hip.sample_knn_t), n_a_i and n_b_i
+    count the other points strictly inside eps_i in A and in B (nfisam_hip.sample_ball_count_t), and `ksg_from_counts` forms
+    I = psi(k) + psi(n) - mean[psi(n_a + 1) + psi(n_b + 1)] on the host.  Only the max norm is accepted.  circular, scale: as
+    `knn_entropy` (the information does not depend on a column's scale; standardising keeps a wide column from deciding every
+    distance).  The estimate of independent blocks scatters about 0 and can be slightly negative.
+    -> dict: mi [n_pairs], zeros [n_pairs] (points whose eps is 0), scale, n, k, raw."""
+    import nfisam_hip as _nh
+    device = _knn_front(x, device)
+    n, width = int(x.shape[0]), int(x.shape[1])
+    pairs = _pair_blocks(pairs_of_blocks, width)
+    flags = _column_flags(circular, width)
+    scale = check_knn_options(width, k, norm, scale, m=n, norms=("max",))
+    return knn_mutual_information_t(_nh._columns(x, device), pairs, k, flags, scale, checked=True)
+
+
+def divergence_from_log_sums(log_sum_nu, log_sum_rho, used_nu, used_rho, d, m: int, n: int) -> np.ndarray:
+    """Wang-Kulkarni-Verdu on the host, per block: D = (d / m) (log_sum_nu - log_sum_rho) + log(n / (m - 1)); NaN unless every
+    one of the m queries was used on both sides."""
+    d = np.asarray(d, dtype=np.float64)
+    ok = (np.asarray(used_nu) == m) & (np.asarray(used_rho) == m)
+    val = (d / m) * (np.asarray(log_sum_nu, dtype=np.float64) - np.asarray(log_sum_rho, dtype=np.float64)) + math.log(n / (m - 1.0))
+    return np.where(ok, val, np.nan)
+
+
+def knn_divergence_t(Xt, Yt, blocks, k=4, circular=None, scale=None, norm="max", checked=False) -> dict:
+    """`knn_divergence` on the COLUMN-major device matrices Xt [x_cols, m], Yt [y_cols, n]; `blocks`: [(rows of Xt, rows of
+    Yt)]; circular and scale have one value per row of Xt."""
+    import nfisam_hip as _nh
+    width, m, n = int(Xt.shape[0]), int(Xt.shape[1]), int(Yt.shape[1])
+    if checked:
+        pairs = [(np.asarray(a, dtype=np.int64), np.asarray(b, dtype=np.int64)) for a, b in blocks]
+        flags = np.zeros(width, dtype=bool) if circular is None else np.asarray(circular, dtype=bool).reshape(-1)
+    else:
+        pairs = _divergence_blocks(blocks, width, int(Yt.shape[0]))
+        flags = _column_flags(circular, width)
+        scale = check_knn_options(width, k, norm, scale, m=m, n=n)
+    xc, yc = np.concatenate([p[0] for p in pairs]), np.concatenate([p[1] for p in pairs])
+    dims = np.array([p[0].size for p in pairs])
+    scale = _knn_scale(Xt, xc, flags, scale, width)
+    wrap = flags[xc].astype(np.uint8)
+    wrap = wrap if wrap.any() else None
+    table = _nh.pack_knn_blocks(dims)
+    rho = _nh.sample_knn_t(Xt, None, table, xc, xc, int(k), norm, scale[xc], wrap, exclude_self=True, checked=True)
+    nu = _nh.sample_knn_t(Xt, Yt, table, xc, yc, int(k), norm, scale[xc], wrap, exclude_self=False, checked=True)
+    used = [r["n_used"].cpu().numpy() for r in (nu, rho)]
+    div = divergence_from_log_sums(nu["log_sum"].cpu().numpy(), rho["log_sum"].cpu().numpy(), used[0], used[1], dims, m, n)
+    return dict(divergence=div, n_used=np.minimum(used[0], used[1]), scale=scale, m=m, n=n, k=int(k), raw=dict(rho=rho, nu=nu))
+
+
+def _divergence_blocks(blocks, x_width, y_width):
+    pairs = _block_pairs(blocks)
+    for b, (xc, yc) in enumerate(pairs):
+        if xc.size > 16:
+            raise ValueError("block %d: %d columns; a block holds at most 16" % (b, xc.size))
+        if xc.min() < 0 or xc.max() >= x_width or yc.min() < 0 or yc.max() >= y_width:
+            raise ValueError("block %d names a column outside its sample set" % b)
+    return pairs
+
+
+def knn_divergence(x, y, blocks, k=4, circular=None, scale=None, norm="max", device=None) -> dict:
+    """The Kullback-Leibler divergence D(P || Q), in nats, of the law P of the sample set x [m, x_cols] from the law Q of
+    y [n, y_cols], restricted to each of `blocks` (column lists that apply to both sets, or (xcols, ycols) pairs; at most 16
+    columns), by the k-nearest-neighbour estimator of Wang, Kulkarni and Verdu:
+        D = (d / m) (sum_i log nu_i - sum_i log rho_i) + log(n / (m - 1)),
+    rho_i the k-th distance of x_i within x (itself excluded), nu_i its k-th distance within y -- two calls of
+    nfisam_hip.sample_knn_t, `divergence_from_log_sums` on the host.  NaN unless every query was used on both sides (a
+    duplicated point, or a point of x that is also in y, has distance 0).  circular, scale ([x_cols]; None: standardised by
+    x's spreads), norm: as `knn_entropy`; the scale cancels in D.
+    -> dict: divergence [n_blocks], n_used [n_blocks], scale, m, n, k, raw."""
+    import nfisam_hip as _nh
+    device = _knn_front(x, device)
+    if np.ndim(y) != 2:
+        raise ValueError("y must be [points, columns]")
+    width = int(x.shape[1])
+    pairs = _divergence_blocks(blocks, width, int(y.shape[1]))
+    flags = _column_flags(circular, width)
+    scale = check_knn_options(width, k, norm, scale, m=int(x.shape[0]), n=int(y.shape[0]))
+    return knn_divergence_t(_nh._columns(x, device), _nh._columns(y, device), pairs, k, flags, scale, norm, checked=True)
 
 
 def sample_mean(samples, var_ordering):
