@@ -662,6 +662,54 @@ int nfisam_sample_ball_count(const float* Xt, int x_rows, int m, const float* Yt
                              const int32_t* ycols, int n_entries, const double* scale, const uint8_t* wrap, int norm,
                              const double* radius, int n_radius, int32_t* count, nfisam_stream_t stream);
 
+/* ---- marginal densities at query points: a Gaussian kernel density estimate in logs (sample_density.hip) -------------------
+ * The marginal posterior density itself, at points the caller chooses: what a marginal's curve on a grid, a map over the
+ * plane, the negative log predictive density at the ground truth (NLPD) and the level of the smallest highest-density
+ * region that holds it are formed from (utils/Statistics.py: density_bandwidth, sample_density_t, hpd_level).  The
+ * reference's figures copy the sample matrix to the host and run scipy.stats.gaussian_kde per coordinate on a 500-point
+ * grid (example/slam/ * /kde_plot_grid.py, traj_plot.py); nfisam_sample_modes evaluates such an estimate at its own converged
+ * starts only.  Qt[q_rows][m] holds the QUERIES and Xt[x_rows][n] the SAMPLES (COLUMN-major float32 device matrices, the
+ * layout of the tree walk's St; they may be the same matrix).  Entry e pairs row qcols[e] of Qt with row xcols[e] of Xt, as
+ * in nfisam_sample_knn; block b is the run of entries col_off .. col_off + d, 1 <= d <= NFISAM_DENSITY_MAX_D, with its own
+ * bandwidth matrix H given as the lower-triangular W with W H W' = I (W = inv(chol(H))).  Blocks may overlap and repeat
+ * entries: that is how bandwidth candidates share one launch.  For block b, query i and sample j
+ *     diff_c = (double)x_jc - (double)q_ic          (brought into [-pi, pi) by the wrap of sample_common.h where wrap[e] is set)
+ *     u_r    = sum_{c <= r} W_rc diff_c             (c ascending, fma)
+ *     e_ij   = -1/2 sum_r u_r^2 + log_w[j]          (log_w NULL: 0; a -inf entry -- a zero weight -- never contributes)
+ *     log_dens[b][i] = ((log_norm + M_i) + log(sum_j exp(e_ij - M_i))) - log W_tot,        M_i = max_j e_ij,
+ * W_tot = exp(log_w_sum) (n for NULL log_w), less w_i = exp(log_w[i]) under exclude_self; without exclude_self log W_tot is
+ * log_w_sum itself.  exclude_self != 0 skips j == i (it requires m == n): the leave-one-out density.
+ *   log_dens [n_blocks][m] double; dens [n_blocks][m] double (nullable) = exp(log_dens).
+ *   A query whose every e_ij is -inf (n = 1 under exclude_self; zero weights only) gets log_dens = -inf and dens = 0.  A query
+ *   with a NaN coordinate in the block gets NaN: the max keeps a NaN.  A query 1e4 bandwidths from every sample gets a finite
+ *   log_dens (about -5e7) and dens = 0: the shift by M_i is what makes the log usable in tails.
+ *   On a circular entry the NEAREST IMAGE alone is summed: a kernel wider than pi / 3 (1 / W_rr) puts more than 0.27 % of its
+ *   mass past the seam, and the Python binding refuses it.
+ *   blocks[n_blocks]: HOST copy of the table (validated here), blocks_dev: DEVICE copy (what the kernel reads); qcols, xcols
+ *   [n_entries] int32, wrap [n_entries] uint8 (nullable), log_w [n] double (nullable): DEVICE arrays.
+ * Float32 points in, float64 everywhere else.  A 256-thread group per (64 queries, block), one query per lane; the samples
+ * are walked twice in chunks of 128 staged in LDS, the four waves a quarter each: first the max, then the sum of exp(e - M)
+ * -- a thread's j ascending, then the four waves in order (sample_common.h); one float64 exp per pair, no float atomics.
+ * Two calls give the same bits; a block's rows are the same bits alone, repeated, or anywhere in a table; a query's result
+ * does not depend on m.
+ * NFISAM_ERR_ARG, before any launch: a NULL pointer (wrap, log_w and dens excepted); m, n, q_rows, x_rows, n_entries or
+ * n_blocks < 1; more than 65535 blocks or 64-wide tiles of queries; exclude_self with m != n; log_w with a log_w_sum that is
+ * not finite; a block of the host copy with d outside 1 .. 6, a log_norm or whiten entry that is not finite, or a diagonal
+ * entry <= 0.  The device copy of the table is not trusted: a block whose entries leave [0, n_entries), that names a row
+ * outside its matrix or whose d is outside 1 .. 6 yields NaN for its rows of log_dens and dens; nothing is read out of bounds
+ * and every other block is untouched.  The Python binding refuses such tables before upload.  (Additive: ABI 1600.) */
+#define NFISAM_DENSITY_MAX_D 6            /* a pair of SE(2) variables; a KDE means nothing wider at n ~ 2000 */
+typedef struct nfisam_density_block {
+    int32_t col_off;      /* first entry of the block in qcols / xcols / wrap */
+    int32_t d;            /* 1 .. NFISAM_DENSITY_MAX_D */
+    double  log_norm;     /* sum_r log W_rr - d/2 log(2 pi), supplied by the host */
+    double  whiten[21];   /* W: lower triangle, row-major packed, d(d+1)/2 used; W H W' = I for bandwidth matrix H */
+} nfisam_density_block;
+int nfisam_sample_density(const float* Qt, int q_rows, int m, const float* Xt, int x_rows, int n, int exclude_self,
+                          const nfisam_density_block* blocks, const nfisam_density_block* blocks_dev, int n_blocks,
+                          const int32_t* qcols, const int32_t* xcols, int n_entries, const uint8_t* wrap,
+                          const double* log_w, double log_w_sum, double* log_dens, double* dens, nfisam_stream_t stream);
+
 /* ---- training -------------------------------------------------------------------------- */
 /* Vector-Jacobian product of the L-layer flow (what torch autograd computes for
  * `loss.backward()` in slam/NFiSAM.py:474): kgrad[L*kparam_count] += d<gz,z>/dtheta + d<gl,logdet>/dtheta,

@@ -38,6 +38,7 @@ EXPORTS = [
     "nfisam_sample_propose", "nfisam_sample_accept", "nfisam_sample_accept_scratch_count",
     "nfisam_chain_record", "nfisam_chain_finish", "nfisam_chain_state_count",
     "nfisam_sample_knn", "nfisam_sample_ball_count",
+    "nfisam_sample_density",
 ]
 
 
@@ -2082,3 +2083,143 @@ def sample_ball_count_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, radius, norm="
                                               C.c_int(KNN_NORMS.get(norm, -1) if isinstance(norm, str) else int(norm)),
                                               _ptr(radius), n_radius, _ptr(count), _stream()), "nfisam_sample_ball_count")
     return count
+
+
+# ---- marginal densities at query points: a Gaussian kernel density estimate in logs (nfisam_sample_density) --------------------
+class DensityBlock(C.Structure):
+    _fields_ = [("col_off", C.c_int32), ("d", C.c_int32), ("log_norm", C.c_double), ("whiten", C.c_double * 21)]
+
+
+DENSITY_BLOCK_DTYPE = np.dtype([("col_off", np.int32), ("d", np.int32), ("log_norm", np.float64), ("whiten", np.float64, (21,))])
+assert DENSITY_BLOCK_DTYPE.itemsize == C.sizeof(DensityBlock) == 184
+DENSITY_MAX_D = 6                                # NFISAM_DENSITY_MAX_D
+DENSITY_MAX_WIDTH = np.pi / 3.0                  # widest kernel on a circular entry: the nearest image alone is summed
+_TRIL = [np.tril_indices(d) for d in range(DENSITY_MAX_D + 1)]
+
+
+def pack_density_blocks(dims, whiten, col_off=None) -> np.ndarray:
+    """The block table (numpy DENSITY_BLOCK_DTYPE) of blocks of `dims` entries; whiten[b]: block b's lower-triangular [d, d]
+    matrix W with W H W' = I for its bandwidth matrix H (inv(cholesky(H)); the upper triangle is not read); log_norm =
+    sum_r log W_rr - d/2 log(2 pi) is formed here.  col_off: each block's first entry (default: consecutive blocks) -- blocks
+    may share entries, which is how bandwidth candidates of one column set go into one launch."""
+    dims = np.asarray(dims, dtype=np.int64).reshape(-1)
+    if len(whiten) != dims.size:
+        raise ValueError("one whitening matrix per block (%d), got %d" % (dims.size, len(whiten)))
+    t = np.zeros(dims.size, dtype=DENSITY_BLOCK_DTYPE)
+    t["d"] = dims
+    t["col_off"] = np.cumsum(dims) - dims if col_off is None else np.asarray(col_off, dtype=np.int64).reshape(-1)
+    for b, (d, W) in enumerate(zip(dims, whiten)):
+        W = np.asarray(W, dtype=np.float64)
+        if not 1 <= d <= DENSITY_MAX_D or W.shape != (d, d):
+            raise ValueError("block %d: a whitening matrix is [d, d] with d in 1..%d, got d = %d and shape %s"
+                             % (b, DENSITY_MAX_D, d, W.shape))
+        t["whiten"][b, :d * (d + 1) // 2] = W[_TRIL[d]]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t["log_norm"][b] = np.log(np.diag(W)).sum() - 0.5 * d * np.log(2.0 * np.pi)
+    return t
+
+
+def check_density_blocks(blocks: np.ndarray, qcols, xcols, q_rows: int, x_rows: int, wrap=None) -> None:
+    """ValueError for tables the kernel must not see: no block or more than 65535, d outside 1..6, entries outside
+    [0, n_entries), a row outside [0, q_rows) / [0, x_rows), flags of another length, a log_norm or whitening entry that is
+    not finite, a diagonal entry <= 0, and a circular entry whose kernel width 1 / W_rr exceeds pi / 3."""
+    cols = {"qcols": (qcols, q_rows), "xcols": (xcols, x_rows)}
+    off, d = _check_table_layout(blocks, DENSITY_BLOCK_DTYPE, "DENSITY_BLOCK_DTYPE", cols, dict(wrap=wrap), DENSITY_MAX_D)
+    _check_rows(cols)
+    flags = None if wrap is None else np.asarray(wrap).astype(bool)
+    for b in range(blocks.size):
+        k = int(d[b])
+        tri = blocks["whiten"][b, :k * (k + 1) // 2]
+        diag = tri[np.cumsum(np.arange(1, k + 1)) - 1]
+        if not np.isfinite(blocks["log_norm"][b]) or not np.all(np.isfinite(tri)):
+            raise ValueError("block %d: log_norm and the whitening matrix must be finite" % b)
+        if not np.all(diag > 0):
+            raise ValueError("block %d: the whitening matrix needs a positive diagonal" % b)
+        if flags is not None:
+            wide = flags[off[b]:off[b] + k] & (1.0 / diag > DENSITY_MAX_WIDTH)
+            if np.any(wide):
+                r = int(np.argmax(wide))
+                raise ValueError("block %d: the kernel of circular entry %d is %.3g rad wide; beyond pi / 3 the nearest image "
+                                 "alone no longer carries its mass" % (b, r, 1.0 / diag[r]))
+
+
+def check_density_args(m: int, n: int, exclude_self=False) -> None:
+    """ValueError for the scalar arguments nfisam_sample_density refuses."""
+    if m < 1 or n < 1:
+        raise ValueError("queries and samples need at least one point each")
+    if m > 65535 * 64:
+        raise ValueError("%d queries are out of range of the grid (65535 tiles of 64)" % m)
+    if exclude_self and m != n:
+        raise ValueError("exclude_self needs the queries to be the samples (m = %d, n = %d)" % (m, n))
+
+
+def density_log_weights(weights, n: int, device, checked=False):
+    """Checked weights (None, numpy or a device tensor) -> (log_w float64 [n] on `device` with -inf for a zero weight, log of
+    their sum); (None, 0.0) without weights.  The logs are formed on the device."""
+    if not checked:
+        weights = _check_weights(weights, n)
+    if weights is None:
+        return None, 0.0
+    w = _f64(weights, device)
+    return torch.log(w), float(torch.log(w.sum()).item())
+
+
+def sample_density(q, x, blocks: np.ndarray, qcols, xcols, wrap=None, weights=None, exclude_self=False, want_density=False,
+                   device=None):
+    """The Gaussian kernel density estimate of the rows of x [n, x_cols] (tensor or numpy; None: q itself) at the rows of q
+    [m, q_cols], within every block of `blocks`, in logs: nfisam_sample_density, all blocks in one launch on the current
+    stream.  `blocks`: numpy DENSITY_BLOCK_DTYPE (`pack_density_blocks`: widths 1..6, a whitening matrix each); entry e of a
+    block pairs column qcols[e] of q with column xcols[e] of x; wrap [n_entries] marks angles (differences brought into
+    [-pi, pi), the nearest image alone); weights [n]: non-negative, None for all ones; exclude_self skips the pair j == i
+    (m == n): the leave-one-out density.
+    -> dict of device tensors: log_density [n_blocks, m] float64, density (the same shape with want_density, else None)."""
+    mats = dict(q=q) if x is None else dict(q=q, x=x)
+    device = _row_major_front("sample_density", device, **mats)
+    other = q if x is None else x
+    check_density_blocks(blocks, qcols, xcols, int(q.shape[1]), int(other.shape[1]), wrap)
+    check_density_args(int(q.shape[0]), int(other.shape[0]), exclude_self)
+    weights = _check_weights(weights, int(other.shape[0]))
+    Qt = _columns(q, device)
+    return sample_density_t(Qt, None if x is None else _columns(x, device), blocks, qcols, xcols, wrap, None, exclude_self,
+                            want_density, checked=True, weights=weights)
+
+
+def sample_density_t(Qt, Xt, blocks: np.ndarray, qcols, xcols, wrap=None, log_w=None, exclude_self=False, want_density=False,
+                     checked=False, weights=None, log_w_sum=None):
+    """`sample_density` on the COLUMN-major matrices Qt [q_rows, m], Xt [x_rows, n] (contiguous float32 device tensors, used
+    in place; Xt None: Qt): what the tree walk wrote.  log_w: None or a float64 [n] tensor on their device (-inf: a zero
+    weight) with log_w_sum the log of the weights' sum (None: formed on the device); or `weights`, from which both are formed
+    on the device (`density_log_weights`).  `checked` skips the table, argument and weight checks (the caller has made them)."""
+    q_rows, m = _column_major_front("Qt", Qt)
+    if Xt is None:
+        Xt = Qt
+    x_rows, n = _column_major_front("Xt", Xt)
+    if Qt.device != Xt.device:
+        raise ValueError("Qt and Xt must be on the same device")
+    device = Qt.device
+    if log_w is not None and weights is not None:
+        raise ValueError("give log_w or weights, not both")
+    if log_w is not None and (not torch.is_tensor(log_w) or log_w.dtype != torch.float64 or tuple(log_w.shape) != (n,) or
+                              log_w.device != device or not log_w.is_contiguous()):
+        raise ValueError("log_w must be a contiguous float64 [n] = [%d] tensor on %s" % (n, device))
+    if not checked:
+        check_density_blocks(blocks, qcols, xcols, q_rows, x_rows, wrap)
+        check_density_args(m, n, exclude_self)
+        weights = _check_weights(weights, n)
+    nb = int(blocks.shape[0])
+    blocks = np.ascontiguousarray(blocks)
+    qc, xc = np.asarray(qcols, dtype=np.int32), np.asarray(xcols, dtype=np.int32)
+    with torch.cuda.device(device):
+        dev = _upload_named(device, blocks=_table_bytes(blocks), qcols=qc, xcols=xc, wrap=_flags(wrap))
+        if weights is not None:
+            log_w, log_w_sum = density_log_weights(weights, n, device, checked=True)
+        elif log_w is not None and log_w_sum is None:
+            log_w_sum = float(torch.logsumexp(log_w, 0).item())
+        log_dens = torch.empty(nb, m, dtype=torch.float64, device=device)
+        dens = torch.empty(nb, m, dtype=torch.float64, device=device) if want_density else None
+        _check(lib().nfisam_sample_density(_ptr(Qt), q_rows, m, _ptr(Xt), x_rows, n, C.c_int(1 if exclude_self else 0),
+                                           blocks.ctypes.data_as(C.c_void_p), _ptr(dev["blocks"]), nb, _ptr(dev["qcols"]),
+                                           _ptr(dev["xcols"]), int(qc.size), _ptr(dev["wrap"]), _ptr(log_w),
+                                           C.c_double(0.0 if log_w_sum is None else log_w_sum), _ptr(log_dens), _ptr(dens),
+                                           _stream()), "nfisam_sample_density")
+    return dict(log_density=log_dens, density=dens)

@@ -1,6 +1,6 @@
 """slam.PosteriorEvaluation -- what a trained NFiSAM solver says about its posterior, not in the reference: densities
 (`posterior_log_pdf`, `joint_log_pdf`, `joint_score`), the solver grading itself (`posterior_diagnostics`, `map_estimate`,
-`posterior_ksd`, `posterior_mmd`), what the posterior holds (`posterior_summary`, `posterior_modes`, `posterior_information`), its samples moved
+`posterior_ksd`, `posterior_mmd`), what the posterior holds (`posterior_summary`, `posterior_modes`, `posterior_information`, `posterior_marginal_density`), its samples moved
 along the joint score (`posterior_refine`, `map_refine`), the joint density's curvature (`joint_hessian_product`,
 `map_newton`, `laplace_approximation`) and Metropolis chains that make the samples asymptotically exact (`posterior_mcmc`).
 
@@ -1102,4 +1102,181 @@ class PosteriorEvaluation:
             div = ST.knn_divergence_t(St, _nh._columns(Y, pts.device), [(cols_of(v), np.arange(rcol[v], rcol[v] + v.dim)) for v in graded],
                                       k, flags, scale, "max", checked=True)
             out["divergence"] = {v: float(div["divergence"][b]) for b, v in enumerate(graded)}
+        return out
+
+    # ---- the marginal density itself: curves, maps, the density at the truth -------------------------------------------
+    def posterior_marginal_density(self, samples=None, n: int = None, variables=None, pairs=None, weights=None, bandwidth="scott",
+                                   curves=None, maps=None, at=None, truth=None) -> dict:
+        """The marginal posterior density of variables at points the caller chooses: a Gaussian kernel density estimate of
+        the sample matrix the tree walk left on the device, evaluated there in logs (nfisam_sample_density: float32 points,
+        float64 arithmetic, a full bandwidth matrix per block, every block of a kind of query in one launch) -- what the
+        reference's figures compute on the host with scipy.stats.gaussian_kde per coordinate (example/slam/*/kde_plot_grid.py),
+        and what a calibration score needs: RMSE says where the estimate is, not whether its uncertainty is right.
+
+        samples, n, variables, pairs and weights are those of `posterior_summary` (a pair (a, b) is ONE joint block, here of
+        at most 6 columns).  bandwidth: "scott", "silverman", a positive factor (scipy's rules, utils.Statistics.
+        density_bandwidth) or "loo", the factor with the largest mean leave-one-out log density -- on a ring or on two
+        hypotheses Scott's rule is several times too wide.  At least one of:
+          curves=g      every coordinate of every variable alone on g points from its min - 3 h to its max + 3 h (a heading:
+                        [-pi, pi)) -> curves[v][c] = {x [g], density [g], h}: the reference's kde_plot_grid at kde_pts = g;
+          maps=(gx, gy) the xy block of every variable of two or more columns -> maps[v] = {x [gx], y [gy], density [gy, gx], H};
+          at            mapping variable or pair -> [q, dim] points, the whole block evaluated (heading included)
+                        -> log_density[key] [q];
+          truth         mapping variable -> [dim] -> nlpd[v] = -log density at the truth, hpd_level[v] (the credible level of
+                        the smallest highest-density region that holds it: utils.Statistics.hpd_level, one more launch with
+                        the samples as queries), mean_nlpd, coverage {0.5, 0.9, 0.95 -> the share of graded variables whose
+                        hpd_level is at most that level}.
+        One launch per kind of query.  -> dict with those keys (None for a kind not asked for), bandwidth (variable or pair ->
+        {factor, H}), n, ess.  It changes no solver state and draws only when `samples` is None.  Raises what
+        `posterior_summary` raises, and ValueError for a bad bandwidth, grid, point set or truth, or a pair wider than 6
+        columns -- before anything is launched; for a column without spread or a heading whose kernel would be wider than
+        pi / 3 -- before any density is evaluated."""
+        from utils import Statistics as ST
+        what = "posterior_marginal_density"
+        pts, importance, variables, pairs = self._summary_front(what, samples, n, variables, pairs, weights)
+        rows = pts.rows
+        for a, b in pairs:
+            if a.dim + b.dim > _nh.DENSITY_MAX_D:
+                raise ValueError("%s: the pair (%s, %s) is %d columns wide; a density block holds at most %d"
+                                 % (what, a.name, b.name, a.dim + b.dim, _nh.DENSITY_MAX_D))
+        for v in variables:
+            if v.dim > _nh.DENSITY_MAX_D:
+                raise ValueError("%s: %s is %d columns wide; a density block holds at most %d" % (what, v.name, v.dim, _nh.DENSITY_MAX_D))
+        if curves is None and maps is None and at is None and truth is None:
+            raise ValueError("%s: ask for at least one of curves, maps, at or truth" % what)
+        try:
+            ST.check_density_options(bandwidth, rows)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (what, e)) from None
+        if curves is not None and (isinstance(curves, bool) or int(curves) != curves or int(curves) < 2):
+            raise ValueError("%s: curves is the number of grid points, an integer >= 2, got %r" % (what, curves))
+        map_vars = []
+        if maps is not None:
+            if np.ndim(maps) != 1 or len(maps) != 2 or any(isinstance(g, bool) or int(g) != g or int(g) < 2 for g in maps):
+                raise ValueError("%s: maps is (gx, gy), two integers >= 2, got %r" % (what, maps))
+            map_vars = [v for v in variables if v.dim >= 2]
+            if not map_vars:
+                raise ValueError("%s: no variable has an xy block to map" % what)
+        at_keys, at_pts = [], []
+        if at is not None:
+            for key, p in at.items():
+                blk = tuple(key) if isinstance(key, (tuple, list)) else (key,)
+                if (len(blk) == 2 and blk not in pairs) or (len(blk) == 1 and blk[0] not in variables) or len(blk) > 2:
+                    raise ValueError("%s: at names %s, which is not among the variables and pairs of this call"
+                                     % (what, "(%s)" % ", ".join(getattr(v, "name", str(v)) for v in blk)))
+                p = np.asarray(p.detach().cpu().numpy() if torch.is_tensor(p) else p, dtype=np.float64)
+                d = sum(v.dim for v in blk)
+                if p.ndim != 2 or p.shape[1] != d or p.shape[0] < 1:
+                    raise ValueError("%s: at[%s] must be [q >= 1, %d], got %s" % (what, "/".join(v.name for v in blk), d, p.shape))
+                at_keys.append(blk), at_pts.append(p)
+            if not at_keys:
+                raise ValueError("%s: at is empty" % what)
+        graded = []
+        if truth is not None:
+            graded = [v for v in variables if v in truth]
+            if not graded:
+                raise ValueError("%s: truth holds none of the variables" % what)
+            for v in graded:
+                if np.ndim(truth[v]) != 1 or len(truth[v]) != v.dim or not np.all(np.isfinite(np.asarray(truth[v], dtype=np.float64))):
+                    raise ValueError("%s: truth of %s must be [%d] finite values, got shape %s" % (what, v.name, v.dim, np.shape(truth[v])))
+        w_host = self._summary_weights(what, weights, importance, rows)
+        table, cols, circ = self._summary_table(variables, pairs, pts.pcol)
+        w_dev, ess = self._weights(what, pts, importance, w_host)
+        flags = np.zeros(pts.total_dim, dtype=bool)
+        flags[cols] = circ != 0
+
+        # every block whose bandwidth is needed: variables and pairs, then the curves' coordinates, then the maps' xy blocks
+        blocks, at_col = [], 0
+        for blk in table:
+            d = sum(v.dim for v in blk)
+            blocks.append(cols[at_col:at_col + d].astype(np.int64))
+            at_col += d
+        index = {blk: b for b, blk in enumerate(table)}
+        curve_of, map_of = {}, {}
+        if curves is not None:
+            for v in variables:
+                for c in range(v.dim):
+                    curve_of[(v, c)] = len(blocks)
+                    blocks.append(np.array([pts.pcol[v] + c], dtype=np.int64))
+        for v in map_vars:
+            map_of[v] = len(blocks)
+            blocks.append(np.array([pts.pcol[v], pts.pcol[v] + 1], dtype=np.int64))
+        St = pts.St
+        device = St.device
+        bw = ST.density_bandwidths_t(St, blocks, flags, w_dev, bandwidth)
+        log_w, log_w_sum = _nh.density_log_weights(w_dev, rows, device, checked=True)
+
+        def launch(Qt, which, qcols, want_density=False):
+            """One launch: blocks `which` (indices into `blocks`) against the queries Qt, block k reading rows qcols[k] of it."""
+            xc = np.concatenate([blocks[b] for b in which])
+            wrap = flags[xc].astype(np.uint8)
+            wrap = wrap if wrap.any() else None
+            tab = _nh.pack_density_blocks([blocks[b].size for b in which], [bw["W"][b] for b in which])
+            qc = np.concatenate(qcols)
+            _nh.check_density_blocks(tab, qc, xc, int(Qt.shape[0]), pts.total_dim, wrap)
+            return _nh.sample_density_t(Qt, St, tab, qc, xc, wrap, log_w, False, want_density, checked=True, log_w_sum=log_w_sum)
+
+        out = dict(curves=None, maps=None, log_density=None, n=rows, ess=ess,
+                   bandwidth={(blk if len(blk) == 2 else blk[0]): dict(factor=float(bw["factor"][b]), H=bw["H"][b].copy())
+                              for blk, b in index.items()})
+        if curves is not None or map_vars:
+            used = np.unique(np.concatenate([blocks[b] for b in list(curve_of.values()) + list(map_of.values())]))
+            lo_d, hi_d = St[used].min(dim=1).values.double().cpu().numpy(), St[used].max(dim=1).values.double().cpu().numpy()
+            lo, hi = dict(zip(used.tolist(), lo_d)), dict(zip(used.tolist(), hi_d))
+
+        def axis(col, h, g):
+            if flags[col]:
+                return np.linspace(-np.pi, np.pi, g, endpoint=False).astype(np.float32)
+            return np.linspace(lo[col] - 3.0 * h, hi[col] + 3.0 * h, g).astype(np.float32)
+
+        if curves is not None:
+            g = int(curves)
+            keys = list(curve_of)
+            grid = np.stack([axis(int(blocks[curve_of[k]][0]), float(np.sqrt(bw["H"][curve_of[k]][0, 0])), g) for k in keys])
+            res = launch(torch.from_numpy(grid).to(device), [curve_of[k] for k in keys], [np.array([r]) for r in range(len(keys))], True)
+            dens = res["density"].cpu().numpy()
+            out["curves"] = {v: [None] * v.dim for v in variables}
+            for r, (v, c) in enumerate(keys):
+                out["curves"][v][c] = dict(x=grid[r].astype(np.float64), density=dens[r].copy(),
+                                           h=float(np.sqrt(bw["H"][curve_of[(v, c)]][0, 0])))
+        if map_vars:
+            gx, gy = int(maps[0]), int(maps[1])
+            grid, axes = np.zeros((2 * len(map_vars), gx * gy), dtype=np.float32), {}
+            for k, v in enumerate(map_vars):
+                H = bw["H"][map_of[v]]
+                ax = axis(pts.pcol[v], float(np.sqrt(H[0, 0])), gx)
+                ay = axis(pts.pcol[v] + 1, float(np.sqrt(H[1, 1])), gy)
+                axes[v] = (ax, ay)
+                grid[2 * k], grid[2 * k + 1] = np.tile(ax, gy), np.repeat(ay, gx)
+            res = launch(torch.from_numpy(grid).to(device), [map_of[v] for v in map_vars],
+                         [np.array([2 * k, 2 * k + 1]) for k in range(len(map_vars))], True)
+            dens = res["density"].cpu().numpy()
+            out["maps"] = {v: dict(x=axes[v][0].astype(np.float64), y=axes[v][1].astype(np.float64), density=dens[k].reshape(gy, gx).copy(),
+                                   H=bw["H"][map_of[v]].copy()) for k, v in enumerate(map_vars)}
+        if at_keys:
+            q = max(p.shape[0] for p in at_pts)                            # a launch has one m: shorter sets repeat their first point
+            host = np.concatenate([np.vstack([p, np.repeat(p[:1], q - p.shape[0], axis=0)]).T for p in at_pts]).astype(np.float32)
+            qcols, r = [], 0
+            for p in at_pts:
+                qcols.append(np.arange(r, r + p.shape[1]))
+                r += p.shape[1]
+            res = launch(torch.from_numpy(np.ascontiguousarray(host)).to(device), [index[blk] for blk in at_keys], qcols)
+            ld = res["log_density"].cpu().numpy()
+            out["log_density"] = {(blk if len(blk) == 2 else blk[0]): ld[k, :p.shape[0]].copy()
+                                  for k, (blk, p) in enumerate(zip(at_keys, at_pts))}
+        if graded:
+            which = [index[(v,)] for v in graded]
+            host = np.concatenate([np.asarray(truth[v], dtype=np.float32) for v in graded]).reshape(-1, 1)
+            qcols, r = [], 0
+            for v in graded:
+                qcols.append(np.arange(r, r + v.dim))
+                r += v.dim
+            at_truth = launch(torch.from_numpy(host).to(device), which, qcols)["log_density"][:, 0]
+            own = launch(St, which, [blocks[b] for b in which])["log_density"]
+            level = torch.stack([ST.hpd_level(own[k], at_truth[k], w_dev) for k in range(len(graded))]).cpu().numpy()
+            nl = (-at_truth).cpu().numpy()
+            out["nlpd"] = {v: float(nl[k]) for k, v in enumerate(graded)}
+            out["hpd_level"] = {v: float(level[k]) for k, v in enumerate(graded)}
+            out["mean_nlpd"] = float(np.mean(nl))
+            out["coverage"] = {lev: float(np.mean(level <= lev)) for lev in (0.5, 0.9, 0.95)}
         return out

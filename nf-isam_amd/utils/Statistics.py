@@ -635,6 +635,230 @@ def knn_divergence(x, y, blocks, k=4, circular=None, scale=None, norm="max", dev
     return knn_divergence_t(_nh._columns(x, device), _nh._columns(y, device), pairs, k, flags, scale, norm, checked=True)
 
 
+# ---- the marginal density itself, where the caller asks: a Gaussian KDE in logs on the device (nfisam_sample_density) ----------
+DENSITY_RULES = ("scott", "silverman", "loo")
+DENSITY_LOO_POWERS = tuple(range(-10, 3))        # leave-one-out candidates: the Scott factor times 2^(k / 2)
+DENSITY_CIRCULAR_VARIANCE_CAP = math.pi ** 2 / 3.0   # the variance of a uniform heading
+
+
+def density_factor(n_eff: float, d: int, rule) -> float:
+    """The bandwidth factor of scipy.stats.gaussian_kde: n_eff^(-1 / (d + 4)) for "scott", (n_eff (d + 2) / 4)^(-1 / (d + 4))
+    for "silverman", or `rule` itself, a positive float."""
+    if isinstance(rule, str):
+        if rule == "scott":
+            return float(n_eff) ** (-1.0 / (d + 4.0))
+        if rule == "silverman":
+            return (float(n_eff) * (d + 2.0) / 4.0) ** (-1.0 / (d + 4.0))
+        raise ValueError("bandwidth is 'scott', 'silverman', 'loo' or a positive factor, got %r" % (rule,))
+    if isinstance(rule, bool) or not np.isscalar(rule) or not np.isfinite(rule) or not rule > 0:
+        raise ValueError("bandwidth is 'scott', 'silverman', 'loo' or a positive factor, got %r" % (rule,))
+    return float(rule)
+
+
+def density_bandwidth(cov, n_eff: float, d: int, rule, circular=None) -> np.ndarray:
+    """The bandwidth matrix H [d, d] of a Gaussian KDE, as scipy.stats.gaussian_kde forms it: `cov` -- the POPULATION covariance
+    `nfisam_hip.sample_moments_t` returns, a heading's deviations wrapped -- made unbiased, cov / (1 - 1 / n_eff), times
+    factor^2 (`density_factor`).  circular [d]: a circular column's variance is capped at pi^2 / 3, the variance of a uniform
+    heading, before the factor (its row and column are scaled down together), so that a ring's heading keeps a kernel the
+    nearest image can carry.  ValueError for a column without spread, a matrix that is not positive definite, n_eff <= 1."""
+    cov = np.array(cov, dtype=np.float64).reshape(d, d)
+    factor = density_factor(n_eff, d, rule)
+    if not float(n_eff) > 1.0:
+        raise ValueError("a bandwidth needs an effective sample size above 1, got %r" % (n_eff,))
+    var = np.diag(cov)
+    if not np.all(np.isfinite(cov)) or not np.all(var > 0):
+        raise ValueError("a column has no spread (variances %s): it has no density" % (var,))
+    if circular is not None:
+        circular = np.asarray(circular, dtype=bool).reshape(-1)
+        shrink = np.where(circular & (var > DENSITY_CIRCULAR_VARIANCE_CAP), np.sqrt(DENSITY_CIRCULAR_VARIANCE_CAP / var), 1.0)
+        cov = cov * shrink[:, None] * shrink[None, :]
+    return cov / (1.0 - 1.0 / float(n_eff)) * factor ** 2
+
+
+def density_whiten(H) -> np.ndarray:
+    """W = inv(cholesky(H)): lower triangular with W H W' = I.  ValueError when H is not positive definite."""
+    H = np.asarray(H, dtype=np.float64)
+    try:
+        L = np.linalg.cholesky(H)
+    except np.linalg.LinAlgError:
+        raise ValueError("the bandwidth matrix is not positive definite (columns without joint spread)") from None
+    W = np.linalg.solve(L, np.eye(L.shape[0]))
+    return np.tril(W)
+
+
+def hpd_level(log_dens_samples, log_dens_point, weights=None):
+    """The credible level of the smallest highest-density region that contains a point: the (weighted) share of the samples
+    whose own KDE log density is at least the point's.  Near 0: the point sits on the peak; near 1: in the tails; over many
+    calibrated posteriors it is uniform.  log_dens_samples [n], log_dens_point: a scalar or [q]; weights [n] or None.  Torch
+    tensors are reduced where they lie (-> a tensor of log_dens_point's shape), anything else with numpy."""
+    if hasattr(log_dens_samples, "is_cuda"):
+        import torch
+        s = log_dens_samples.double().reshape(-1)
+        p = torch.as_tensor(log_dens_point, dtype=torch.float64, device=s.device)
+        w = torch.ones_like(s) if weights is None else torch.as_tensor(weights, dtype=torch.float64, device=s.device).reshape(-1)
+        inside = (s[None, :] >= p.reshape(-1, 1)).to(torch.float64)
+        return ((inside * w[None, :]).sum(dim=1) / w.sum()).reshape(p.shape)
+    s = np.asarray(log_dens_samples, dtype=np.float64).reshape(-1)
+    p = np.asarray(log_dens_point, dtype=np.float64)
+    w = np.ones_like(s) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+    inside = (s[None, :] >= p.reshape(-1, 1)).astype(np.float64)
+    out = ((inside * w[None, :]).sum(axis=1) / w.sum()).reshape(p.shape)
+    return float(out) if out.ndim == 0 else out
+
+
+def check_density_options(bandwidth, n: int, m: int = None, exclude_self=False):
+    """ValueError for a bad bandwidth rule or too few points (two at least: the unbiased covariance; leave-one-out)."""
+    if isinstance(bandwidth, str):
+        if bandwidth not in DENSITY_RULES:
+            raise ValueError("bandwidth is 'scott', 'silverman', 'loo' or a positive factor, got %r" % (bandwidth,))
+    else:
+        density_factor(2.0, 1, bandwidth)
+    if n < 2:
+        raise ValueError("a density estimate needs at least two samples, got %d" % n)
+    if exclude_self and m is not None and m != n:
+        raise ValueError("exclude_self needs the queries to be the samples (m = %d, n = %d)" % (m, n))
+
+
+def _density_blocks(blocks, x_width, q_width):
+    import nfisam_hip as _nh
+    pairs = _block_pairs(blocks)
+    for b, (xc, qc) in enumerate(pairs):
+        if xc.size > _nh.DENSITY_MAX_D:
+            raise ValueError("block %d: %d columns; a density block holds at most %d" % (b, xc.size, _nh.DENSITY_MAX_D))
+        if xc.min() < 0 or xc.max() >= x_width or qc.min() < 0 or qc.max() >= q_width:
+            raise ValueError("block %d names a column outside its matrix" % b)
+    return pairs
+
+
+def _loo_mean(log_dens, weights):
+    """The (weighted) mean over the samples of every row of log_dens [rows, n], on the device; a zero weight's row entry is
+    not read."""
+    if weights is None:
+        return log_dens.mean(dim=1)
+    import torch
+    w = torch.as_tensor(weights, dtype=torch.float64, device=log_dens.device)
+    return torch.where(w[None, :] > 0, log_dens * w[None, :], torch.zeros_like(log_dens)).sum(dim=1) / w.sum()
+
+
+def density_bandwidths_t(Xt, cols, flags, weights=None, bandwidth="scott") -> dict:
+    """The bandwidth of every block `cols` (lists of rows of the COLUMN-major device matrix Xt [x_cols, n]; flags: which rows
+    are angles): the blocks' covariances from ONE nfisam_hip.sample_moments_t call, `density_bandwidth` on the host.
+    "loo": every (block, candidate) pair -- the Scott factor times 2^(k / 2), k = -10 .. 2 -- is one block of ONE
+    nfisam_hip.sample_density_t launch with the samples as queries and exclude_self; the largest (weighted) mean
+    leave-one-out log density picks the factor, the lowest candidate on ties.  A candidate too wide for a heading (pi / 3) is
+    left out.  Arguments are taken as checked.
+    -> dict: H (list of [d, d]), W (their whitening matrices), factor [n_blocks], n_eff, loo (None, or per block {factors,
+    scores})."""
+    import nfisam_hip as _nh
+    n = int(Xt.shape[1])
+    n_eff = effective_sample_size(weights, n)
+    flat = np.concatenate(cols)
+    dims = np.array([c.size for c in cols])
+    wrap = flags[flat].astype(np.uint8)
+    table = _nh.pack_moment_blocks(dims)
+    _, _, cov = _nh.sample_moments_t(Xt, table, flat, wrap if wrap.any() else None, weights, checked=True)
+    cov = cov.cpu().numpy()
+    covs = [cov[int(r["cov_off"]):int(r["cov_off"]) + int(r["d"]) ** 2].reshape(int(r["d"]), int(r["d"])) for r in table]
+    circ = [flags[c] for c in cols]
+    loo = None
+    if bandwidth == "loo":
+        cand, owner, Ws, offs = [], [], [], []
+        for b, (c, d) in enumerate(zip(cols, dims)):
+            scott = density_factor(n_eff, int(d), "scott")
+            for k in DENSITY_LOO_POWERS:
+                f = scott * 2.0 ** (k / 2.0)
+                W = density_whiten(density_bandwidth(covs[b], n_eff, int(d), f, circ[b]))
+                if np.any(circ[b] & (1.0 / np.diag(W) > _nh.DENSITY_MAX_WIDTH)):
+                    continue
+                cand.append(f), owner.append(b), Ws.append(W), offs.append(int(table["col_off"][b]))
+            if b not in owner:
+                raise ValueError("block %d: every leave-one-out candidate is too wide for its heading" % b)
+        owner = np.asarray(owner)
+        blocks = _nh.pack_density_blocks(dims[owner], Ws, offs)
+        wr = wrap if wrap.any() else None
+        _nh.check_density_blocks(blocks, flat, flat, int(Xt.shape[0]), int(Xt.shape[0]), wr)
+        res = _nh.sample_density_t(Xt, None, blocks, flat, flat, wr, None, True, False, checked=True, weights=weights)
+        scores = _loo_mean(res["log_density"], weights).cpu().numpy()
+        cand = np.asarray(cand)
+        factor, loo = np.zeros(len(cols)), []
+        for b in range(len(cols)):
+            mine = np.flatnonzero(owner == b)
+            s = np.where(np.isnan(scores[mine]), -np.inf, scores[mine])
+            factor[b] = cand[mine][int(np.argmax(s))]                    # (the first maximum: the lowest candidate on ties)
+            loo.append(dict(factors=cand[mine].copy(), scores=scores[mine].copy()))
+    else:
+        factor = np.array([density_factor(n_eff, int(d), bandwidth) for d in dims])
+    H = [density_bandwidth(covs[b], n_eff, int(dims[b]), float(factor[b]), circ[b]) for b in range(len(cols))]
+    return dict(H=H, W=[density_whiten(h) for h in H], factor=factor, n_eff=n_eff, loo=loo)
+
+
+def sample_density_t(Xt, Qt, blocks, circular=None, weights=None, bandwidth="scott", exclude_self=False, want_density=False,
+                     checked=False) -> dict:
+    """`sample_density` on the COLUMN-major device matrices Xt [x_cols, n] (the samples) and Qt [q_cols, m] (the queries; None:
+    the samples themselves) -- contiguous float32, used in place: what the tree walk wrote.  `blocks`: lists of rows (of both
+    matrices) or (rows of Xt, rows of Qt) pairs; circular has one flag per row of Xt.  `checked`: the caller has made every
+    check.  The results stay on the device."""
+    import nfisam_hip as _nh
+    width, n = int(Xt.shape[0]), int(Xt.shape[1])
+    q_width, m = (width, n) if Qt is None else (int(Qt.shape[0]), int(Qt.shape[1]))
+    if checked:
+        pairs = [(np.asarray(a, dtype=np.int64), np.asarray(b, dtype=np.int64)) for a, b in _block_pairs(blocks)]
+        flags = np.zeros(width, dtype=bool) if circular is None else np.asarray(circular, dtype=bool).reshape(-1)
+    else:
+        pairs = _density_blocks(blocks, width, q_width)
+        flags = _column_flags(circular, width)
+        check_density_options(bandwidth, n, m, exclude_self)
+        weights = _nh._check_weights(weights, n)
+    cols = [p[0] for p in pairs]
+    bw = density_bandwidths_t(Xt, cols, flags, weights, bandwidth)
+    xc, qc = np.concatenate(cols), np.concatenate([p[1] for p in pairs])
+    wrap = flags[xc].astype(np.uint8)
+    wrap = wrap if wrap.any() else None
+    table = _nh.pack_density_blocks([c.size for c in cols], bw["W"])
+    _nh.check_density_blocks(table, qc, xc, q_width, width, wrap)
+    res = _nh.sample_density_t(Xt if Qt is None else Qt, Xt, table, qc, xc, wrap, None, exclude_self, want_density, checked=True,
+                               weights=weights)
+    out = dict(log_density=res["log_density"], factor=bw["factor"], H=bw["H"], n_eff=bw["n_eff"])
+    if want_density:
+        out["density"] = res["density"]
+    if bw["loo"] is not None:
+        out["loo"] = bw["loo"]
+    return out
+
+
+def sample_density(x, queries, blocks, circular=None, weights=None, bandwidth="scott", exclude_self=False, want_density=False,
+                   device=None) -> dict:
+    """The Gaussian kernel density estimate of the sample set x [n, x_cols] (numpy or torch) at the rows of `queries`
+    [m, q_cols] (None: the samples themselves), restricted to each of `blocks` (lists of at most 6 column indices that apply to
+    both, or (columns of x, columns of queries) pairs), in logs -- what scipy.stats.gaussian_kde(x[:, block].T).logpdf
+    returns, for all blocks in ONE device call (nfisam_hip.sample_density_t: float32 points, float64 arithmetic, a full
+    bandwidth matrix per block).
+
+    circular [x_cols]: columns that are angles (differences wrapped into [-pi, pi); the nearest image alone is summed, so a
+    heading's kernel may be at most pi / 3 wide).  weights [n]: non-negative, None for all ones.  bandwidth: "scott",
+    "silverman" or a positive factor -- scipy's rules on the unbiased (weighted) covariance (`density_bandwidth`) -- or "loo":
+    the factor among the Scott factor times 2^(k / 2), k = -10 .. 2, with the largest mean leave-one-out log density (one more
+    launch).  On a ring or on two hypotheses Scott's rule is several times too wide; "loo" is not.  exclude_self: the
+    leave-one-out density (queries None).
+    -> dict: log_density [n_blocks, m] (a float64 device tensor), density (the same, with want_density), factor [n_blocks],
+    H (per block [d, d]), n_eff, and with "loo": loo (per block {factors, scores}).  Every ValueError -- a bad block, rule
+    or weight, fewer than two samples, a column without spread -- is raised before the density launch.  No CPU path."""
+    import nfisam_hip as _nh
+    device = _knn_front(x, device)
+    if queries is not None and np.ndim(queries) != 2:
+        raise ValueError("queries must be [points, columns]")
+    n, width = int(x.shape[0]), int(x.shape[1])
+    m, q_width = (n, width) if queries is None else (int(queries.shape[0]), int(queries.shape[1]))
+    pairs = _density_blocks(blocks, width, q_width)
+    flags = _column_flags(circular, width)
+    check_density_options(bandwidth, n, m, exclude_self)
+    if m < 1:
+        raise ValueError("no queries")
+    weights = _nh._check_weights(weights, n)
+    return sample_density_t(_nh._columns(x, device), None if queries is None else _nh._columns(queries, device), pairs, flags,
+                            weights, bandwidth, exclude_self, want_density, checked=True)
+
+
 def sample_mean(samples, var_ordering):
     """The reference's `sample_mean` (src/utils/Statistics.py:151-171) on the device: the mean of every column of samples
     [n, sum of the variables' dims], circular for the columns the variables flag as angles, arithmetic for the others
