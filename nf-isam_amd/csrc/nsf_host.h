@@ -17,6 +17,7 @@
 
 #include "../../include/nfisam_hip.h"
 #include "nsf_device.h"
+#include "nsf_knobs.h"
 #include "nsf_split.h"
 #include "nsf_units.h"
 
@@ -165,18 +166,10 @@ static int set_lds(KernelT kernel, size_t bytes) {
     return NFISAM_OK;
 }
 
-// ---- launch-shape knobs (environment variables are for A/B measurements and tests) -------------------------------
+// ---- launch-shape knobs (environment variables are for A/B measurements and tests: nsf_knobs.h) -------------------
 // The weight-gradient GEMMs run on the matrix cores when H == 8 (ga2 | ga1 share one 16-row MFMA operand tile); other
-// hidden widths, and NFISAM_GRAD=butterfly, take the cross-lane butterfly reduction of round 1.
-static inline bool use_mfma_grad(int H) {
-    const char* e = getenv("NFISAM_GRAD");
-    return H == 8 && !(e != nullptr && strcmp(e, "butterfly") == 0);
-}
-
-static inline int weights_mode() {   // 0: scalar-cache path, 1: LDS copy, -1: automatic
-    const char* e = getenv("NFISAM_WEIGHTS");
-    return (e == nullptr) ? -1 : (strcmp(e, "lds") == 0 ? 1 : (strcmp(e, "scalar") == 0 ? 0 : -1));
-}
+// hidden widths take the cross-lane butterfly reduction of round 1.
+constexpr bool use_mfma_grad(int H) { return H == 8; }
 
 // Training kernel family, chosen per launch: "split" (two lanes per particle, 32-particle tiles) while the
 // launch leaves SIMDs idle -- it halves the instructions per wave and doubles the waves -- and "wide" (one
@@ -192,11 +185,8 @@ static inline bool dim_major_enabled();
 //  with ONE layer's panels resident; `pair_h4` = "a hidden width other than 8 whose pair kernel takes this launch")
 static inline int train_tile(int n_cliques, int max_n, int max_D, int H, bool nll_L1 = false, bool pair_h4 = false) {
     if (H != 8 && !((H == 4 || H == 16) && pair_h4 && !nll_L1)) return TILE;
-    const char* e = getenv("NFISAM_TRAIN");            // read per call: tests switch families in-process
-    if (e != nullptr) {
-        if (strcmp(e, "wide") == 0) return TILE;
-        if (strcmp(e, "split") == 0) return TILE2;
-    }
+    if (knob::train("wide")) return TILE;              // read per call: tests switch families in-process
+    if (knob::train("split")) return TILE2;
     if (nll_L1 && dim_major_enabled() && max_D <= 96) return TILE;
     const long waves = (long)((max_n + TILE2 - 1) / TILE2) * (long)max_D * (long)n_cliques;
     return waves <= 1280 ? TILE2 : TILE;
@@ -204,10 +194,7 @@ static inline int train_tile(int n_cliques, int max_n, int max_D, int H, bool nl
 
 // Throughput launches (wide family, L == 1) go to nsf_train1_kernel (dim-major blocks) unless NFISAM_DIM_MAJOR=0
 // (A/B against nsf_train_kernel's tile-major blocks).
-static inline bool dim_major_enabled() {
-    const char* e = getenv("NFISAM_DIM_MAJOR");
-    return !(e != nullptr && e[0] == '0');
-}
+static inline bool dim_major_enabled() { return knob::dim_major(); }
 // LDS rows (of XS floats) of one wave of the dim-major kernel: particle tile [max_D] + staging [16] + h1 [H] + (D > 16) the
 // rows 16.. of dW0 summed over the wave's tiles
 __host__ __device__ static inline int train1_wave_rows(int max_D, int H) {
@@ -224,11 +211,7 @@ constexpr int PANEL_BASE = 4;      // LDS words in front of the conditioner pane
 // NFISAM_BIG_W = 1..8 for experiments.  Eight (half the gradient copies for the fused Adam update to read back, half the
 // staging work per thread) measured 13 % SLOWER on a single Plaza clique: two waves per SIMD on 60 CUs instead of one
 // wave per SIMD on 120 -- in the latency regime a wave wants its SIMD to itself.
-static inline int dim_major_waves() {
-    const char* e = getenv("NFISAM_BIG_W");
-    const int v = e != nullptr ? atoi(e) : 4;
-    return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 4;
-}
+static inline int dim_major_waves() { return knob::int_in_set(knob::big_w(), 1, 2, 4, 8, 4); }
 // ---- two lanes per particle on the dim-major kernel (round 6, nsf_half.h) --------------------------------------------------
 // The family for launches that leave most SIMDs idle -- ONE clique, i.e. every fit of a real NF-iSAM run: a wave covers 32
 // particles with a shorter per-lane program (stamped arithmetic of a unit 9.3 k -> 7.1 k cycles), twice the waves, blocks of
@@ -237,13 +220,9 @@ static inline int dim_major_waves() {
 // each (<= 256) and a (clique, dim) group keeps to EIGHT blocks (n <= 1024): the exchange between a group's blocks is bound
 // by the instructions a thread spends per gradient copy, and with sixteen copies it gives back what the shorter unit gained
 // (one clique, D = 15, us per iteration, 64-particle family / this one: n = 500 .. 1024: 7.4 / 6.25; n = 1500 .. 2048: 7.40 / 7.34).
-// NFISAM_HALF=0: never; =2: groups of up to sixteen blocks too (measurements); NFISAM_HALF_W=4|8: waves per block (8: 256
+// NFISAM_HALF=0: never; =2: groups of up to sixteen blocks too (measurements).  Four waves per block (eight: 256
 // particles per block, two waves per SIMD -- measured slower: the younger wave of a SIMD runs at half speed).
-static inline int half_waves() {
-    const char* e = getenv("NFISAM_HALF_W");
-    const int v = e != nullptr ? atoi(e) : 4;
-    return (v == 4 || v == 8) ? v : 4;
-}
+constexpr int half_waves() { return 4; }
 // compute units of the current device, asked once per device and translation unit (first call OUTSIDE a stream capture:
 // unit_prepare / plan creation); 0: unknown
 static inline int device_cus() {
@@ -259,8 +238,8 @@ static inline int device_cus() {
     return v > 0 ? v : 0;
 }
 static inline bool half_shape(int n_cliques, int max_n, int max_D, int K, int H, int L, int T) {
-    const char* e = getenv("NFISAM_HALF");               // read per call: tests switch families in-process
-    if (e != nullptr && e[0] == '0') return false;
+    const int mode = knob::half();                       // read per call: tests switch families in-process
+    if (mode == '0') return false;
     if (H != 8 || K < 2 || hp_of(K) != 16 || L != 1 || T != 1 || max_D > 16 || max_D < 1) return false;
     const int per_block = 32 * half_waves();
     const long copies = (max_n + per_block - 1) / per_block;
@@ -269,28 +248,17 @@ static inline bool half_shape(int n_cliques, int max_n, int max_D, int K, int H,
     // at most 240 blocks, a CU each): one Plaza clique 6.71 us per iteration against 6.94 for the 64-particle family, +3 % of
     // Plaza1's training rate -- but 240 whole-CU blocks fill seven of the eight XCDs to the last CU, so it is not the default
     // (DESIGN.md 3.1h).  Its loss record is order-free like every other launch's (LOSS_SLOTS = 128: two blocks per slot).
-    if (e != nullptr && e[0] == '2') return copies <= PERSIST_MAX_COPIES && blocks <= 256;
+    if (mode == '2') return copies <= PERSIST_MAX_COPIES && blocks <= 256;
     return copies <= 8 && blocks <= 256;
 }
 // hidden widths the dim-major kernel is instantiated for (H <= 8: [ga2 | ga1] share one 16-row MFMA operand tile;
 // H = 16: one tile each and separate bias chains)
-static inline bool dim_major_hidden(int H) {
-    const char* e = getenv("NFISAM_GRAD");
-    if (e != nullptr && strcmp(e, "butterfly") == 0) return false;
-    return H == 8 || H == 4 || H == 16;
-}
-// smallest launch ((tile, dim) units) that goes to the dim-major kernel; NFISAM_DIM_MAJOR_MIN overrides (experiments)
-static inline long dim_major_min_units() {
-    const char* e = getenv("NFISAM_DIM_MAJOR_MIN");
-    return e != nullptr ? atol(e) : 0;
-}
+constexpr bool dim_major_hidden(int H) { return H == 8 || H == 4 || H == 16; }
 static inline bool is_dim_major(int n_cliques, int max_n, int max_D, int L, int tile, int H) {
-    const long tiles = (long)((max_n + TILE - 1) / TILE) * n_cliques;
     // four waves' LDS rows + the weight panel must fit next to each other (160 KB per CU): D <= 96; wider cliques take
     // the tile-major kernels
     // (H = 16: D <= 80 -- the panel and the h1 rows are twice as big)
-    return tile == TILE && L == 1 && dim_major_hidden(H) && dim_major_enabled() && max_D <= (H == 16 ? 80 : 96) &&
-           tiles * max_D > dim_major_min_units();
+    return tile == TILE && L == 1 && dim_major_hidden(H) && dim_major_enabled() && max_D <= (H == 16 ? 80 : 96);
 }
 
 // 64-particle tiles summed into one gradient copy (one wave's sweep in nsf_train1_kernel, one block's in
@@ -301,11 +269,10 @@ static inline bool is_dim_major(int n_cliques, int max_n, int max_D, int L, int 
 static inline int tiles_per_block(int n_cliques, int max_n, int max_D, int L, int tile, int H) {
     if (tile != TILE || L != 1 || !(use_mfma_grad(H) || dim_major_hidden(H))) return 1;
     const long tiles_c = (max_n + TILE - 1) / TILE, tiles = tiles_c * n_cliques;
-    if (tiles * max_D <= dim_major_min_units()) return 1;
-    const char* e = getenv("NFISAM_TILES_PER_BLOCK");
+    const int asked = knob::tiles_per_block();       // (0 when unset: in neither family's set)
     int T = 1;
     if (is_dim_major(n_cliques, max_n, max_D, L, tile, H)) {
-        if (e != nullptr && (atoi(e) == 1 || atoi(e) == 2 || atoi(e) == 4 || atoi(e) == 8)) return atoi(e);
+        if (const int t = knob::int_in_set(asked, 1, 2, 4, 8, 0)) return t;
         // One tile per wave while the launch is at most ~2 rounds of resident waves (3 per SIMD x 1024 SIMDs); beyond that
         // waves take two tiles (and share one prologue: tile fetch, weight panel, pending Adam update), then four.
         // Measured on 8..64 cliques of n = 2000, D = 15 with the iteration split over two parallel graph branches
@@ -321,7 +288,7 @@ static inline int tiles_per_block(int n_cliques, int max_n, int max_D, int L, in
     }
     if (!use_mfma_grad(H)) return 1;             // nsf_train_kernel sweeps several tiles per block on its MFMA gradient path only
     if (tiles <= 256) return 1;                  // nsf_train_kernel spreads the dims over grid.z there: one tile per block
-    if (e != nullptr && atoi(e) >= 1 && atoi(e) <= 8) return atoi(e);
+    if (const int t = knob::int_in_range(asked, 1, 8, 0)) return t;
     const int W = max_D < 4 ? max_D : 4;
     while (T < 4 && tiles * W / (2 * T) >= 4096) T *= 2;
     return T;

@@ -653,16 +653,7 @@ extern "C" int nfisam_nsf_backward(const float* x, const float* kparams, int n, 
 
 // Small launches use per-tile gradient slabs (kgrad must then hold n_tiles copies, see
 // nfisam_nsf_grad_workspace_count); large ones accumulate with atomics into a single copy.
-static int slab_max_tiles() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("NFISAM_SLAB_MAX_TILES");
-        v = (e != nullptr) ? atoi(e) : 128;
-        if (v < 0) v = 0;
-    }
-    return v;
-}
-static bool use_slabs(int max_n, int tile) { return (max_n + tile - 1) / tile <= slab_max_tiles(); }
+static bool use_slabs(int max_n, int tile) { return (max_n + tile - 1) / tile <= knob::slab_max_tiles(); }
 
 // Upper bound over both kernel families (the launch shape is picked per launch; several tiles per block only
 // lower the number of copies).
@@ -730,8 +721,7 @@ static TrainProblem make_problem(const nfisam_clique* cliques, bool on_host, int
 // MFMA conditioner, nsf_cond_mfma.h) when the launch is dim-major with few gradient copies; the chunk's last update is
 // applied by nsf_adam_kernel in `close_chunk` mode.  Saves one kernel boundary (~3-4 us) per iteration.
 static bool fused_adam_shape(const TrainProblem& q, const TrainShape& sh) {
-    const char* e = getenv("NFISAM_FUSED_ADAM");
-    if (e != nullptr && e[0] == '0') return false;
+    if (!knob::fused_adam()) return false;
     if (!is_dim_major(q.n_cliques, q.max_n, q.max_D, q.L, sh.tile, q.H) || sh.slab == 0) return false;
     return (q.max_n + sh.slab - 1) / sh.slab <= 8;              // nsf_adam_kernel's one-thread-per-parameter summation order
 }
@@ -741,8 +731,7 @@ static bool fused_adam_shape(const TrainProblem& q, const TrainShape& sh) {
 // the parameters themselves: whoever set them -- the caller, an earlier run -- did not go through the Adam kernel).
 static bool pair_image_shape(const TrainProblem& q, const TrainShape& sh) {
     if (q.L < 2 || sh.tile != TILE2 || q.max_D > PAIR_MAX_D) return false;
-    const char* e = getenv("NFISAM_PAIR_IMAGE");
-    if (e != nullptr && e[0] == '0') return false;
+    if (!knob::pair_image()) return false;
     const NsfUnitOps* ops = find_ops(q.K, q.H);
     return ops != nullptr && ops->pair_lds(q.L, q.max_D) > 0;
 }
@@ -838,17 +827,13 @@ static inline double mono_seconds() {
 static std::atomic<bool> g_persist_broken{false};     // a persistent launch of this process stalled once: never again (nfisam_nsf_train_plan_run)
 static bool persist_shape(const TrainProblem& q, long* blocks_out = nullptr, long* places_out = nullptr) {
     const int max_n = q.max_n, max_D = q.max_D, K = q.K, H = q.H, L = q.L;
-    static const bool on = !(getenv("NFISAM_PERSIST") != nullptr && getenv("NFISAM_PERSIST")[0] == '0');
-    if (!on || g_persist_broken.load() || q.host == nullptr || L != 1 || (H != 16 && H != 8 && H != 4) || max_D > FUSED_COUNTERS) return false;
+    if (!knob::persist() || g_persist_broken.load() || q.host == nullptr || L != 1 || (H != 16 && H != 8 && H != 4) || max_D > FUSED_COUNTERS) return false;
     const TrainShape sh = train_shape(q);
     // (the one-launch-per-iteration fused form sums at most eight gradient copies -- fused_adam_shape --; the persistent
     //  exchange takes up to sixteen, round 5: single cliques of up to 4096 particles, whose plain graph is then gradient
     //  kernel + Adam kernel per iteration; nsf_adam_kernel's lane-partial order for that many copies is the order the
     //  persistent staging sums in, so the two graphs of such a plan still leave the same bits)
-    {
-        const char* fe = getenv("NFISAM_FUSED_ADAM");
-        if (fe != nullptr && fe[0] == '0') return false;
-    }
+    if (!knob::fused_adam()) return false;
     if (!is_dim_major(q.n_cliques, max_n, max_D, L, sh.tile, H) || sh.T != 1 || sh.slab == 0 || (sh.W != 4 && !sh.half) ||
         (max_n + sh.slab - 1) / sh.slab > PERSIST_MAX_COPIES)
         return false;
@@ -871,11 +856,9 @@ static bool persist_shape(const TrainProblem& q, long* blocks_out = nullptr, lon
         std::lock_guard<std::mutex> lk(mu);
         cache.emplace_back(key, places);
     }
-    long limit = places - places / 8;
-    if (const char* e = getenv("NFISAM_PERSIST_BLOCKS")) limit = atol(e);    // (measurement aid)
     if (blocks_out != nullptr) *blocks_out = blocks;
     if (places_out != nullptr) *places_out = places;
-    return blocks <= limit;
+    return blocks <= places - places / 8;
 }
 
 // ---- "probe before persisting" -----------------------------------------------------------------------------------------------
@@ -930,8 +913,7 @@ static int cu_count(int dev) {
     return n > 0 ? n : 0;
 }
 static bool device_is_quiet(long blocks, long places) {
-    static const bool on = !(getenv("NFISAM_PERSIST_PROBE") != nullptr && getenv("NFISAM_PERSIST_PROBE")[0] == '0');
-    if (!on || blocks < 1 || places < 1) return true;
+    if (!knob::persist_probe() || blocks < 1 || places < 1) return true;
     static std::mutex mu;
     struct Seen { int dev; long blocks; long per_cu; double at; bool quiet; };   // (an answer is reused for the SAME footprint only)
     static std::vector<Seen> seen;
@@ -962,7 +944,7 @@ static bool device_is_quiet(long blocks, long places) {
         if (hipGetLastError() == hipSuccess && hipMemcpyAsync(out, ctr, sizeof(out), hipMemcpyDeviceToHost, st) == hipSuccess &&
             hipStreamSynchronize(st) == hipSuccess)
             quiet = out[1] == 0u;
-        if (getenv("NFISAM_PROBE_DEBUG") != nullptr)
+        if (knob::probe_debug())
             fprintf(stderr, "nfisam probe: %ld blocks (%ld places, %ld per CU, %zu B of LDS each): %u arrived, %u gave up, %.3f ms\n", blocks, places,
                     per_cu, lds, out[0], out[1], 1e3 * (mono_seconds() - now));
     }
@@ -1031,8 +1013,7 @@ static int enqueue_chunk_end(const TrainProblem& q, const nfisam_adam_cfg* cfg, 
         const int ablocks = adam_blocks(q, ad, true);
         // behind a chunk-persistent launch of cliques of up to SPAN_MAX_D dims: ONE kernel, the bookkeeping block next to the Adam
         // blocks (nsf_adam_kernel with `fused_close`; NFISAM_FUSED_CLOSE=0: two kernels, the same bits)
-        static const bool fuse_on = !(getenv("NFISAM_FUSED_CLOSE") != nullptr && getenv("NFISAM_FUSED_CLOSE")[0] == '0');
-        if (persistent_chunk && fuse_on && q.max_D <= SPAN_MAX_D) {
+        if (persistent_chunk && knob::fused_close() && q.max_D <= SPAN_MAX_D) {
             ad.fused_close = 1;
             ad.chunk = chunk;
             ad.mirror = mirror;
@@ -1072,7 +1053,7 @@ static int plan_chains(const TrainProblem& q) {
     // measured (MI355X): C3 (3072 waves) 15.0 -> 14.5 us per iteration, 64 cliques (7680 waves) 89.5 -> 82.5;
     // one Plaza clique (480 waves) 11.3 -> 11.7: stays one launch
     int chains = waves >= 1536 ? 2 : 1;
-    if (const char* ce = getenv("NFISAM_CHAINS")) chains = atoi(ce);
+    if (knob::chains_set()) chains = knob::chains();
     const int octets = (q.n_cliques * q.max_D + 7) / 8;
     if (chains > octets) chains = octets;
     if (chains < 1) chains = 1;
@@ -1298,7 +1279,7 @@ static int plan_create_impl(const nfisam_clique* host_cliques, const nfisam_cliq
         // (a plan that is ONE short chunk keeps one launch per iteration: the two-branch graph costs ~12 us more to launch,
         //  which 20 iterations do not earn back -- C3, 20 iterations: 18.2 vs 18.8 us per iteration; with several chunks the
         //  launch of chunk k + 1 hides behind chunk k and two branches win from 20 iterations per chunk up: 15.2 -> 14.5)
-        const bool one_short_chunk = cfg->max_iters <= p->chunk && p->chunk < 40 && getenv("NFISAM_CHAINS") == nullptr;
+        const bool one_short_chunk = cfg->max_iters <= p->chunk && p->chunk < 40 && !knob::chains_set();
         const int chains = (one_short_chunk || !p->val.empty()) ? 1 : plan_chains(p->prob);
         for (int g = 1; g < chains && e == hipSuccess; ++g) {
             hipStream_t st = nullptr;
@@ -1375,9 +1356,8 @@ static int plan_create_impl(const nfisam_clique* host_cliques, const nfisam_cliq
         // ~10 us inside the launch against ~20 us between two launches (gap 8.9 + closing Adam 4.8 + bookkeeping 6.8), but the run
         // itself ~55 us more (the long launch iterates ~2 % slower than four short ones): Plaza1's fits, ~12 windows each, gain 1.5 %.
         // Not worth being the default of the last round: OFF unless NFISAM_SPAN=1 (read per plan: tests switch it in-process).
-        const char* span_env = getenv("NFISAM_SPAN");
-        const bool span_on = (span_env != nullptr && span_env[0] == '1') || (use_graph & 4) != 0;      // (bit 2 of use_graph: the caller wants nfisam_nsf_train_plan_launch_async)
-        p->span_run = span_env != nullptr && span_env[0] == '1';
+        p->span_run = knob::span();
+        const bool span_on = p->span_run || (use_graph & 4) != 0;      // (bit 2 of use_graph: the caller wants nfisam_nsf_train_plan_launch_async)
         if (span_on && p->exec_p != nullptr && n_cliques == 1 && p->val.empty() && L == 1 && (use_graph & 2) == 0 && p->prob.max_D <= SPAN_MAX_D &&
             cfg->max_iters > p->chunk && cfg->average_window > 0) {
             hipError_t es = hipStreamBeginCapture(p->cap, hipStreamCaptureModeThreadLocal);
@@ -1404,7 +1384,7 @@ static int plan_create_impl(const nfisam_clique* host_cliques, const nfisam_cliq
                 es = hipStreamEndCapture(p->cap, &p->graph_s);
             }
             if (es == hipSuccess && ss == NFISAM_OK) es = hipGraphInstantiate(&p->exec_s, p->graph_s, nullptr, nullptr, 0);
-            if (getenv("NFISAM_SPAN_DEBUG") != nullptr)
+            if (knob::span_debug())
                 fprintf(stderr, "nfisam: window-spanning graph of a plan (n %d, D %d, chunk %d, max_iters %d): capture %d, launcher %d\n", p->prob.max_n, p->prob.max_D,
                         p->chunk, (int)cfg->max_iters, (int)es, ss);
             if (es != hipSuccess || ss != NFISAM_OK) {             // (not an error of the plan: it keeps to one launch per chunk)
@@ -1459,7 +1439,7 @@ static int enqueue_validated_period(const nfisam_train_plan* p, hipStream_t s, b
 static int wait_chunk(const nfisam_train_plan* p, int k, hipStream_t work, bool* poisoned) {
     const volatile nfisam_train_state* m = p->hst;
     const struct timespec nap = {0, 50000};
-    static const double give_up_s = getenv("NFISAM_WAIT_SECONDS") != nullptr ? atof(getenv("NFISAM_WAIT_SECONDS")) : 60.0;   // (test knob)
+    const double give_up_s = knob::wait_seconds();   // (test knob)
     double t0 = 0.0, last_query = 0.0;
     for (long looks = 0;; ++looks) {
         bool all = true;
@@ -1513,8 +1493,7 @@ extern "C" int nfisam_nsf_train_plan_run(nfisam_train_plan* p, int32_t* iters_ru
     // The chunks' graphs were captured on the plan's private stream; they are REPLAYED on the caller's own stream (round 4:
     // two event record / wait pairs per run, ~12 us of a 20-iteration plan's 330, bought nothing -- a graph may be launched into
     // any stream, the legacy null stream included; NFISAM_PLAN_STREAM=private restores the hand-over).
-    static const bool own_stream = getenv("NFISAM_PLAN_STREAM") != nullptr && strcmp(getenv("NFISAM_PLAN_STREAM"), "private") == 0;
-    if (p->exec && (own_stream || p->stepping)) {
+    if (p->exec && (knob::plan_stream("private") || p->stepping)) {
         HIP_TRY(hipEventRecord(p->ev, user));          // order after prior work on the caller's stream
         HIP_TRY(hipStreamWaitEvent(p->cap, p->ev, 0));
         work = p->cap;
@@ -1573,8 +1552,7 @@ extern "C" int nfisam_nsf_train_plan_run(nfisam_train_plan* p, int32_t* iters_ru
             // hipGraphLaunch of a two-node graph costs more host time than the two launches -- Plaza1's fits 3.45 -> 3.41 s, the 20-step
             // bench line -0.1 us per step, same bits; NFISAM_PERSIST_DIRECT=0 replays the captured graph as before).  The plain form's
             // chunk (up to 2 x 128 kernels) stays a graph.
-            static const bool direct = !(getenv("NFISAM_PERSIST_DIRECT") != nullptr && getenv("NFISAM_PERSIST_DIRECT")[0] == '0');
-            if (direct && persist && p->val.empty()) {
+            if (knob::persist_direct() && persist && p->val.empty()) {
                 int rc = enqueue_step(p->prob, &p->cfg, persistent_chunk(p->chunk), work);
                 if (rc == NFISAM_OK) rc = enqueue_chunk_end(p->prob, &p->cfg, p->chunk, work, p->hst_dev, true);
                 if (rc) return rc;
@@ -1598,8 +1576,8 @@ extern "C" int nfisam_nsf_train_plan_run(nfisam_train_plan* p, int32_t* iters_ru
     };
     // Chunk k + 1 is enqueued BEFORE the host looks at the outcome of chunk k: the stop flags are checked on the device
     // (a chunk behind an early stop is ~chunk empty launches), so the GPU never waits for the host between chunks.
-    // NFISAM_RUN_AHEAD=0 restores launch - wait - launch.
-    static const bool run_ahead = !(getenv("NFISAM_RUN_AHEAD") != nullptr && getenv("NFISAM_RUN_AHEAD")[0] == '0');
+    // NFISAM_RUN_AHEAD=0 restores launch - wait - launch (read per run: a test compares the two in one process).
+    const bool run_ahead = knob::run_ahead();
     if (total_chunks > 0 && !span) {
         int rc = launch_chunk();
         if (rc) return fail(rc);

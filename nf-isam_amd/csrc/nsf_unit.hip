@@ -3533,8 +3533,7 @@ static int unit_walk(const nfisam_post_clique* table, int n_cliques, const int32
     // one-lane-per-sample walk
     const size_t wmax = (size_t)L * (size_t)Layout<KK, HH>::off(max_D);
     const size_t lds2 = (2 * wmax + 8 * (size_t)max_D + 2 * (size_t)max_D + (size_t)3 * max_D * XS2) * sizeof(float);
-    const char* walk_env = getenv("NFISAM_WALK");          // "plain" forces the one-lane walk (tests, A/B)
-    const bool force_plain = (walk_env != nullptr && strcmp(walk_env, "plain") == 0);
+    const bool force_plain = knob::walk("plain");          // forces the one-lane walk (tests, A/B)
     if constexpr (HH % 8 == 0) {
         if (L == 1 && lds2 <= 150 * 1024 && max_D <= 64 && !force_plain) {
             int rc = set_lds(nsf_posterior_walk2_kernel<KK, HH>, lds2);
@@ -3581,19 +3580,12 @@ static int unit_density(const nfisam_post_clique* table, int n_cliques, const in
 // The tile-major kernels (nsf_train_kernel, nsf_train2_kernel) take the launch's arguments alone: one pointer type, so a launcher
 // picks its instantiation once and sets the LDS attribute on the kernel it launches.
 using TrainKernel = void (*)(TrainArgs);
-// nsf_train_kernel of one (K, H): MFMA weight gradients (hidden_dim 8 only: use_mfma_grad) x LDS copy of the parameters
+// nsf_train_kernel of one (K, H): MFMA weight gradients (hidden_dim 8 only: use_mfma_grad), with or without an LDS copy of the parameters
 template <int KK, int HH>
-static TrainKernel train_kernel_of(bool mf, bool wl) {
-    if (mf) {
-        if constexpr (HH == 8) {
-            if (wl) return nsf_train_kernel<KK, HH, true, true, 1>;
-            return nsf_train_kernel<KK, HH, true, false, 1>;
-        } else {
-            return nullptr;
-        }
-    }
-    if (wl) return nsf_train_kernel<KK, HH, false, true, 1>;
-    return nsf_train_kernel<KK, HH, false, false, 1>;
+static TrainKernel train_kernel_of(bool wl) {
+    constexpr bool MF = use_mfma_grad(HH);
+    if (wl) return nsf_train_kernel<KK, HH, MF, true, 1>;
+    return nsf_train_kernel<KK, HH, MF, false, 1>;
 }
 
 // parameter floats one block must hold: all layers, or (dims spread over grid.z) its own dims' blocks
@@ -3638,10 +3630,10 @@ struct PairMap {
 // LDS bytes of nsf_train3_kernel; 0: the launch does not fit it (too wide, or the panels of all layers exceed the CU's LDS)
 template <int KK, int HH>
 static size_t pair_kernel_lds(int L, int max_D) {
+    const int forced = knob::pair();      // '0' | '1' forces one of the kernels (A/B, tests)
     if constexpr (HH == 16) {
         // hidden_dim 16 (round 5): ONE layer's panels resident (9.1 KB per dim at K = 9), sixteen h1 rows per wave
-        const char* pe = getenv("NFISAM_PAIR");
-        if ((pe != nullptr && pe[0] == '0') || max_D > PAIR_MAX_D || max_D < 1) return 0;
+        if (forced == '0' || max_D > PAIR_MAX_D || max_D < 1) return 0;
         const int W = ((max_D + 1) / 2 < 8) ? (max_D + 1) / 2 : 8;
         const size_t fl = (size_t)pair_tile_floats(L, max_D, 1) + (size_t)W * pair_wave_floats<16>() + (size_t)max_D * PairPanel<KK, HH>::floats(max_D);
         return fl * sizeof(float) <= 160 * 1024 ? fl * sizeof(float) : 0;
@@ -3649,9 +3641,8 @@ static size_t pair_kernel_lds(int L, int max_D) {
         // Narrow cliques stay with nsf_train2_kernel: up to four dims are one wave per SIMD there too, and its units get
         // cheaper with the dim (measured, us per iteration split / pair: D 3, L 4: 28.8 / 30.6; D 4: 30.8 / 31.3; D 5: 33.9 /
         // 33.6; D 6 (C2): 39.1 / 34.1; D 8, L 3: 36.5 / 31.1).  NFISAM_PAIR=0 | 1 forces one of them (A/B, tests).
-        const char* pe = getenv("NFISAM_PAIR");
-        const int min_D = ((pe != nullptr && pe[0] == '1') || HH != 8) ? 1 : 6;      // (hidden_dim 4 has no two-lanes-per-particle kernel to stay with)
-        if ((pe != nullptr && pe[0] == '0') || max_D > PAIR_MAX_D || max_D < min_D) return 0;
+        const int min_D = (forced == '1' || HH != 8) ? 1 : 6;      // (hidden_dim 4 has no two-lanes-per-particle kernel to stay with)
+        if (forced == '0' || max_D > PAIR_MAX_D || max_D < min_D) return 0;
         const int W = ((max_D + 1) / 2 < 8) ? (max_D + 1) / 2 : 8;
         const size_t fl = (size_t)pair_tile_floats(L, max_D, 1) + (size_t)W * PAIR_WAVE_FLOATS +
                           (size_t)L * max_D * PairPanel<KK, HH>::floats(max_D);
@@ -3679,10 +3670,7 @@ static int unit_train2(TrainArgs a, int n_cliques, int max_n, int max_D, hipStre
             if (rc) return rc;
             a.g_tiles = 1;
             a.xrows = max_D;
-            {
-                const char* se = getenv("NFISAM_PAIR_STASH");
-                a.pair_stash = ((HH != 16 || KK <= 11) && a.pair_ws && a.L > 1 && pair_stash_fits(max_n, max_D) && !(se != nullptr && se[0] == '0')) ? 1 : 0;
-            }
+            a.pair_stash = ((HH != 16 || KK <= 11) && a.pair_ws && a.L > 1 && pair_stash_fits(max_n, max_D) && knob::pair_stash()) ? 1 : 0;
             const int W = ((max_D + 1) / 2 < 8) ? (max_D + 1) / 2 : 8;
             rc = set_lds(nsf_train3_kernel<KK, HH>, lds3);
             if (rc) return rc;
@@ -3702,14 +3690,11 @@ static int unit_train2(TrainArgs a, int n_cliques, int max_n, int max_D, hipStre
         if (independent_dims && tiles * max_D <= 2048) { W = 1; groups = max_D; }
         else if (independent_dims && tiles * W <= 4096) groups = (max_D + W - 1) / W;
         a.g_tiles = independent_dims ? 0 : 1;
-        {
-            const char* pe = getenv("NFISAM_DIM_PAIRING");
-            a.pair_dims = (pe != nullptr && pe[0] == '0') ? 0 : 1;
-        }
+        a.pair_dims = knob::dim_pairing() ? 1 : 0;
         const size_t tile_floats = (((size_t)a.L + 2 * a.g_tiles) * max_D + 1 + (size_t)W * StgRows<KK, HH>::split) * XS2;
         const size_t wfloats = block_weight_floats<KK, HH>(a, max_D, W, groups);
         // the lanes of a pair read different weight rows: LDS copy whenever it fits, global loads otherwise
-        const bool wl = weights_mode() != 0 && (tile_floats + wfloats) * sizeof(float) <= 150 * 1024;
+        const bool wl = (tile_floats + wfloats) * sizeof(float) <= 150 * 1024;
         a.wl_floats = wl ? (int)wfloats : 0;
         const size_t lds = (tile_floats + (wl ? wfloats : 0)) * sizeof(float);
         const TrainKernel kernel = wl ? nsf_train2_kernel<KK, HH, true> : nsf_train2_kernel<KK, HH, false>;
@@ -3841,8 +3826,7 @@ static bool lean_launch_fits(long blocks, int max_D) {
     static std::mutex mu;
     static long places[MAXDEV][FUSED_COUNTERS + 1] = {};
     if (max_D < 1 || max_D > FUSED_COUNTERS) return false;
-    const char* le = getenv("NFISAM_LEAN");                  // "0": never (A/B, tests; read per call)
-    if (le != nullptr && le[0] == '0') return false;
+    if (!knob::lean()) return false;                         // "0": never (A/B, tests; read per call)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return false;
     long pl;
@@ -3883,8 +3867,6 @@ static int unit_train1(TrainArgs a, int n_cliques, int max_n, int max_D, hipStre
     int rc = PanelMap<KK, HH>::get(max_D, &a.panel_map);
     if (rc) return rc;
     const size_t lds = train1_lds_bytes<KK, HH>(max_D, W, a.persist_iters > 0);
-    size_t lds_launch = lds;
-    if (const char* pe = getenv("NFISAM_LDS_PAD_KB")) lds_launch += (size_t)atoi(pe) * 1024;   // experiments: fewer blocks per CU
     const bool persist = a.persist_iters > 0;
     if (persist && (T != 1 || !a.slab || !a.fused_adam || a.L != 1 || max_D > FUSED_COUNTERS)) return NFISAM_ERR_ARG;
     // the (clique, dim, 256 particles) blocks this launch really has (host copy of the descriptors: the plan's, or the single one)
@@ -3896,8 +3878,7 @@ static int unit_train1(TrainArgs a, int n_cliques, int max_n, int max_D, hipStre
     bool lean = false;
     if constexpr (lean_persist_v<KK, HH>) { if (persist && W == 4 && !spl) lean = lean_launch_fits<KK, HH, true>(real_blocks, max_D); }
     else if constexpr (lean_persist_inst_v<KK, HH>) {
-        static const bool lone_lean = !(getenv("NFISAM_LONE_LEAN") != nullptr && getenv("NFISAM_LONE_LEAN")[0] == '0');
-        if (persist && W == 4 && !spl && lone_lean && real_blocks <= 256) lean = lean_launch_fits<KK, HH, true>(real_blocks, max_D);
+        if (persist && W == 4 && !spl && knob::lone_lean() && real_blocks <= 256) lean = lean_launch_fits<KK, HH, true>(real_blocks, max_D);
     }
     if constexpr (lean_plain_v<KK, HH>) { if (!persist && W == 4 && !spl) lean = lean_launch_fits<KK, HH, false>(real_blocks, max_D); }
     // a window-spanning launch closes its windows in the kernel: that code exists in the two-wave builds (nsf_train1_kernel: ROOMY)
@@ -3905,20 +3886,19 @@ static int unit_train1(TrainArgs a, int n_cliques, int max_n, int max_D, hipStre
     const bool wide = persist && gx > 8;                   // groups of 9 .. 16 blocks (n > 2048): the WIDE instantiation
     // helper waves (round 6): a two-wave build whose blocks get a CU each is launched with eight waves per block -- waves 4 .. 7
     // own no particles and take part in the staging only (one parameter per thread: stage_cond_panel_persist_solo)
-    static const bool helpers_on = !(getenv("NFISAM_HELPERS") != nullptr && getenv("NFISAM_HELPERS")[0] == '0');
     // (MI355X: 256 CUs -> at most 224 such blocks, 240 for groups of nine to sixteen.  The dispatcher deals workgroups round-robin to
     //  the eight XCDs, so what must fit is the busiest XCD's share -- (octets of groups) x (blocks per group), padding included -- into
     //  its cus / 8 CUs: at most 7/8 of them by default; the sixteen-copy launches of NFISAM_HALF=2 may fill an XCD)
     const long cus = device_cus();
     const long per_xcd = (long)((a.groups + 7) / 8) * gx;
-    const bool helpers = helpers_on && persist && (spl || lean || HH == 16) && W == 4 &&      // (hidden_dim 16 compiles to two waves per SIMD anyway)
+    const bool helpers = knob::helpers() && persist && (spl || lean || HH == 16) && W == 4 &&      // (hidden_dim 16 compiles to two waves per SIMD anyway)
                          real_blocks <= (wide ? cus - cus / 16 : cus - cus / 8) &&
                          per_xcd <= (wide ? cus / 8 : cus / 8 - cus / 64);       // (also the window-spanning launch: the in-kernel bookkeeping's work is its first four waves')
     const int BW = helpers ? 2 * W : W;                    // waves per block
     if (persist && gx > PERSIST_MAX_COPIES) return NFISAM_ERR_ARG;
     const Train1Kernel kernel = train1_kernel_of<KK, HH>({persist, lean, wide, spl});
     if (kernel == nullptr) return NFISAM_ERR_ARG;
-    rc = set_lds(kernel, lds_launch);
+    rc = set_lds(kernel, lds);
     if (rc) return rc;
 
     // few cliques: their descriptors travel in the kernel arguments
@@ -3938,18 +3918,17 @@ static int unit_train1(TrainArgs a, int n_cliques, int max_n, int max_D, hipStre
     if (nch > 255 || ch < 0 || ch >= nch) return NFISAM_ERR_ARG;
     {   // contended launches (more than one block per CU: several waves share a SIMD) divide the Adam update among a group's blocks
         // (read by the chunk-persistent kernels only, whose launches have T == 1 and a host copy of the descriptors)
-        static const char* se = getenv("NFISAM_PERSIST_SPLIT");
-        a.persist_split = (se != nullptr) ? (se[0] == '1') : (real_blocks > 256);
+        const int forced = knob::persist_split();
+        a.persist_split = forced >= 0 ? (forced == '1') : (real_blocks > 256);
     }
-    static const int spin_log2 = getenv("NFISAM_PERSIST_SPINS") != nullptr ? atoi(getenv("NFISAM_PERSIST_SPINS")) : 15;           // (~1 us per look: a member that never arrives costs tens of milliseconds, not seconds -- round 4: 22)
-    a.persist_spins = spin_log2 < 1 ? 1 : (spin_log2 > 30 ? 30 : spin_log2);
-    static const bool drop = getenv("NFISAM_PERSIST_DROP") != nullptr && getenv("NFISAM_PERSIST_DROP")[0] == '1';                  // (test knob)
-    static const bool scatter = getenv("NFISAM_PERSIST_SCATTER") != nullptr && getenv("NFISAM_PERSIST_SCATTER")[0] == '1';   // (test knob)
+    a.persist_spins = knob::persist_spins();           // (default 15, ~1 us per look: a member that never arrives costs tens of milliseconds, not seconds -- round 4: 22)
+    const bool drop = knob::persist_drop();            // (test knob)
+    const bool scatter = knob::persist_scatter();      // (test knob)
     // the two test knobs reach the chunk-persistent kernels only; `scatter` also transposes their grid
     const int shifts = a.t_shift | (a.w_shift << 8) | (ch << 16) | (nch << 24) |
                        (persist ? (scatter ? 0x80 : 0) | (drop ? 0x40 : 0) : 0);
     if (gz > 0)
-        hipLaunchKernelGGL(kernel, (persist && scatter) ? dim3(gx, 8, gz) : dim3(8, gx, gz), dim3(64 * BW), lds_launch, s, dev, a.panel_map,
+        hipLaunchKernelGGL(kernel, (persist && scatter) ? dim3(gx, 8, gz) : dim3(8, gx, gz), dim3(64 * BW), lds, s, dev, a.panel_map,
                            a.magic_cliques, a.groups, a.grid_cliques, a.xrows, shifts, a, few);
     HIP_TRY(hipGetLastError());
     return NFISAM_OK;
@@ -3960,7 +3939,7 @@ template <int KK, int HH>
 static int unit_train(const TrainArgs& a_in, int n_cliques, int max_n, int max_D, hipStream_t s) {
     if (a_in.tile == TILE2) return unit_train2<KK, HH>(a_in, n_cliques, max_n, max_D, s);
     TrainArgs a = a_in;
-    const bool mf = use_mfma_grad(HH);
+    constexpr bool mf = use_mfma_grad(HH);
     const long tiles = (long)((max_n + TILE - 1) / TILE) * n_cliques;
     // L == 1 and no dL/dx requested: the dims of a tile never exchange data.  When the launch is small
     // (latency-bound) every (tile, dim) unit becomes its own single-wave block, so that every wave has
@@ -3974,9 +3953,7 @@ static int unit_train(const TrainArgs& a_in, int n_cliques, int max_n, int max_D
         // 4 waves per block: a wave's staging tile is 6.3 KB (24 rows), so 16 waves fit a CU next to the particle tiles.
         // Up to 256 tiles every wave still gets a single unit (dims spread over grid.z); larger launches let a wave
         // loop over its dims and amortise the tile load.
-        W = 4;
-        const char* e = getenv("NFISAM_BIG_W");
-        if (e != nullptr && atoi(e) >= 1 && atoi(e) <= 8) W = atoi(e);
+        W = knob::int_in_range(knob::big_w(), 1, 8, 4);
         if (W > max_D) W = max_D;
         if (tiles <= 256) groups = (max_D + W - 1) / W;
         if (groups == 1 && mf && a.tiles_per_block > 1) T = a.tiles_per_block;
@@ -3988,14 +3965,12 @@ static int unit_train(const TrainArgs& a_in, int n_cliques, int max_n, int max_D
     const size_t wfloats = block_weight_floats<KK, HH>(a, max_D, W, groups);
     // LDS copy of the parameters: pays when few waves share a SIMD (nothing hides a cold scalar-cache
     // miss per weight row); it must fit next to the tiles.  Large batches keep the scalar path.
-    const int wm = weights_mode();
     const long blocks = ((tiles + T - 1) / T) * groups;
     const bool fits = (tile_floats + wfloats) * sizeof(float) <= 150 * 1024;
-    const bool wl = fits && (wm == 1 || (wm == -1 && blocks * W <= 4096 && !(independent_dims && blocks * W > 1024)));
+    const bool wl = fits && blocks * W <= 4096 && !(independent_dims && blocks * W > 1024);
     a.wl_floats = wl ? (int)wfloats : 0;
     const size_t lds = (tile_floats + (wl ? wfloats : 0)) * sizeof(float);
-    const TrainKernel kernel = train_kernel_of<KK, HH>(mf, wl);
-    if (kernel == nullptr) return NFISAM_ERR_ARG;
+    const TrainKernel kernel = train_kernel_of<KK, HH>(wl);
     const int rc = set_lds(kernel, lds);
     if (rc) return rc;
     hipLaunchKernelGGL(kernel, dim3((max_n + TILE * T - 1) / (TILE * T), n_cliques, groups), dim3(64 * W), lds, s, a);
