@@ -337,6 +337,34 @@ int nfisam_sample_mmd(const float* Xt, int x_rows, int m, const float* Yt, int y
                       const nfisam_mmd_block* blocks_dev, int n_blocks, const int32_t* xcols, const int32_t* ycols, int n_entries,
                       const double* scale, const uint8_t* wrap, double* sums, double* scratch, nfisam_stream_t stream);
 
+/* ---- the MMD permutation test: the kernel sums under many relabellings of the pooled set (sample_mmd_perm.hip) -------------
+ * What the number nfisam_sample_mmd gives is worth: pool the two sets, relabel them n_perms times and ask how often the
+ * relabelled MMD reaches the observed one.  Pooled point q is column q of Xt for q < m and column q - m of Yt otherwise; with K
+ * the block's kernel on the pooled set (formula, wrap and scale word for word those of nfisam_sample_mmd), l in {0,1}^(m + n)
+ * a relabelling with m ones, t = K 1 and T = 1' K 1,
+ *     sums[b][p] = { Sxx', Syy', Sxy' } = { l' K l,  T - 2 l' t + l' K l,  l' t - l' K l }      (double[n_blocks][n_perms][3]):
+ * the three sums of nfisam_sample_mmd between the points labelled 1 and the points labelled 0, ready for the same estimators.
+ *   labels: DEVICE, [m + n][W] uint64, W = (n_perms + 63) / 64: bit p & 63 of word [q][p >> 6] is set when pooled point q
+ *   counts as the first set under permutation p; bits past n_perms are ignored.  The entry does not read device data on the
+ *   host: that every permutation has exactly m set bits is the caller's check (the Python binding makes it).
+ *   n_perms: 1 .. NFISAM_MMD_PERM_MAX a call (callers split longer lists: a permutation's numbers do not depend on the split);
+ *   scratch: nfisam_sample_mmd_perm_scratch_count doubles on the device: two per (block, strip of 64 pooled points,
+ *   permutation rounded up to 256) and one per (block, strip); every other argument as in nfisam_sample_mmd.
+ * Every Gram value is evaluated once per 256 permutations, then costs one float64 multiply-add (v_mfma_f64_16x16x4_f64) per
+ * permutation.  Two launches, no float atomics: a 256-thread group per (tile row of the pooled upper triangle, block, 256
+ * permutations), then a thread per (block, permutation) adds the strips in an order that depends on (m, n) alone: two calls
+ * give the same bits; a block's numbers are the same bits alone or anywhere in a table; a permutation's numbers are the same
+ * bits alone, first or last of a call.
+ * NFISAM_ERR_ARG, before any launch: what nfisam_sample_mmd refuses, a NULL labels, n_perms outside 1 .. NFISAM_MMD_PERM_MAX,
+ * more than 2^24 - 1 groups (strips x chunks of 256 permutations x blocks).  Bad table entries or rows yield NaN for that
+ * block and nothing is read out of bounds, as there.  (Additive: ABI 1600.) */
+#define NFISAM_MMD_PERM_MAX 16384
+size_t nfisam_sample_mmd_perm_scratch_count(int m, int n, int n_blocks, int n_perms);   /* 0 for arguments the entry refuses */
+int nfisam_sample_mmd_perm(const float* Xt, int x_rows, int m, const float* Yt, int y_rows, int n,
+                           const nfisam_mmd_block* blocks, const nfisam_mmd_block* blocks_dev, int n_blocks,
+                           const int32_t* xcols, const int32_t* ycols, int n_entries, const double* scale, const uint8_t* wrap,
+                           const uint64_t* labels, int n_perms, double* sums, double* scratch, nfisam_stream_t stream);
+
 /* ---- kernel Stein discrepancy: the pairwise Stein sums of a sample set and its scores (sample_ksd.hip) -----------------------
  * The reference's Gaussian_kernel_stein_discrepancy (src/utils/Statistics.py:216-245) for a DIAGONAL kernel precision p[rows],
  * p_c >= 0.  With d = x_i - x_j, brought into [-pi, pi] as sign(d) wrap(|d|) where wrap[c] is set, and s = the scores:

@@ -1,4 +1,4 @@
-// sample_pairs.h — what the pairwise evaluators over the sample matrix share (sample_mmd.hip, sample_ksd.hip, sample_svgd.hip;
+// sample_pairs.h — what the pairwise evaluators over the sample matrix share (sample_mmd.hip, sample_mmd_perm.hip, sample_ksd.hip, sample_svgd.hip;
 // sample_modes.hip takes the host check of a block table, sample_knn.hip the tile's shape and tile_count, sample_density.hip tile_count): one level up from sample_common.h, which it includes, as
 // factor_model.h is for the factor units.  Each unit still writes out its own walk over the pair tile -- coordinates, chunk
 // loop, row lookup, block guard, wave combine: as shared helpers they cost registers or changed a kernel's listing

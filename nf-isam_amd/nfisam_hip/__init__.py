@@ -29,6 +29,7 @@ EXPORTS = [
     "nfisam_normalize_columns", "nfisam_simulate_clique", "nfisam_nsf_train_plan_launch_async",
     "nfisam_nsf_posterior_log_density", "nfisam_factor_graph_log_density",
     "nfisam_sample_mmd", "nfisam_sample_mmd_scratch_count",
+    "nfisam_sample_mmd_perm", "nfisam_sample_mmd_perm_scratch_count",
     "nfisam_sample_moments", "nfisam_sample_quantiles",
     "nfisam_sample_modes", "nfisam_sample_modes_merge",
     "nfisam_factor_graph_score", "nfisam_factor_graph_score_scratch_count",
@@ -124,6 +125,7 @@ def lib():
         _lib.nfisam_nsf_train_plan_stream.restype = C.c_void_p
         _lib.nfisam_nsf_train_plan_enqueued.restype = C.c_long
         _lib.nfisam_sample_mmd_scratch_count.restype = C.c_size_t
+        _lib.nfisam_sample_mmd_perm_scratch_count.restype = C.c_size_t
         _lib.nfisam_factor_graph_score_scratch_count.restype = C.c_size_t
         _lib.nfisam_factor_graph_hvp_scratch_count.restype = C.c_size_t
         _lib.nfisam_sample_ksd_scratch_count.restype = C.c_size_t
@@ -1098,6 +1100,124 @@ def mmd_sums_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, scale=None, wrap=None, 
                                        _ptr(dev["blocks"]), nb, _ptr(dev["xcols"]), _ptr(dev["ycols"]), int(xc.size),
                                        _ptr(dev["scale"]), _ptr(dev["wrap"]), _ptr(sums), _ptr(scratch), _stream()),
                "nfisam_sample_mmd")
+    return sums
+
+
+# ---- the MMD permutation test: the kernel sums under many relabellings of the pooled set (nfisam_sample_mmd_perm) -------------
+MMD_PERM_MAX = 16384                     # NFISAM_MMD_PERM_MAX: permutations per launch
+MMD_PERM_CHUNK = 256                     # the permutations one group of the kernel carries: calls are split at its multiples
+MMD_PERM_SCRATCH_BYTES = 256 << 20       # a call's strip partials stay below this where 256 permutations a launch allow it
+
+
+def pack_perm_labels(L) -> np.ndarray:
+    """bool [P, m + n] (row p: which pooled points count as the first set under permutation p) -> uint64 [m + n, W],
+    W = (P + 63) // 64: bit p & 63 of word [q][p >> 6], what nfisam_sample_mmd_perm reads."""
+    L = np.asarray(L)
+    if L.ndim != 2 or L.dtype != np.bool_ or L.shape[0] < 1:
+        raise ValueError("labels must be a bool [permutations >= 1, m + n] array")
+    P, N = L.shape
+    W = (P + 63) // 64
+    bits = np.zeros((N, W * 64), dtype=np.uint8)
+    bits[:, :P] = L.T
+    return np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little")).view("<u8").reshape(N, W)
+
+
+def unpack_perm_labels(packed, n_perms: int) -> np.ndarray:
+    """The inverse of `pack_perm_labels`: uint64 [m + n, W] -> bool [n_perms, m + n] (bits past n_perms are dropped)."""
+    packed = np.ascontiguousarray(packed, dtype="<u8")
+    bits = np.unpackbits(packed.view(np.uint8).reshape(packed.shape[0], -1), axis=1, bitorder="little")
+    return np.ascontiguousarray(bits[:, :int(n_perms)].T).astype(np.bool_)
+
+
+def check_perm_labels(labels, m: int, n: int, n_perms: int) -> None:
+    """ValueError unless `labels` describes `n_perms` relabellings of m + n pooled points with exactly m ones each: a bool
+    [n_perms, m + n] array, or its packed form uint64 [m + n, (n_perms + 63) // 64] (`pack_perm_labels`; bits past n_perms are
+    ignored).  The kernel's entry cannot make this check: it does not read device data on the host."""
+    m, n, n_perms = int(m), int(n), int(n_perms)
+    if m < 1 or n < 1:
+        raise ValueError("both sample sets need at least one point")
+    if n_perms < 1:
+        raise ValueError("at least one permutation is needed, got %d" % n_perms)
+    if not isinstance(labels, np.ndarray) or labels.ndim != 2 or labels.dtype not in (np.dtype(np.bool_), np.dtype(np.uint64)):
+        raise ValueError("labels must be a bool [permutations, m + n] or a packed uint64 [m + n, words] numpy array")
+    if labels.dtype == np.bool_:
+        if labels.shape != (n_perms, m + n):
+            raise ValueError("labels must be [%d, %d] (permutations, m + n), got %s" % (n_perms, m + n, tuple(labels.shape)))
+        ones = labels.sum(axis=1)
+    else:
+        if labels.shape != (m + n, (n_perms + 63) // 64):
+            raise ValueError("packed labels must be [%d, %d] (m + n, words), got %s"
+                             % (m + n, (n_perms + 63) // 64, tuple(labels.shape)))
+        ones = unpack_perm_labels(labels, n_perms).sum(axis=1)
+    if np.any(ones != m):
+        p = int(np.argmax(ones != m))
+        raise ValueError("permutation %d labels %d points as the first set, not m = %d" % (p, int(ones[p]), m))
+
+
+def _perm_count(labels, n_perms):
+    """The number of permutations `labels` holds: its rows (bool) or `n_perms`, which the packed form needs."""
+    if isinstance(labels, np.ndarray) and labels.ndim == 2 and labels.dtype == np.bool_:
+        if n_perms is not None and int(n_perms) != labels.shape[0]:
+            raise ValueError("n_perms = %d, but labels has %d rows" % (int(n_perms), labels.shape[0]))
+        return int(labels.shape[0])
+    if n_perms is None:
+        raise ValueError("labels must be a bool [permutations, m + n] numpy array, or packed uint64 with n_perms given")
+    return int(n_perms)
+
+
+def mmd_perm_sums(X, Y, blocks: np.ndarray, xcols, ycols, labels, scale=None, wrap=None, device=None, n_perms=None):
+    """The kernel sums {Sxx', Syy', Sxy'} of every block of `blocks` under every relabelling of the pooled set [X; Y]
+    (X [m, x_cols], Y [n, y_cols], tensor or numpy): the null distribution of the MMD permutation test, every Gram value
+    evaluated once for 256 permutations (nfisam_sample_mmd_perm).  `labels`: bool [P, m + n] numpy, row p marks the pooled
+    points that count as the first set under permutation p (exactly m of them), or its packed form (`pack_perm_labels`) with
+    `n_perms`; everything else as `mmd_sums`.  Every check comes before the first copy.
+    -> [n_blocks, P, 3] float64 device tensor; [b, p] feeds `Statistics.mmd_from_sums` like a row of `mmd_sums`."""
+    device = _row_major_front("mmd_perm_sums", device, X=X, Y=Y)
+    check_mmd_blocks(blocks, xcols, ycols, int(X.shape[1]), int(Y.shape[1]), scale, wrap)
+    check_perm_labels(labels, int(X.shape[0]), int(Y.shape[0]), _perm_count(labels, n_perms))
+    return mmd_perm_sums_t(_columns(X, device), _columns(Y, device), blocks, xcols, ycols, labels, scale, wrap, checked=True,
+                           n_perms=n_perms)
+
+
+def mmd_perm_sums_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, labels, scale=None, wrap=None, checked=False, n_perms=None):
+    """`mmd_perm_sums` on the COLUMN-major matrices Xt [x_rows, m], Yt [y_rows, n] (contiguous float32 device tensors, used in
+    place).  More than MMD_PERM_MAX permutations, or more than fit MMD_PERM_SCRATCH_BYTES of strip partials, are launched in
+    chunks (multiples of 256) and concatenated: a permutation's numbers do not depend on the split."""
+    (x_rows, m), (y_rows, n) = _column_major_front("Xt", Xt), _column_major_front("Yt", Yt)
+    if Xt.device != Yt.device:
+        raise ValueError("Xt and Yt must be on the same device")
+    device = Xt.device
+    P = _perm_count(labels, n_perms)
+    if not checked:
+        check_mmd_blocks(blocks, xcols, ycols, x_rows, y_rows, scale, wrap)
+        check_perm_labels(labels, m, n, P)
+    nb = int(blocks.shape[0])
+    blocks = np.ascontiguousarray(blocks)
+    xc, yc = np.asarray(xcols, dtype=np.int32), np.asarray(ycols, dtype=np.int32)
+    packed = pack_perm_labels(labels) if labels.dtype == np.bool_ else np.ascontiguousarray(labels)
+    per_perm = int(lib().nfisam_sample_mmd_perm_scratch_count(m, n, nb, MMD_PERM_CHUNK)) // MMD_PERM_CHUNK * 8
+    if per_perm < 1:
+        raise ValueError("mmd_perm_sums: %d + %d points in %d blocks exceed the grid" % (m, n, nb))
+    step = max(MMD_PERM_SCRATCH_BYTES // per_perm // MMD_PERM_CHUNK, 1) * MMD_PERM_CHUNK
+    step = min(step, MMD_PERM_MAX)
+    sums = torch.empty(nb, P, 3, dtype=torch.float64, device=device)
+    with torch.cuda.device(device):
+        dev = _upload_named(device, blocks=_table_bytes(blocks), xcols=xc, ycols=yc, scale=_entry_f64(scale), wrap=_flags(wrap))
+        for p0 in range(0, P, step):
+            cnt = min(step, P - p0)
+            words = np.ascontiguousarray(packed[:, p0 // 64:(p0 + cnt + 63) // 64]).view(np.int64)
+            lab = torch.from_numpy(words).to(device)
+            count = int(lib().nfisam_sample_mmd_perm_scratch_count(m, n, nb, cnt))
+            if count < 1:
+                raise ValueError("mmd_perm_sums: %d + %d points, %d blocks and %d permutations exceed the grid" % (m, n, nb, cnt))
+            scratch = torch.empty(count, dtype=torch.float64, device=device)
+            out = sums if cnt == P else torch.empty(nb, cnt, 3, dtype=torch.float64, device=device)
+            _check(lib().nfisam_sample_mmd_perm(_ptr(Xt), x_rows, m, _ptr(Yt), y_rows, n, blocks.ctypes.data_as(C.c_void_p),
+                                                _ptr(dev["blocks"]), nb, _ptr(dev["xcols"]), _ptr(dev["ycols"]), int(xc.size),
+                                                _ptr(dev["scale"]), _ptr(dev["wrap"]), _ptr(lab), cnt, _ptr(out), _ptr(scratch),
+                                                _stream()), "nfisam_sample_mmd_perm")
+            if out is not sums:
+                sums[:, p0:p0 + cnt] = out
     return sums
 
 

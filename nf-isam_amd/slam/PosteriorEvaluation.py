@@ -755,8 +755,23 @@ class PosteriorEvaluation:
         Raises RuntimeError when there is nothing to grade yet, ValueError for an unknown option, a requested variable that
         the ordering, `reference` or `samples` lack, a wrong width, ragged rows or too few points -- before anything is
         launched."""
-        from utils.Statistics import ESTIMATORS, mmd_from_sums
-        what = "posterior_mmd"
+        from utils.Statistics import mmd_from_sums
+        t = self._mmd_tables("posterior_mmd", reference, samples, n, variables, blocks, columns, estimator, sigma, joint)
+        pts, Y, wrap, ycols = t["pts"], t["Y"], t["wrap"], t["ycols"]
+        scale = None
+        if standardise:
+            std = np.maximum(Y.astype(np.float64).std(axis=0), 1e-3)
+            scale = np.where(wrap != 0, 1.0, 1.0 / std[ycols])
+        _nh.check_mmd_blocks(t["blocks"], t["xcols"], ycols, pts.total_dim, t["width"], scale, t["flags"])
+        sums = _nh.mmd_sums_t(pts.St, _nh._columns(Y, pts.device), t["blocks"], t["xcols"], ycols, scale, t["flags"], checked=True)
+        return self._mmd_result(t, mmd_from_sums(sums.cpu().numpy(), pts.rows, t["m"], estimator))
+
+    def _mmd_tables(self, what, reference, samples, n, variables, blocks, columns, estimator, sigma, joint) -> dict:
+        """What `posterior_mmd` and `posterior_mmd_test` share: the option checks, the front, the reference set laid out side
+        by side and the block table (the joint block, one block per variable, the further blocks) -> dict: pts, Y [m, width]
+        float32, m, width, variables, joint, estimator, blocks (MMD_BLOCK_DTYPE), xcols, ycols, wrap [entries] uint8, flags
+        (wrap, or None when no entry is an angle).  Nothing is launched."""
+        from utils.Statistics import ESTIMATORS
         if estimator not in ESTIMATORS:
             raise ValueError("%s: estimator must be one of %s, got %r" % (what, ESTIMATORS, estimator))
         if columns not in ("xy", "all"):
@@ -810,21 +825,75 @@ class PosteriorEvaluation:
                 np.asarray(sigma, dtype=np.float64).reshape(-1)
             if sig.size != len(table) or not np.all(np.isfinite(sig) & (sig > 0)):
                 raise ValueError("%s: sigma is one positive bandwidth, or one per block (%d)" % (what, len(table)))
-        scale = None
-        if standardise:
-            std = np.maximum(Y.astype(np.float64).std(axis=0), 1e-3)
-            scale = np.where(wrap != 0, 1.0, 1.0 / std[ycols])
-        flags = wrap if wrap.any() else None
-        blocks_np = _nh.pack_mmd_blocks(dims, sig)
-        _nh.check_mmd_blocks(blocks_np, xcols, ycols, pts.total_dim, width, scale, flags)
-        sums = _nh.mmd_sums_t(pts.St, _nh._columns(Y, pts.device), blocks_np, xcols, ycols, scale, flags, checked=True)
-        val = mmd_from_sums(sums.cpu().numpy(), rows, m, estimator)
-        k0 = 1 if joint else 0
+        return dict(pts=pts, Y=Y, m=m, width=width, variables=variables, joint=joint, estimator=estimator,
+                    blocks=_nh.pack_mmd_blocks(dims, sig), xcols=xcols, ycols=ycols, wrap=wrap, flags=wrap if wrap.any() else None)
+
+    @staticmethod
+    def _mmd_result(t: dict, val) -> dict:
+        """The values `val` [blocks of `_mmd_tables`] under the names `posterior_mmd` returns them by."""
+        variables, m, rows = t["variables"], t["m"], t["pts"].rows
+        k0 = 1 if t["joint"] else 0
         marginal = {v: float(val[k0 + i]) for i, v in enumerate(variables)}
-        return dict(joint=float(val[0]) if joint else None, marginal=marginal,
+        return dict(joint=float(val[0]) if t["joint"] else None, marginal=marginal,
                     marginal_mean=float(np.mean(list(marginal.values()))),
                     blocks=[float(x) for x in val[k0 + len(variables):]], floor=float(np.sqrt(1.0 / m + 1.0 / rows)),
-                    m=m, n=rows, estimator=estimator)
+                    m=m, n=rows, estimator=t["estimator"])
+
+    def posterior_mmd_test(self, reference, samples=None, n: int = None, variables=None, blocks=None, columns: str = "xy",
+                           estimator: str = "mmd", sigma=None, standardise: bool = False, joint: bool = True,
+                           permutations: int = 999, seed=0, alpha: float = 0.05) -> dict:
+        """`posterior_mmd` with what its numbers are worth: the permutation test of H0 "the posterior samples and the
+        reference set come from one law", for the joint block, every variable's marginal and every further block.  The two
+        sets are pooled and relabelled `permutations` times (`Statistics.permutation_labels(n, m, permutations, seed)`: the
+        posterior points are the first set); a p-value is how often the relabelled statistic reaches the observed one --
+        exact under exchangeability, with ONE reference set.  All blocks and permutations in one device launch per chunk of
+        permutations (nfisam_sample_mmd_perm: every Gram value once for 256 permutations); the observed values come from
+        `posterior_mmd`'s own launch.
+
+        Arguments as `posterior_mmd`, except: standardise divides each non-circular column's differences by the std of that
+        column over the POOLED set (floored at 1e-3) -- a scale taken from one of the sets would change with the labels and
+        break the exchangeability the test rests on; without it the values are `posterior_mmd`'s bit for bit.
+        permutations >= 1; alpha in (0, 1): the level of `threshold` and `rejected`.
+        -> what `posterior_mmd` returns, and p_value {joint (None without `joint`), marginal: {variable: p}, blocks: [...]},
+        p = (1 + #{null >= observed}) / (1 + permutations) ("mmd" is compared on its MMDu2 values, so a NaN never enters);
+        marginal_p_holm {variable: Holm-adjusted p over the variables}; rejected [variables with adjusted p <= alpha];
+        threshold (the same three places: the (1 - alpha) quantile of the null, the observed value included);
+        permutations, seed, alpha.  Raises what `posterior_mmd` raises and ValueError for permutations < 1 or a bad alpha --
+        before anything is launched."""
+        from utils import Statistics as ST
+        what = "posterior_mmd_test"
+        permutations = int(permutations)
+        if permutations < 1:
+            raise ValueError("%s: permutations must be >= 1, got %d" % (what, permutations))
+        if not 0.0 < alpha < 1.0:
+            raise ValueError("%s: alpha must lie in (0, 1), got %r" % (what, alpha))
+        t = self._mmd_tables(what, reference, samples, n, variables, blocks, columns, estimator, sigma, joint)
+        pts, Y, wrap, xcols, ycols, m = t["pts"], t["Y"], t["wrap"], t["xcols"], t["ycols"], t["m"]
+        rows, variables = pts.rows, t["variables"]
+        labels = ST.permutation_labels(rows, m, permutations, seed)
+        scale = None
+        if standardise:                                             # the pooled spread: the same under every relabelling
+            X = pts.St[torch.from_numpy(xcols.astype(np.int64)).to(pts.device)].cpu().numpy().astype(np.float64)
+            std = np.maximum(np.concatenate([X, Y.astype(np.float64)[:, ycols].T], axis=1).std(axis=1), 1e-3)
+            scale = np.where(wrap != 0, 1.0, 1.0 / std)
+        _nh.check_mmd_blocks(t["blocks"], xcols, ycols, pts.total_dim, t["width"], scale, t["flags"])
+        Yt = _nh._columns(Y, pts.device)
+        obs = _nh.mmd_sums_t(pts.St, Yt, t["blocks"], xcols, ycols, scale, t["flags"], checked=True)
+        null = _nh.mmd_perm_sums_t(pts.St, Yt, t["blocks"], xcols, ycols, labels, scale, t["flags"], checked=True)
+        res = ST.permutation_test_from_sums(obs.cpu().numpy(), null.cpu().numpy(), rows, m, estimator, alpha)
+        out = self._mmd_result(t, res["statistic"])
+        k0 = 1 if joint else 0
+
+        def places(a):
+            return dict(joint=float(a[0]) if joint else None, marginal={v: float(a[k0 + i]) for i, v in enumerate(variables)},
+                        blocks=[float(x) for x in a[k0 + len(variables):]])
+
+        holm = ST.holm_adjust(res["p_value"][k0:k0 + len(variables)])
+        out.update(p_value=places(res["p_value"]), threshold=places(res["threshold"]),
+                   marginal_p_holm={v: float(holm[i]) for i, v in enumerate(variables)},
+                   rejected=[v for i, v in enumerate(variables) if holm[i] <= alpha],
+                   permutations=permutations, seed=seed, alpha=float(alpha))
+        return out
 
     # ---- what posterior_summary and posterior_modes share: arguments, block table, the weights ------------------------------
     def _summary_front(self, what, samples, n, variables, pairs, weights):

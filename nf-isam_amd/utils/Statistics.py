@@ -108,6 +108,15 @@ def mmd_blocks(x, y, blocks, estimator: str = "MMDb", sigma=None, scale=None, ci
     column of x (and its partner in y), e.g. 1 / std.  circular [x_cols]: columns that are angles, compared by differences
     wrapped into [-pi, pi).  "MMDu2" and "mmd" need m, n >= 2 (ValueError).  There is no CPU path."""
     import nfisam_hip as _nh
+    table, xcols, ycols, sc, wr, m, n = _mmd_block_tables(x, y, blocks, estimator, sigma, scale, circular)
+    sums = _nh.mmd_sums(x, y, table, xcols, ycols, scale=sc, wrap=wr, device=device)
+    return mmd_from_sums(sums.cpu().numpy(), m, n, estimator)
+
+
+def _mmd_block_tables(x, y, blocks, estimator, sigma, scale, circular):
+    """The argument checks and defaults of `mmd_blocks` (and of `mmd_permutation_test`, which shares them)
+    -> (block table, xcols, ycols, scale per entry or None, wrap per entry or None, m, n).  No device."""
+    import nfisam_hip as _nh
     if estimator not in ESTIMATORS:
         raise ValueError("estimator must be one of %s, got %r" % (ESTIMATORS, estimator))
     if np.ndim(x) != 2 or np.ndim(y) != 2:
@@ -140,9 +149,123 @@ def mmd_blocks(x, y, blocks, estimator: str = "MMDb", sigma=None, scale=None, ci
         if circular.size != x.shape[1]:
             raise ValueError("circular: one flag per column of x (%d), got %d" % (x.shape[1], circular.size))
         wr = circular[xcols].astype(np.uint8)
-    table = _nh.pack_mmd_blocks(dims, sig)
-    sums = _nh.mmd_sums(x, y, table, xcols, ycols, scale=sc, wrap=wr, device=device)
-    return mmd_from_sums(sums.cpu().numpy(), m, n, estimator)
+    return _nh.pack_mmd_blocks(dims, sig), xcols, ycols, sc, wr, m, n
+
+
+# ---- what an MMD value is worth: the permutation test (nfisam_sample_mmd_perm) -------------------------------------------------
+def permutation_labels(m: int, n: int, permutations: int, seed) -> np.ndarray:
+    """The relabellings of a permutation test of m + n pooled points -> bool [permutations, m + n], row p True where a
+    point counts as the first set.  A CONTRACT, so that a seed names the same test everywhere:
+    rng = np.random.Generator(np.random.PCG64(seed)), and row p has its m ones at rng.permutation(m + n)[:m], the rows drawn
+    in order p = 0, 1, ..."""
+    m, n, permutations = int(m), int(n), int(permutations)
+    if m < 1 or n < 1:
+        raise ValueError("both sample sets need at least one point")
+    if permutations < 1:
+        raise ValueError("permutations must be >= 1, got %d" % permutations)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    L = np.zeros((permutations, m + n), dtype=np.bool_)
+    for p in range(permutations):
+        L[p, rng.permutation(m + n)[:m]] = True
+    return L
+
+
+def _null_shapes(statistic, null):
+    """-> (statistic [nb], null [nb, P >= 1]) as float64 arrays."""
+    statistic, null = np.asarray(statistic, dtype=np.float64).reshape(-1), np.asarray(null, dtype=np.float64)
+    null = null.reshape(statistic.size, -1)
+    if null.shape[1] < 1:
+        raise ValueError("the null distribution needs at least one value per block")
+    return statistic, null
+
+
+def permutation_p_value(statistic, null) -> np.ndarray:
+    """(1 + #{null >= statistic}) / (1 + P) per block: statistic [nb], null [nb, P] -> [nb].  Exact under exchangeability,
+    never 0.  For the estimator "mmd" (a square root, NaN where MMDu2 is negative) pass the MMDu2 values of both: the
+    square root is monotone, so it is the same test, and no NaN enters a comparison (`mmd_permutation_test` does so)."""
+    statistic, null = _null_shapes(statistic, null)
+    if np.isnan(statistic).any() or np.isnan(null).any():
+        raise ValueError("NaN in the statistic or its null distribution (compare \"mmd\" on its MMDu2 values)")
+    return (1.0 + (null >= statistic[:, None]).sum(axis=1)) / (1.0 + null.shape[1])
+
+
+def permutation_threshold(statistic, null, alpha: float = 0.05) -> np.ndarray:
+    """The (1 - alpha) quantile of the null distribution with the observed value included, per block: the smallest of the
+    P + 1 values that at most alpha (P + 1) of them exceed -- a statistic above it has p_value <= alpha."""
+    statistic, null = _null_shapes(statistic, null)
+    if not 0.0 < alpha < 1.0:
+        raise ValueError("alpha must lie in (0, 1), got %r" % (alpha,))
+    pooled = np.sort(np.concatenate([null, statistic[:, None]], axis=1), axis=1)
+    k = int(np.ceil((1.0 - alpha) * pooled.shape[1] - 1e-9)) - 1         # (1 - 0.05) * 1000 must count as 950, not 950.0000000000001
+    return pooled[:, min(max(k, 0), pooled.shape[1] - 1)]
+
+
+def holm_adjust(p) -> np.ndarray:
+    """Holm's step-down adjusted p-values: with p sorted ascending, p_(k) -> max_{j <= k} min(1, (K - j + 1) p_(j)); a
+    hypothesis is rejected at family-wise level alpha when its adjusted value is <= alpha.  Same shape as `p`."""
+    p = np.asarray(p, dtype=np.float64)
+    flat = p.reshape(-1)
+    if flat.size == 0:
+        return p.copy()
+    if np.isnan(flat).any() or flat.min() < 0.0 or flat.max() > 1.0:
+        raise ValueError("p-values must lie in [0, 1]")
+    order = np.argsort(flat, kind="stable")
+    adj = np.minimum(1.0, (flat.size - np.arange(flat.size)) * flat[order])
+    out = np.empty_like(flat)
+    out[order] = np.maximum.accumulate(adj)
+    return out.reshape(p.shape)
+
+
+def permutation_test_from_sums(obs_sums, null_sums, m: int, n: int, estimator: str = "MMDb", alpha: float = 0.05) -> dict:
+    """The test's numbers from the kernel sums: obs_sums [nb, 3] (`mmd_sums`), null_sums [nb, P, 3] (`mmd_perm_sums`)
+    -> dict(statistic [nb], null [nb, P], p_value, threshold, p_holm).  "mmd" is compared on its MMDu2 values, reported as
+    the square roots (NaN where MMDu2 is negative; its threshold is NaN then too)."""
+    obs_sums, null_sums = np.asarray(obs_sums, dtype=np.float64), np.asarray(null_sums, dtype=np.float64)
+    nb, P = null_sums.shape[0], null_sums.shape[1]
+    stat = mmd_from_sums(obs_sums, m, n, estimator)
+    null = mmd_from_sums(null_sums.reshape(-1, 3), m, n, estimator).reshape(nb, P)
+    if estimator == "mmd":
+        cmp_stat = mmd_from_sums(obs_sums, m, n, "MMDu2")
+        cmp_null = mmd_from_sums(null_sums.reshape(-1, 3), m, n, "MMDu2").reshape(nb, P)
+    else:
+        cmp_stat, cmp_null = stat, null
+    p = permutation_p_value(cmp_stat, cmp_null)
+    thr = permutation_threshold(cmp_stat, cmp_null, alpha)
+    if estimator == "mmd":
+        with np.errstate(invalid="ignore"):
+            thr = np.sqrt(thr)
+    return dict(statistic=stat, null=null, p_value=p, threshold=thr, p_holm=holm_adjust(p))
+
+
+def mmd_permutation_test(x, y, blocks, permutations: int = 999, seed=0, estimator: str = "MMDb", sigma=None, scale=None,
+                         circular=None, alpha: float = 0.05, labels=None, device=None) -> dict:
+    """What the values of `mmd_blocks` are worth: the permutation test of H0 "x and y come from one law", per block.  The two
+    sets are pooled and relabelled `permutations` times (`permutation_labels(m, n, permutations, seed)`; an explicit `labels`
+    bool [P, m + n] overrides `seed`), and the p-value is how often the relabelled statistic reaches the observed one:
+    exact under exchangeability, one reference set is enough, valid for every estimator.  All blocks and all permutations in
+    one device launch per 256-permutation-aligned chunk (nfisam_hip.mmd_perm_sums: every Gram value once, not once per
+    permutation); the observed statistic comes from the `mmd_sums` launch and is `mmd_blocks`' value bit for bit.
+
+    x, y, blocks, estimator, sigma, scale, circular, device: as `mmd_blocks`, with its checks and defaults.
+    -> dict: statistic [nb], null [nb, P], p_value [nb] = (1 + #{null >= statistic}) / (1 + P) ("mmd": compared on the
+    MMDu2 values), threshold [nb] (the (1 - alpha) quantile of the null with the observed value included), p_holm [nb]
+    (Holm's adjustment over the blocks), permutations, seed (None with explicit labels), estimator, m, n."""
+    import nfisam_hip as _nh
+    table, xcols, ycols, sc, wr, m, n = _mmd_block_tables(x, y, blocks, estimator, sigma, scale, circular)
+    if not 0.0 < alpha < 1.0:
+        raise ValueError("alpha must lie in (0, 1), got %r" % (alpha,))
+    if labels is None:
+        labels = permutation_labels(m, n, permutations, seed)
+    else:
+        labels, seed = np.asarray(labels), None
+        if labels.dtype != np.bool_ or labels.ndim != 2:
+            raise ValueError("labels must be a bool [permutations, m + n] array")
+    _nh.check_perm_labels(labels, m, n, labels.shape[0])
+    obs = _nh.mmd_sums(x, y, table, xcols, ycols, scale=sc, wrap=wr, device=device)
+    null = _nh.mmd_perm_sums(x, y, table, xcols, ycols, labels, scale=sc, wrap=wr, device=device)
+    out = permutation_test_from_sums(obs.cpu().numpy(), null.cpu().numpy(), m, n, estimator, alpha)
+    out.update(permutations=int(labels.shape[0]), seed=seed, estimator=estimator, m=m, n=n)
+    return out
 
 
 # ---- what a sample set says: means, covariances, quantiles on the device (nfisam_sample_moments / nfisam_sample_quantiles) ----
