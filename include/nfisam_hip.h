@@ -738,6 +738,77 @@ int nfisam_sample_density(const float* Qt, int q_rows, int m, const float* Xt, i
                           const int32_t* qcols, const int32_t* xcols, int n_entries, const uint8_t* wrap,
                           const double* log_w, double log_w_sum, double* log_dens, double* dens, nfisam_stream_t stream);
 
+/* ---- trajectory error of every sample against ground truth: aligned ATE and RPE (sample_trajectory.hip) -------------------
+ * The figure SLAM work is judged by, for every row of the sample matrix instead of for the posterior mean alone.  The
+ * reference grades one trajectory on the host: its Plaza scripts copy the samples out, take the mean, align it to the truth
+ * with `kabsch_umeyama` (src/utils/Functions.py:53-71, an SVD) and report the RMSE that is left
+ * (example/slam/plaza_dataset/plaza_traj_performance_plot.py:112-114,196-198,282-293).  Xt[x_rows][n] is the COLUMN-major
+ * float32 device matrix of the tree walk (the layout of nfisam_sample_moments); a lane carries one sample.
+ * The table: P entries, one per pose or landmark.  Entry e names the rows col_x, col_y, col_th of Xt (col_th = -1: no
+ * heading) and holds the float64 truth ax, ay, ath; flags bit 0 (NFISAM_TRAJ_ALIGNED): the entry takes part in the
+ * alignment; bit 1 (NFISAM_TRAJ_LANDMARK): its squared residual goes to the landmark sum, not to the trajectory's. */
+#define NFISAM_TRAJ_ALIGNED  1
+#define NFISAM_TRAJ_LANDMARK 2
+#define NFISAM_TRAJ_ALIGN_NONE       0
+#define NFISAM_TRAJ_ALIGN_RIGID      1
+#define NFISAM_TRAJ_ALIGN_SIMILARITY 2
+#define NFISAM_TRAJ_OUT_ROWS 8
+typedef struct nfisam_traj_entry {
+    int32_t col_x, col_y;      /* rows of Xt */
+    int32_t col_th;            /* row of the heading, or -1 */
+    int32_t flags;             /* NFISAM_TRAJ_ALIGNED | NFISAM_TRAJ_LANDMARK */
+    double  ax, ay, ath;       /* ground truth (ath is not read where col_th = -1) */
+} nfisam_traj_entry;
+typedef struct nfisam_traj_pair {
+    int32_t i, j;              /* two entries that have headings: the pose j is seen from the pose i */
+    int32_t slot;              /* which sum the pair goes to, 0 .. n_slots - 1 (one slot per stride) */
+    int32_t reserved;
+} nfisam_traj_pair;
+
+/* nfisam_sample_trajectory_error replaces Functions.py:53-71 and plaza_traj_performance_plot.py:112-114,196-198,282-293, per
+ * sample.  Over the aligned entries, with a', b' the truth and the sample about their centroids a_bar, b_bar:
+ *     dot = sum a'.b',  cross = sum (a'_y b'_x - a'_x b'_y),  g = hypot(dot, cross),  theta = atan2(cross, dot)
+ *     mode NONE: theta = 0, c = 1, t = 0;  RIGID: c = 1;  SIMILARITY: c = g / sum |b'|^2 (the least-squares scale);
+ *     t = a_bar - c R(theta) b_bar in both aligned modes.
+ *   reflect != 0: the improper fit R(phi) diag(1, -1), phi = atan2(cross-, dot-), dot- = sum (a'_x b'_x - a'_y b'_y),
+ *   cross- = sum (a'_x b'_y + a'_y b'_x), is taken when hypot(dot-, cross-) > g; a heading h then maps to phi - h and theta
+ *   reports phi.  g == 0 (one aligned entry, coincident points) gives theta = 0; sum |b'|^2 == 0 gives c = 1.  This is the
+ *   SVD route's result with S = diag(1, d).  Two passes throughout: never sum x^2 - (sum x)^2 on raw coordinates.
+ *   A second sweep forms the residuals r_e = a_e - (c R b_e + t).
+ *   out  [NFISAM_TRAJ_OUT_ROWS][n] double: theta, c, t_x, t_y, sum |r|^2 over the entries without NFISAM_TRAJ_LANDMARK, the
+ *        same over those with it, sum wrap_pi(b_th + theta - a_th)^2 over the entries with a heading, the largest |r_e| over
+ *        the trajectory entries (NaN if there is none).  (The entry counts are the table's.)
+ *   iout [2][n] int32: 1 where the improper fit was taken; the entry of that largest residual (the first of equal ones; -1).
+ *   entry_sums [P + 1] double: sum_i w_i |r_e,i|^2 for every entry, then sum_i w_i (weights [n] double, NULL: all ones).
+ *   scratch: nfisam_sample_trajectory_scratch_count(n, P) doubles.
+ *   entries: HOST copy of the table (validated here); entries_dev: DEVICE copy (what the kernels read).
+ * Float32 points in, float64 everywhere else; no float atomics.  A 256-thread group per 64 samples: a sample per lane, wave w
+ * takes the entries w, w + 4, ..., the four waves' sums meet in wave order; the per-entry sums take a wave_sum per tile and a
+ * second launch that adds the tiles in ascending order.  Two calls give the same bits; a sample's row of out / iout depends on
+ * its own column and the table alone, not on n or the other samples.  A NaN or infinite coordinate of a sample makes every
+ * output of that sample NaN (iout: 0, -1) and the entry sums, which add over samples; no other sample changes.
+ * NFISAM_ERR_ARG, before any launch: a NULL pointer (weights excepted); x_rows, n or P < 1; an unknown mode; an entry of the
+ * host copy with a row outside [0, x_rows) (col_th: [-1, x_rows)), an unknown flag or a truth that is not finite; an aligned
+ * mode without an aligned entry.  A row of the DEVICE copy outside the matrix is never read and yields NaN.
+ * (Additive: ABI 1600.) */
+size_t nfisam_sample_trajectory_scratch_count(int n, int P);
+int nfisam_sample_trajectory_error(const float* Xt, int x_rows, int n, const nfisam_traj_entry* entries,
+                                   const nfisam_traj_entry* entries_dev, int P, int mode, int reflect, const double* weights,
+                                   double* out, int32_t* iout, double* entry_sums, double* scratch, nfisam_stream_t stream);
+
+/* Relative pose error, the gauge-free companion (no alignment; in the reference nowhere: its scripts stop at
+ * plaza_traj_performance_plot.py:282-293).  For a pair (i, j) of entries with headings, from the sample and from the truth
+ * alike:  d = R(-th_i) (p_j - p_i),  dth = wrap_pi(th_j - th_i).
+ *   out [n_slots][2][n] double: per slot and sample, sum |d_est - d_true|^2 and sum wrap_pi(dth_est - dth_true)^2 over the
+ *   slot's pairs (their count is the table's).  One launch serves every slot: a group per (64 samples, slot), wave w takes the
+ *   pairs w, w + 4, ... of the table and skips other slots'.  The same promises as above.
+ * NFISAM_ERR_ARG, before any launch: a NULL pointer; x_rows, n, P, n_pairs or n_slots < 1; more than 65535 slots; a bad entry
+ * (as above); a pair of the host copy that names an entry outside [0, P), an entry without a heading or a slot outside
+ * [0, n_slots).  (Additive: ABI 1600.) */
+int nfisam_sample_trajectory_rpe(const float* Xt, int x_rows, int n, const nfisam_traj_entry* entries,
+                                 const nfisam_traj_entry* entries_dev, int P, const nfisam_traj_pair* pairs,
+                                 const nfisam_traj_pair* pairs_dev, int n_pairs, int n_slots, double* out, nfisam_stream_t stream);
+
 /* ---- training -------------------------------------------------------------------------- */
 /* Vector-Jacobian product of the L-layer flow (what torch autograd computes for
  * `loss.backward()` in slam/NFiSAM.py:474): kgrad[L*kparam_count] += d<gz,z>/dtheta + d<gl,logdet>/dtheta,

@@ -40,6 +40,7 @@ EXPORTS = [
     "nfisam_chain_record", "nfisam_chain_finish", "nfisam_chain_state_count",
     "nfisam_sample_knn", "nfisam_sample_ball_count",
     "nfisam_sample_density",
+    "nfisam_sample_trajectory_error", "nfisam_sample_trajectory_rpe", "nfisam_sample_trajectory_scratch_count",
 ]
 
 
@@ -132,6 +133,7 @@ def lib():
         _lib.nfisam_sample_svgd_scratch_count.restype = C.c_size_t
         _lib.nfisam_sample_accept_scratch_count.restype = C.c_size_t
         _lib.nfisam_chain_state_count.restype = C.c_size_t
+        _lib.nfisam_sample_trajectory_scratch_count.restype = C.c_size_t
         for name in EXPORTS:
             getattr(_lib, name)   # raises AttributeError if the ABI is incomplete
     return _lib
@@ -2343,3 +2345,186 @@ def sample_density_t(Qt, Xt, blocks: np.ndarray, qcols, xcols, wrap=None, log_w=
                                            C.c_double(0.0 if log_w_sum is None else log_w_sum), _ptr(log_dens), _ptr(dens),
                                            _stream()), "nfisam_sample_density")
     return dict(log_density=log_dens, density=dens)
+
+
+# ---- trajectory error per sample: aligned ATE and RPE (nfisam_sample_trajectory_error, nfisam_sample_trajectory_rpe) ------------
+class TrajEntry(C.Structure):
+    _fields_ = [("col_x", C.c_int32), ("col_y", C.c_int32), ("col_th", C.c_int32), ("flags", C.c_int32), ("ax", C.c_double),
+                ("ay", C.c_double), ("ath", C.c_double)]
+
+
+class TrajPair(C.Structure):
+    _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("slot", C.c_int32), ("reserved", C.c_int32)]
+
+
+TRAJ_ENTRY_DTYPE = np.dtype([("col_x", np.int32), ("col_y", np.int32), ("col_th", np.int32), ("flags", np.int32),
+                             ("ax", np.float64), ("ay", np.float64), ("ath", np.float64)])
+TRAJ_PAIR_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("slot", np.int32), ("reserved", np.int32)])
+assert TRAJ_ENTRY_DTYPE.itemsize == C.sizeof(TrajEntry) == 40 and TRAJ_PAIR_DTYPE.itemsize == C.sizeof(TrajPair) == 16
+TRAJ_ALIGNED, TRAJ_LANDMARK = 1, 2                # NFISAM_TRAJ_ALIGNED, NFISAM_TRAJ_LANDMARK
+TRAJ_MODES = {"none": 0, "rigid": 1, "similarity": 2}                 # NFISAM_TRAJ_ALIGN_*
+TRAJ_OUT_ROWS = 8                                 # NFISAM_TRAJ_OUT_ROWS
+TRAJ_ERROR_KEYS = ("theta", "scale", "t", "sse_traj", "sse_landmark", "sse_heading", "worst", "reflected", "worst_entry",
+                   "entry_sums", "weight_sum", "n_traj", "n_landmark", "n_heading")
+
+
+def pack_traj_entries(col_x, col_y, col_th, truth_xy, truth_th=None, aligned=None, landmark=None) -> np.ndarray:
+    """The entry table (numpy TRAJ_ENTRY_DTYPE): entry e reads the rows col_x[e], col_y[e] and col_th[e] (-1: no heading) of
+    the column-major matrix and is graded against truth_xy[e] (and truth_th[e]).  aligned [P] (default: every entry that is no
+    landmark) marks the entries of the alignment, landmark [P] (default: none) those whose residual goes to the landmark sum."""
+    col_x = np.asarray(col_x, dtype=np.int64).reshape(-1)
+    P = col_x.size
+    xy = np.asarray(truth_xy, dtype=np.float64).reshape(-1, 2) if P else np.zeros((0, 2))
+    th = np.zeros(P) if truth_th is None else np.asarray(truth_th, dtype=np.float64).reshape(-1)
+    land = np.zeros(P, dtype=bool) if landmark is None else np.asarray(landmark, dtype=bool).reshape(-1)
+    al = ~land if aligned is None else np.asarray(aligned, dtype=bool).reshape(-1)
+    col_y, col_th = np.asarray(col_y, dtype=np.int64).reshape(-1), np.asarray(col_th, dtype=np.int64).reshape(-1)
+    if not (col_y.size == col_th.size == th.size == land.size == al.size == xy.shape[0] == P):
+        raise ValueError("pack_traj_entries: one row triple, one truth and one flag per entry (%d)" % P)
+    t = np.zeros(P, dtype=TRAJ_ENTRY_DTYPE)
+    t["col_x"], t["col_y"], t["col_th"] = col_x, col_y, col_th
+    t["flags"] = al.astype(np.int32) * TRAJ_ALIGNED + land.astype(np.int32) * TRAJ_LANDMARK
+    t["ax"], t["ay"], t["ath"] = xy[:, 0], xy[:, 1], np.where(col_th >= 0, th, 0.0)
+    return t
+
+
+def pack_traj_pairs(poses, strides) -> np.ndarray:
+    """The pair table (numpy TRAJ_PAIR_DTYPE) of a time-ordered list `poses` of entries: slot s holds the pairs
+    (poses[k], poses[k + strides[s]])."""
+    poses = np.asarray(poses, dtype=np.int64).reshape(-1)
+    rows = []
+    for s, k in enumerate(strides):
+        k = int(k)
+        if not 1 <= k < poses.size:
+            raise ValueError("pack_traj_pairs: stride %d needs 1 <= stride < %d poses" % (k, poses.size))
+        rows.extend((int(a), int(b), s, 0) for a, b in zip(poses[:-k], poses[k:]))
+    if not rows:
+        raise ValueError("pack_traj_pairs: no stride")
+    return np.array(rows, dtype=TRAJ_PAIR_DTYPE)
+
+
+def check_traj_entries(entries: np.ndarray, x_rows: int, align="rigid") -> int:
+    """ValueError for what the kernels must not see: a table of another dtype or without entries, a row outside [0, x_rows)
+    (col_th: -1 or a row), an unknown flag, a truth that is not finite, an unknown mode, an aligned mode without an aligned
+    entry.  -> the mode's number."""
+    if align not in TRAJ_MODES:
+        raise ValueError("align is one of %s, got %r" % (", ".join(repr(k) for k in TRAJ_MODES), align))
+    if not isinstance(entries, np.ndarray) or entries.dtype != TRAJ_ENTRY_DTYPE or entries.ndim != 1:
+        raise ValueError("entries must be a 1-D numpy array of TRAJ_ENTRY_DTYPE")
+    if entries.size < 1:
+        raise ValueError("entries: at least one entry is needed (P >= 1)")
+    for name, low in (("col_x", 0), ("col_y", 0), ("col_th", -1)):
+        c = entries[name]
+        if int(c.min()) < low or int(c.max()) >= int(x_rows):
+            raise ValueError("entry %d: %s = %d is out of range of the %d rows of the matrix"
+                             % (int(np.argmax((c < low) | (c >= int(x_rows)))), name, int(c[np.argmax((c < low) | (c >= int(x_rows)))]),
+                                int(x_rows)))
+    if np.any(entries["flags"] & ~(TRAJ_ALIGNED | TRAJ_LANDMARK)):
+        raise ValueError("entry %d: unknown flag" % int(np.argmax(entries["flags"] & ~(TRAJ_ALIGNED | TRAJ_LANDMARK) != 0)))
+    ok = np.isfinite(entries["ax"]) & np.isfinite(entries["ay"]) & (np.isfinite(entries["ath"]) | (entries["col_th"] < 0))
+    if not np.all(ok):
+        raise ValueError("entry %d: the truth is not finite" % int(np.argmin(ok)))
+    if align != "none" and not np.any(entries["flags"] & TRAJ_ALIGNED):
+        raise ValueError("align=%r needs at least one aligned entry" % align)
+    return TRAJ_MODES[align]
+
+
+def check_traj_pairs(pairs: np.ndarray, entries: np.ndarray, n_slots: int = None) -> int:
+    """ValueError for a pair table of another dtype or without pairs, a pair that names an entry outside the table or one
+    without a heading, a slot outside [0, n_slots) (default: the largest slot + 1; at most 65535).  -> n_slots."""
+    if not isinstance(pairs, np.ndarray) or pairs.dtype != TRAJ_PAIR_DTYPE or pairs.ndim != 1:
+        raise ValueError("pairs must be a 1-D numpy array of TRAJ_PAIR_DTYPE")
+    if pairs.size < 1:
+        raise ValueError("pairs: at least one pair is needed")
+    P = int(entries.size)
+    for name in ("i", "j"):
+        bad = (pairs[name] < 0) | (pairs[name] >= P)
+        if np.any(bad):
+            raise ValueError("pair %d: %s = %d is outside the %d entries" % (int(np.argmax(bad)), name, int(pairs[name][np.argmax(bad)]), P))
+        blind = entries["col_th"][pairs[name]] < 0
+        if np.any(blind):
+            raise ValueError("pair %d: entry %d has no heading" % (int(np.argmax(blind)), int(pairs[name][np.argmax(blind)])))
+    n_slots = int(pairs["slot"].max()) + 1 if n_slots is None else int(n_slots)
+    if not 1 <= n_slots <= 65535:
+        raise ValueError("1..65535 slots are supported, got %d" % n_slots)
+    bad = (pairs["slot"] < 0) | (pairs["slot"] >= n_slots)
+    if np.any(bad):
+        raise ValueError("pair %d: slot %d is outside [0, %d)" % (int(np.argmax(bad)), int(pairs["slot"][np.argmax(bad)]), n_slots))
+    return n_slots
+
+
+def sample_trajectory_error(X, entries: np.ndarray, align="rigid", reflect=False, weights=None, device=None):
+    """Every row of X [n, x_cols] (tensor or numpy; float32 points, float64 arithmetic) aligned to the ground truth of
+    `entries` and graded: nfisam_sample_trajectory_error, one sample per lane, on the current stream.  `entries`: numpy
+    TRAJ_ENTRY_DTYPE (`pack_traj_entries`), its rows naming COLUMNS of X; align "none", "rigid" (theta, t) or "similarity"
+    (and the least-squares scale); reflect: also try the improper fit; weights [n] float64 (None: all ones) enter entry_sums
+    alone.  -> dict: theta, scale, sse_traj, sse_landmark, sse_heading, worst [n] float64, t [2, n] float64, reflected,
+    worst_entry [n] int32, entry_sums [P] float64 (sum_i w_i |r_e,i|^2), weight_sum (a 0-d tensor) -- on the device -- and the
+    counts n_traj, n_landmark, n_heading of the table."""
+    device = _row_major_front("sample_trajectory_error", device, X=X)
+    if int(X.shape[0]) < 1:
+        raise ValueError("sample_trajectory_error: no points")
+    check_traj_entries(entries, int(X.shape[1]), align)
+    weights = _check_weights(weights, int(X.shape[0]))
+    return sample_trajectory_error_t(_columns(X, device), entries, align, reflect, weights, checked=True)
+
+
+def sample_trajectory_error_t(Xt, entries: np.ndarray, align="rigid", reflect=False, weights=None, checked=False):
+    """`sample_trajectory_error` on the COLUMN-major matrix Xt [x_rows, n] (a contiguous float32 device tensor, used in place):
+    what the tree walk wrote.  `checked` skips the table and weight checks (the caller has made them)."""
+    x_rows, n = _column_major_front("Xt", Xt)
+    device = Xt.device
+    if n < 1:
+        raise ValueError("sample_trajectory_error: no points")
+    if not checked:
+        check_traj_entries(entries, x_rows, align)
+        weights = _check_weights(weights, n)
+    entries = np.ascontiguousarray(entries)
+    P = int(entries.size)
+    land = (entries["flags"] & TRAJ_LANDMARK) != 0
+    with torch.cuda.device(device):
+        dev = _upload_named(device, entries=_table_bytes(entries))
+        w_d = _f64(weights, device)
+        out = torch.empty(TRAJ_OUT_ROWS, n, dtype=torch.float64, device=device)
+        iout = torch.empty(2, n, dtype=torch.int32, device=device)
+        sums = torch.empty(P + 1, dtype=torch.float64, device=device)
+        scratch = torch.empty(int(lib().nfisam_sample_trajectory_scratch_count(n, P)), dtype=torch.float64, device=device)
+        _check(lib().nfisam_sample_trajectory_error(_ptr(Xt), x_rows, n, entries.ctypes.data_as(C.c_void_p), _ptr(dev["entries"]), P,
+                                                    TRAJ_MODES[align], C.c_int(1 if reflect else 0), _ptr(w_d), _ptr(out),
+                                                    _ptr(iout), _ptr(sums), _ptr(scratch), _stream()),
+               "nfisam_sample_trajectory_error")
+    return dict(theta=out[0], scale=out[1], t=out[2:4], sse_traj=out[4], sse_landmark=out[5], sse_heading=out[6], worst=out[7],
+                reflected=iout[0], worst_entry=iout[1], entry_sums=sums[:P], weight_sum=sums[P], n_traj=int((~land).sum()),
+                n_landmark=int(land.sum()), n_heading=int((entries["col_th"] >= 0).sum()))
+
+
+def sample_trajectory_rpe(X, entries: np.ndarray, pairs: np.ndarray, n_slots=None, device=None):
+    """Relative pose error of every row of X [n, x_cols] (tensor or numpy) over the pairs of `pairs` (numpy TRAJ_PAIR_DTYPE,
+    `pack_traj_pairs`): nfisam_sample_trajectory_rpe, every slot in one launch.  -> dict: trans, rot [n_slots, n] float64 device
+    tensors (sum |d_est - d_true|^2 and sum wrap_pi(dth_est - dth_true)^2 over the slot's pairs), count [n_slots] (numpy)."""
+    device = _row_major_front("sample_trajectory_rpe", device, X=X)
+    if int(X.shape[0]) < 1:
+        raise ValueError("sample_trajectory_rpe: no points")
+    check_traj_entries(entries, int(X.shape[1]), "none")
+    n_slots = check_traj_pairs(pairs, entries, n_slots)
+    return sample_trajectory_rpe_t(_columns(X, device), entries, pairs, n_slots, checked=True)
+
+
+def sample_trajectory_rpe_t(Xt, entries: np.ndarray, pairs: np.ndarray, n_slots=None, checked=False):
+    """`sample_trajectory_rpe` on the COLUMN-major matrix Xt [x_rows, n] (a contiguous float32 device tensor, used in place)."""
+    x_rows, n = _column_major_front("Xt", Xt)
+    device = Xt.device
+    if n < 1:
+        raise ValueError("sample_trajectory_rpe: no points")
+    if not checked:
+        check_traj_entries(entries, x_rows, "none")
+        n_slots = check_traj_pairs(pairs, entries, n_slots)
+    n_slots = int(n_slots)
+    entries, pairs = np.ascontiguousarray(entries), np.ascontiguousarray(pairs)
+    with torch.cuda.device(device):
+        dev = _upload_named(device, entries=_table_bytes(entries), pairs=_table_bytes(pairs))
+        out = torch.empty(n_slots, 2, n, dtype=torch.float64, device=device)
+        _check(lib().nfisam_sample_trajectory_rpe(_ptr(Xt), x_rows, n, entries.ctypes.data_as(C.c_void_p), _ptr(dev["entries"]),
+                                                  int(entries.size), pairs.ctypes.data_as(C.c_void_p), _ptr(dev["pairs"]),
+                                                  int(pairs.size), n_slots, _ptr(out), _stream()), "nfisam_sample_trajectory_rpe")
+    return dict(trans=out[:, 0], rot=out[:, 1], count=np.bincount(pairs["slot"], minlength=n_slots).astype(np.int64))

@@ -1,6 +1,6 @@
 """slam.PosteriorEvaluation -- what a trained NFiSAM solver says about its posterior, not in the reference: densities
 (`posterior_log_pdf`, `joint_log_pdf`, `joint_score`), the solver grading itself (`posterior_diagnostics`, `map_estimate`,
-`posterior_ksd`, `posterior_mmd`), what the posterior holds (`posterior_summary`, `posterior_modes`, `posterior_information`, `posterior_marginal_density`), its samples moved
+`posterior_ksd`, `posterior_mmd`, and against ground truth `posterior_trajectory_error`), what the posterior holds (`posterior_summary`, `posterior_modes`, `posterior_information`, `posterior_marginal_density`), its samples moved
 along the joint score (`posterior_refine`, `map_refine`), the joint density's curvature (`joint_hessian_product`,
 `map_newton`, `laplace_approximation`) and Metropolis chains that make the samples asymptotically exact (`posterior_mcmc`).
 
@@ -1348,4 +1348,115 @@ class PosteriorEvaluation:
             out["hpd_level"] = {v: float(level[k]) for k, v in enumerate(graded)}
             out["mean_nlpd"] = float(np.mean(nl))
             out["coverage"] = {lev: float(np.mean(level <= lev)) for lev in (0.5, 0.9, 0.95)}
+        return out
+
+    # ---- how far every sampled trajectory lies from the ground truth: aligned ATE and RPE ---------------------------------------
+    def posterior_trajectory_error(self, truth, samples=None, n: int = None, poses=None, landmarks=None, align: str = "rigid",
+                                   reflect: bool = False, weights=None, strides=(1,), quantiles=(0.05, 0.5, 0.95),
+                                   threshold=None) -> dict:
+        """The trajectory error of EVERY posterior sample against ground truth, computed on the device from the sample matrix
+        the tree walk left there (nfisam_sample_trajectory_error / nfisam_sample_trajectory_rpe: a sample per lane, float32
+        points, float64 arithmetic).  Each row of that matrix is one complete trajectory: it is aligned to the truth on its
+        own (the planar Kabsch-Umeyama fit in closed form) and graded, so the result is the DISTRIBUTION of the absolute
+        trajectory error over the hypotheses the posterior holds -- where the reference's Plaza scripts grade the posterior mean
+        alone (example/slam/plaza_dataset/plaza_traj_performance_plot.py:112-114,196-198,282-293 with
+        src/utils/Functions.py:53-71), a point that on a multi-modal posterior is no hypothesis at all.
+
+        truth: variable -> [dim] ground truth.  samples, n: as in `posterior_summary` (None draws `n` points through the
+        walk; otherwise what `posterior_log_pdf` accepts); the matrix stays on the device.  poses: the time-ordered
+        trajectory (default: the variables of `physical_vars`, in their order, that have a circular third coordinate and
+        appear in `truth`; nothing is selected by name).  landmarks: graded through the poses' transform, outside the
+        alignment (default: the 2-column variables in `truth`).  align: "none", "rigid" or "similarity" (the least-squares
+        scale); reflect: also try the mirrored fit.  weights: None, an [n] array or "importance" as in `posterior_summary`;
+        they enter the aggregates (per_pose_rmse, summary, mean_trajectory) alone.  strides: the pose distances of the
+        relative pose error (an empty list: none).  quantiles, threshold: of `summary`.
+        -> dict: ate, heading_rms, landmark_rmse [n] (NaN without headings / landmarks), theta, scale [n], t [n, 2], reflected
+        [n] bool, worst_pose (dict(index [n]: the position in `poses` of the pose farthest from its truth, value [n])),
+        per_pose_rmse (variable -> sqrt(sum_i w_i |r_i|^2 / sum_i w_i), poses and landmarks: which stretch of the path is
+        off), rpe ({stride: dict(trans [n], rot [n], pairs)}), summary (utils.Statistics.trajectory_error_summary of ate),
+        mean_trajectory (dict(ate, landmark_rmse, R, c, t): the posterior MEAN -- nfisam_sample_moments' means -- aligned by
+        utils.Functions.kabsch_umeyama on the host and graded: the reference script's number; under "rigid" its scale is set
+        to 1, under "none" it is `posterior_summary`'s translation_rmse over the poses), poses, landmarks, n, ess.
+        Raises RuntimeError when there is nothing to grade yet; ValueError when `truth` holds none of the poses, for a stride
+        outside [1, poses), an unknown mode, bad weights, quantiles or truths -- before anything is launched."""
+        from utils import Functions as FN
+        from utils import Statistics as ST
+        what = "posterior_trajectory_error"
+        if align not in _nh.TRAJ_MODES:
+            raise ValueError("%s: align is one of 'none', 'rigid', 'similarity', got %r" % (what, align))
+        if not hasattr(truth, "__contains__") or not hasattr(truth, "__getitem__"):
+            raise ValueError("%s: truth maps variables to their ground truth" % what)
+        pts, importance, _, _ = self._summary_front(what, samples, n, None, None, weights)
+        known = pts.pcol
+        given = poses is not None
+        if poses is None:
+            poses = [v for v in self.physical_vars if v.dim == 3 and v.circular_dim_list[2] and v in truth and v in known]
+        poses = list(poses)
+        if landmarks is None:
+            landmarks = [v for v in self.physical_vars if v.dim == 2 and v in truth and v in known and v not in poses]
+        landmarks = list(landmarks)
+        if not poses or (given and not any(v in truth for v in poses)):
+            raise ValueError("%s: truth holds none of the poses" % what)
+        for v in poses + landmarks:
+            if v not in known:
+                raise ValueError("%s: variable %s is not in the elimination ordering" % (what, getattr(v, "name", v)))
+            if v not in truth:
+                raise ValueError("%s: truth lacks variable %s" % (what, v.name))
+            if v.dim < 2 or np.ndim(truth[v]) != 1 or len(truth[v]) != v.dim or not np.all(np.isfinite(np.asarray(truth[v], dtype=np.float64))):
+                raise ValueError("%s: truth of %s must be [%d] finite values with an xy part, got shape %s"
+                                 % (what, v.name, v.dim, np.shape(truth[v])))
+        if len(set(poses)) != len(poses):
+            raise ValueError("%s: a pose is listed twice" % what)
+        headed = [v.dim >= 3 and bool(v.circular_dim_list[2]) for v in poses]
+        try:
+            strides = ST.check_strides(strides, len(poses)) if len(tuple(strides)) else ()
+        except ValueError as e:
+            raise ValueError("%s: %s" % (what, e)) from None
+        if strides and not all(headed):
+            raise ValueError("%s: the relative pose error needs a heading on every pose; pass strides=()" % what)
+        probs = np.asarray(quantiles, dtype=np.float64).reshape(-1)
+        if not np.all((probs >= 0.0) & (probs <= 1.0)):
+            raise ValueError("%s: quantiles is a list of probabilities in [0, 1]" % what)
+        if threshold is not None and not float(threshold) > 0.0:
+            raise ValueError("%s: threshold is a positive distance" % what)
+        w_host = self._summary_weights(what, weights, importance, pts.rows)
+
+        every = poses + landmarks
+        P = len(poses)
+        truth64 = [np.asarray(truth[v], dtype=np.float64) for v in every]
+        entries = _nh.pack_traj_entries([known[v] for v in every], [known[v] + 1 for v in every],
+                                        [known[v] + 2 if k < P and headed[k] else -1 for k, v in enumerate(every)],
+                                        np.array([a[:2] for a in truth64]), [a[2] if a.size > 2 else 0.0 for a in truth64],
+                                        landmark=np.arange(len(every)) >= P)
+        _nh.check_traj_entries(entries, pts.total_dim, align)
+        pairs = _nh.pack_traj_pairs(np.arange(P), strides) if strides else None
+        if pairs is not None:
+            _nh.check_traj_pairs(pairs, entries, len(strides))
+
+        w_dev, ess = self._weights(what, pts, importance, w_host)
+        res = ST.trajectory_error_t(pts.St, entries, align, reflect, w_dev, checked=True)
+        rpe = ST._rpe_result(_nh.sample_trajectory_rpe_t(pts.St, entries, pairs, len(strides), checked=True), strides) if strides else {}
+        # the posterior mean, graded the reference's way: the device's means, then the SVD fit on the host
+        cols = np.array([known[v] + c for v in every for c in range(2)], dtype=np.int32)
+        blocks = _nh.pack_moment_blocks(np.ones(cols.size, dtype=np.int64))
+        mean_d, _, _ = _nh.sample_moments_t(pts.St, blocks, cols, None, w_dev)
+        est = mean_d.cpu().numpy().reshape(-1, 2)
+        ref = np.array([a[:2] for a in truth64])
+        R, c, t = np.eye(2), 1.0, np.zeros(2)
+        if align != "none":
+            R, c, t = FN.kabsch_umeyama(ref[:P], est[:P], reflect=reflect)
+            if align == "rigid":
+                c, t = 1.0, ref[:P].mean(axis=0) - R @ est[:P].mean(axis=0)
+        r2 = np.sum((ref - (c * est @ R.T + t)) ** 2, axis=1)
+        w_np = None if w_dev is None else (w_dev.cpu().numpy() if torch.is_tensor(w_dev) else np.asarray(w_dev))
+        out = dict(res)
+        per_entry = out.pop("per_entry_rmse")
+        out.pop("weight_sum")
+        index, value = out.pop("worst_pose")
+        out.update(worst_pose=dict(index=index, value=value), per_pose_rmse={v: float(per_entry[k]) for k, v in enumerate(every)},
+                   rpe=rpe, summary=ST.trajectory_error_summary(res["ate"], w_np, probs, threshold),
+                   mean_trajectory=dict(ate=float(np.sqrt(r2[:P].mean())),
+                                        landmark_rmse=float(np.sqrt(r2[P:].mean())) if len(every) > P else float("nan"),
+                                        R=R, c=float(c), t=t),
+                   poses=poses, landmarks=landmarks, n=pts.rows, ess=ess)
         return out

@@ -982,6 +982,178 @@ def sample_density(x, queries, blocks, circular=None, weights=None, bandwidth="s
                             weights, bandwidth, exclude_self, want_density, checked=True)
 
 
+# ---- trajectory error of every sample: aligned ATE and RPE on the device (nfisam_sample_trajectory_error / _rpe) ---------------
+def trajectory_entries(width, truth_xy, truth_th=None, pose_cols=None, landmark_cols=None, landmark_xy=None):
+    """The entry table of `trajectory_error` for a sample set of `width` columns: P poses, time-ordered, graded against
+    truth_xy [P, 2] (and truth_th [P] where they have headings), then L landmarks against landmark_xy [L, 2], outside the
+    alignment.  pose_cols [P, 3] (or [P, 2] without headings) names their columns; default: consecutive triples (pairs
+    without truth_th) from column 0.  landmark_cols [L, 2]; default with landmark_xy: consecutive pairs after the poses.
+    -> (numpy TRAJ_ENTRY_DTYPE table, P)."""
+    import nfisam_hip as _nh
+    xy = np.asarray(truth_xy, dtype=np.float64)
+    if xy.ndim != 2 or xy.shape[1] != 2 or xy.shape[0] < 1:
+        raise ValueError("truth_xy must be [poses, 2] with at least one pose, got %s" % (xy.shape,))
+    P = xy.shape[0]
+    d = 2 if truth_th is None else 3
+    if truth_th is not None and np.shape(truth_th) != (P,):
+        raise ValueError("truth_th must be [%d], got %s" % (P, np.shape(truth_th)))
+    pc = np.arange(P * d).reshape(P, d) if pose_cols is None else np.asarray(pose_cols, dtype=np.int64)
+    if pc.ndim != 2 or pc.shape != (P, d):
+        raise ValueError("pose_cols must be [%d, %d], got %s" % (P, d, pc.shape))
+    L = 0
+    if landmark_xy is not None or landmark_cols is not None:
+        if landmark_xy is None:
+            raise ValueError("landmark_cols needs landmark_xy, the landmarks' ground truth")
+        lxy = np.asarray(landmark_xy, dtype=np.float64)
+        if lxy.ndim != 2 or lxy.shape[1] != 2:
+            raise ValueError("landmark_xy must be [landmarks, 2], got %s" % (lxy.shape,))
+        L = lxy.shape[0]
+        lc = int(pc.max()) + 1 + np.arange(L * 2).reshape(L, 2) if landmark_cols is None else np.asarray(landmark_cols, dtype=np.int64)
+        if lc.shape != (L, 2):
+            raise ValueError("landmark_cols must be [%d, 2], got %s" % (L, lc.shape))
+        xy = np.vstack([xy, lxy])
+        pc = np.vstack([np.hstack([pc, np.full((P, 3 - d), -1)]), np.hstack([lc, np.full((L, 1), -1)])])
+        d = 3
+    th = None if truth_th is None else np.concatenate([np.asarray(truth_th, dtype=np.float64), np.zeros(L)])
+    entries = _nh.pack_traj_entries(pc[:, 0], pc[:, 1], pc[:, 2] if d == 3 else np.full(P + L, -1), xy, th,
+                                    landmark=np.arange(P + L) >= P)
+    _nh.check_traj_entries(entries, int(width), "none")
+    return entries, P
+
+
+def _trajectory_result(r) -> dict:
+    """The device dict of nfisam_hip.sample_trajectory_error_t -> host float64 arrays in the words of `trajectory_error`."""
+    host = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in r.items()}
+    nt, nl, nh_ = host["n_traj"], host["n_landmark"], host["n_heading"]
+    W = float(host["weight_sum"])
+    nan = np.full_like(host["sse_traj"], np.nan)
+    per_entry = np.sqrt(host["entry_sums"] / W)
+    return dict(ate=np.sqrt(host["sse_traj"] / nt) if nt else nan, heading_rms=np.sqrt(host["sse_heading"] / nh_) if nh_ else nan,
+                landmark_rmse=np.sqrt(host["sse_landmark"] / nl) if nl else nan, theta=host["theta"], scale=host["scale"],
+                t=host["t"].T.copy(), reflected=host["reflected"].astype(bool), worst_pose=(host["worst_entry"], host["worst"]),
+                per_entry_rmse=per_entry, weight_sum=W, n=int(host["theta"].size))
+
+
+def trajectory_error_t(Xt, entries, align="rigid", reflect=False, weights=None, checked=False) -> dict:
+    """`trajectory_error` on the COLUMN-major float32 device matrix Xt [x_rows, n] (used in place) and a packed entry table
+    (`trajectory_entries`, or nfisam_hip.pack_traj_entries: its rows name rows of Xt)."""
+    import nfisam_hip as _nh
+    return _trajectory_result(_nh.sample_trajectory_error_t(Xt, entries, align, reflect, weights, checked=checked))
+
+
+def trajectory_error(x, truth_xy, truth_th=None, pose_cols=None, landmark_cols=None, landmark_xy=None, align="rigid",
+                     reflect=False, weights=None, device=None) -> dict:
+    """The absolute trajectory error of EVERY row of the sample set x [n, x_cols] (numpy or torch) against ground truth, each
+    row aligned to the truth on its own, in one device call (nfisam_hip.sample_trajectory_error: float32 points, float64
+    arithmetic, the planar Kabsch-Umeyama fit in closed form) -- what the reference's Plaza scripts do for the posterior mean
+    alone with `kabsch_umeyama` on the host.  The columns and truths are those of `trajectory_entries`.
+    align: "none", "rigid" (rotation and translation) or "similarity" (and the least-squares scale g / sum |b'|^2 -- not the
+    scale rule of utils.Functions.kabsch_umeyama); reflect: also try the mirrored fit.  Landmarks are graded through the
+    poses' transform and take no part in it.  weights [n] enter per_entry_rmse alone.
+    -> dict of float64 numpy arrays: ate, heading_rms, landmark_rmse [n] (root mean squares over the poses, their headings,
+    the landmarks; NaN where there are none), theta, scale [n], t [n, 2], reflected [n] bool, worst_pose ((entry [n], its
+    residual [n]): the pose farthest from its truth), per_entry_rmse [P + L] (sqrt(sum_i w_i |r_e,i|^2 / sum_i w_i): which
+    stretch of the path is off), weight_sum, n.  A row with a NaN or infinite coordinate has NaN results, and
+    per_entry_rmse with it.  There is no CPU path."""
+    import nfisam_hip as _nh
+    if np.ndim(x) != 2:
+        raise ValueError("x must be [points, columns]")
+    entries, _ = trajectory_entries(int(x.shape[1]), truth_xy, truth_th, pose_cols, landmark_cols, landmark_xy)
+    return _trajectory_result(_nh.sample_trajectory_error(x, entries, align, reflect, weights, device=device))
+
+
+def _rpe_result(r, strides) -> dict:
+    trans, rot, count = r["trans"].cpu().numpy(), r["rot"].cpu().numpy(), r["count"]
+    return {int(k): dict(trans=np.sqrt(trans[s] / count[s]), rot=np.sqrt(rot[s] / count[s]), pairs=int(count[s]))
+            for s, k in enumerate(strides)}
+
+
+def check_strides(strides, poses: int):
+    """-> the tuple of strides; ValueError unless it is a non-empty list of distinct integers in [1, poses)."""
+    try:
+        out = tuple(int(k) for k in strides)
+        exact = all(float(k) == int(k) for k in strides)
+    except (TypeError, ValueError):
+        raise ValueError("strides is a list of integers, got %r" % (strides,)) from None
+    if not out or not exact or len(set(out)) != len(out):
+        raise ValueError("strides is a non-empty list of distinct integers, got %r" % (strides,))
+    for k in out:
+        if not 1 <= k < poses:
+            raise ValueError("stride %d: a stride lies in [1, %d) for %d poses" % (k, poses, poses))
+    return out
+
+
+def relative_pose_error_t(Xt, entries, poses, strides=(1,), checked=False) -> dict:
+    """`relative_pose_error` on the COLUMN-major device matrix Xt and a packed entry table; `poses`: the time-ordered entries."""
+    import nfisam_hip as _nh
+    strides = check_strides(strides, len(poses))
+    pairs = _nh.pack_traj_pairs(poses, strides)
+    n_slots = _nh.check_traj_pairs(pairs, entries, len(strides))
+    if not checked:
+        _nh.check_traj_entries(entries, int(Xt.shape[0]), "none")
+    return _rpe_result(_nh.sample_trajectory_rpe_t(Xt, entries, pairs, n_slots, checked=True), strides)
+
+
+def relative_pose_error(x, truth_xy, truth_th, pose_cols=None, strides=(1,), device=None) -> dict:
+    """Relative pose error of every row of x [n, x_cols] over the time-ordered poses of `trajectory_entries`: for the poses k
+    and k + stride, d = R(-th_k) (p_{k+stride} - p_k) and dth = wrap_pi(th_{k+stride} - th_k) from the sample and from the truth;
+    gauge-free, so nothing is aligned (nfisam_hip.sample_trajectory_rpe, every stride in one launch).
+    -> {stride: dict(trans [n], rot [n], pairs)}: the root mean squares of |d_est - d_true| and of
+    wrap_pi(dth_est - dth_true) over the stride's pairs, float64 numpy."""
+    import nfisam_hip as _nh
+    if np.ndim(x) != 2:
+        raise ValueError("x must be [points, columns]")
+    if truth_th is None:
+        raise ValueError("relative_pose_error needs headings: truth_th")
+    entries, P = trajectory_entries(int(x.shape[1]), truth_xy, truth_th, pose_cols)
+    strides = check_strides(strides, P)
+    pairs = _nh.pack_traj_pairs(np.arange(P), strides)
+    return _rpe_result(_nh.sample_trajectory_rpe(x, entries, pairs, len(strides), device=device), strides)
+
+
+def weighted_quantiles(values, probs, weights=None) -> np.ndarray:
+    """Quantiles of `values` at `probs`: numpy's "linear" rule without weights; with weights the inverted weighted CDF -- the
+    smallest value whose cumulative weight reaches p times the total."""
+    v = np.asarray(values, dtype=np.float64)
+    p = np.asarray(probs, dtype=np.float64).reshape(-1)
+    if weights is None:
+        return np.quantile(v, p)
+    order = np.argsort(v, kind="stable")
+    cum = np.cumsum(np.asarray(weights, dtype=np.float64)[order])
+    at = np.minimum(np.searchsorted(cum, p * cum[-1], side="left"), v.size - 1)
+    return v[order][at]
+
+
+def trajectory_error_summary(ate, weights=None, quantiles=(0.05, 0.5, 0.95), threshold=None) -> dict:
+    """What the per-sample errors `ate` [n] say, on the host in float64 (n numbers need no kernel): -> dict(mean (weighted),
+    quantiles ({p: value}, `weighted_quantiles`), best (sample, value), below (the share of the weight on samples with
+    ate < threshold; None without a threshold), ess ((sum w)^2 / sum w^2), n, n_nan).  Samples whose error is NaN carry no
+    weight here and are counted in n_nan."""
+    a = np.asarray(ate, dtype=np.float64).reshape(-1)
+    if a.size < 1:
+        raise ValueError("trajectory_error_summary: no samples")
+    probs = np.asarray(quantiles, dtype=np.float64).reshape(-1)
+    if not np.all((probs >= 0.0) & (probs <= 1.0)):
+        raise ValueError("quantiles is a list of probabilities in [0, 1]")
+    w = None
+    if weights is not None:
+        w = np.asarray(weights, dtype=np.float64).reshape(-1)
+        if w.size != a.size or not np.all(np.isfinite(w)) or np.any(w < 0) or not np.any(w > 0):
+            raise ValueError("weights must be [n] = [%d], finite, non-negative and not all zero" % a.size)
+    ok = np.isfinite(a)
+    if w is not None:
+        ok &= w > 0
+    if not ok.any():
+        return dict(mean=float("nan"), quantiles={float(p): float("nan") for p in probs}, best=(-1, float("nan")),
+                    below=None if threshold is None else float("nan"), ess=0.0, n=int(a.size), n_nan=int((~np.isfinite(a)).sum()))
+    av, wv = a[ok], (np.ones(int(ok.sum())) if w is None else w[ok])
+    q = weighted_quantiles(av, probs, None if w is None else wv)
+    best = int(np.flatnonzero(ok)[np.argmin(av)])
+    return dict(mean=float(np.sum(wv * av) / np.sum(wv)), quantiles={float(p): float(v) for p, v in zip(probs, q)},
+                best=(best, float(a[best])), below=None if threshold is None else float(np.sum(wv[av < threshold]) / np.sum(wv)),
+                ess=float(np.sum(wv) ** 2 / np.sum(wv * wv)), n=int(a.size), n_nan=int((~np.isfinite(a)).sum()))
+
+
 def sample_mean(samples, var_ordering):
     """The reference's `sample_mean` (src/utils/Statistics.py:151-171) on the device: the mean of every column of samples
     [n, sum of the variables' dims], circular for the columns the variables flag as angles, arithmetic for the others
