@@ -471,6 +471,9 @@ __device__ __forceinline__ void spline_eval(float v, const float (&th)[PoP], flo
     S.d0 = kMinDeriv + fsoftplus(S.ud0);
     S.d1 = kMinDeriv + fsoftplus(S.ud1);
     rq_math<INV>(vs, S.Xk, S.dx, S.Yk, S.dy, S.d0, S.d1, S.t, out, lad);
+    // A draw inside the box stays inside: at z = B the root is t = 1 and Xk + 1 * (B - Xk) may round one ulp past B, where a
+    // later forward pass would take the value for a tail (identity, log-det 0).
+    if (INV) out = (out > B) ? B : ((out < -B) ? -B : out);   // (a NaN stays a NaN)
     if (!S.inside) { out = v; lad = 0.0f; }
 }
 

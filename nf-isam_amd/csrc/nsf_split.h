@@ -168,6 +168,7 @@ __device__ __forceinline__ void spline_eval2(float v, const float (&th)[hp_of(K)
     S.d0 = kMinDeriv + fsoftplus(S.ud0);
     S.d1 = kMinDeriv + fsoftplus(S.ud1);
     rq_math<INV>(vs, S.Xk, S.dx, S.Yk, S.dy, S.d0, S.d1, S.t, out, lad);
+    if (INV) out = (out > B) ? B : ((out < -B) ? -B : out);      // see spline_eval
     if (!S.inside) { out = v; lad = 0.0f; }
 }
 
