@@ -7,6 +7,7 @@ Tolerances (the kernels use 1-ulp hardware exp2/log2/rcp, fp32 t
   z / x            1e-4 abs
   log-det / loss   2e-4 abs
   gradients        1e-3 rel + 2e-5 abs (of the n-normalised gradient)
+                   (the tight check, per parameter against float64 in every launch form: tests/test_train_gradient_{cpu,gpu}.py)
   Adam trajectory  after 10 steps: 2e-3 abs on parameters
 """
 import glob
