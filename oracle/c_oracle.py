@@ -5,6 +5,7 @@ Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import 
 All functions take/return numpy arrays in the torch blob layout documented in nsf_oracle_impl.h.
 `dtype` selects the float (reference arithmetic) or double (yardstick) instantiation.
 """
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -32,6 +33,19 @@ def lib():
         _lib.nsf_oracle_param_count_f.restype = C.c_size_t
         _lib.nsf_oracle_param_count_d.restype = C.c_size_t
     return _lib
+
+
+@contextlib.contextmanager
+def one_thread():
+    """The oracle's threads add their gradients in the order they arrive, so a float32 run differs from call to call in its last
+    bits -- and, where training amplifies them (an unstable start, a long run), in everything.  Inside this context the oracle runs
+    on one thread: the same bits every time, for yardsticks that have to be reproducible."""
+    before = lib().omp_get_max_threads()
+    lib().omp_set_num_threads(1)
+    try:
+        yield
+    finally:
+        lib().omp_set_num_threads(before)
 
 
 def _sfx(dtype):
