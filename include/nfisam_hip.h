@@ -365,6 +365,50 @@ int nfisam_sample_mmd_perm(const float* Xt, int x_rows, int m, const float* Yt, 
                            const int32_t* xcols, const int32_t* ycols, int n_entries, const double* scale, const uint8_t* wrap,
                            const uint64_t* labels, int n_perms, double* sums, double* scratch, nfisam_stream_t stream);
 
+/* ---- sliced Wasserstein: every (block, direction) slice of two sample sets in one launch (sample_transport.hip) --------------
+ * Not in the reference (its src/utils/Statistics.py stops at MMD, RMSE and KSD): how far, in the variables' own units, one
+ * sample set must be moved to become the other.  Block b of the table holds the entries col_off .. col_off + d of the row
+ * lists (entry e pairs row xcols[e] of Xt with row ycols[e] of Yt, as in nfisam_sample_mmd) and n_dirs directions of d doubles
+ * each, direction j at dirs[dir_off + j d ..]; its slices are out[out_off .. out_off + n_dirs).  Blocks may overlap and
+ * repeat entries; their directions and results are their own. */
+typedef struct nfisam_transport_block {
+    int32_t col_off;           /* first entry of the block in xcols / ycols / kind / scale */
+    int32_t d;                 /* number of entries, >= 1 (no upper limit) */
+    int32_t n_dirs;            /* number of directions, 1 .. 65535 */
+    int32_t reserved;          /* 0 */
+    int64_t dir_off;           /* first double of the block's directions in dirs: [n_dirs][d] */
+    int64_t out_off;           /* the block's first slice in out */
+} nfisam_transport_block;
+
+#define NFISAM_TRANSPORT_MAX_N 8192  /* most points per set: two lists of float64 keys in LDS, 128 KiB */
+/* out[out_off_b + j] = W_p^p of the two sets projected on direction j of block b, with
+ *     key(x) = sum_e dir[j][e] * scale[e] * f_e((double)x_e)  in ascending e,  f_e by kind[e]: 0 the value, 1 cos, 2 sin,
+ *     W_p^p  = int_0^1 |F_X^-1(t) - F_Y^-1(t)|^p dt = sum_i sum_j w_ij |a_i - b_j|^p / (m n)  on the sorted keys a [m], b [n],
+ *     j = floor(i n / m) .. ceil((i + 1) n / m) - 1,  w_ij = min((i + 1) n, (j + 1) m) - max(i n, j m):
+ * for m == n the mean of |a_(i) - b_(i)|^p, by the same loop.  A heading enters a block as two entries naming the same row, one
+ * cos and one sin (the chord embedding: continuous across +-pi, the radian difference for small differences); there is no
+ * wrap flag.  A basis vector as direction gives the exact 1-D W_p^p of that entry's marginal.
+ *   Xt[x_rows][m], Yt[y_rows][n]: COLUMN-major float32 device matrices (the layout of the tree walk's St);
+ *   blocks[n_blocks]: HOST copy of the table (validated here), blocks_dev: DEVICE copy of the same table (what the kernel reads);
+ *   xcols, ycols [n_entries] int32, kind [n_entries] uint8 (nullable: all 0), scale [n_entries] double (nullable: all 1),
+ *   dirs [dirs_count] double, out [out_count] double: DEVICE arrays;  p: 1 or 2.
+ * Float32 points in; float64 projection, cos / sin, keys and sums.  One launch, no float atomics: a 256-thread group per
+ * (direction, block) projects both sets, sorts both key lists in 8 (pad(m) + pad(n)) bytes of dynamic LDS (bitonic, padded
+ * with +inf to powers of two) and adds the pieces in a fixed order: two calls give the same bits; a block's slices are the
+ * same bits alone, repeated or anywhere in a table; a direction's slice is the same bits alone or among others.  A slice
+ * with a non-finite key is NaN.
+ * NFISAM_ERR_ARG, before any launch: a NULL pointer (kind and scale excepted), m, n, x_rows, y_rows, n_entries or n_blocks < 1,
+ * m or n > NFISAM_TRANSPORT_MAX_N, p not 1 or 2, more than 65535 blocks, a block with d < 1 or n_dirs outside 1 .. 65535, a
+ * block whose directions leave [0, dirs_count) or whose slices leave [0, out_count).  The device arrays are not read on the
+ * host: a block whose entries leave [0, n_entries), that names a row outside its matrix or that has a kind > 2 yields NaN
+ * in all its slices, reads nothing out of bounds and leaves every other block untouched; the Python binding refuses such
+ * tables before upload.  (Additive: ABI 1600.) */
+int nfisam_sample_sliced_transport(const float* Xt, int x_rows, int m, const float* Yt, int y_rows, int n,
+                                   const nfisam_transport_block* blocks, const nfisam_transport_block* blocks_dev, int n_blocks,
+                                   const int32_t* xcols, const int32_t* ycols, const uint8_t* kind, const double* scale,
+                                   int n_entries, const double* dirs, long long dirs_count, int p, double* out,
+                                   long long out_count, nfisam_stream_t stream);
+
 /* ---- kernel Stein discrepancy: the pairwise Stein sums of a sample set and its scores (sample_ksd.hip) -----------------------
  * The reference's Gaussian_kernel_stein_discrepancy (src/utils/Statistics.py:216-245) for a DIAGONAL kernel precision p[rows],
  * p_c >= 0.  With d = x_i - x_j, brought into [-pi, pi] as sign(d) wrap(|d|) where wrap[c] is set, and s = the scores:

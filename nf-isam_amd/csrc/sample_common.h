@@ -1,5 +1,5 @@
 // sample_common.h — what the float64 evaluators over the column-major sample matrix share (factor_density.hip,
-// factor_score.hip, sample_mmd.hip, sample_mmd_perm.hip, sample_ksd.hip, sample_svgd.hip, sample_summary.hip, sample_modes.hip, sample_mcmc.hip, sample_chains.hip, sample_knn.hip, sample_density.hip, sample_trajectory.hip): the angle wrap, the wave
+// factor_score.hip, sample_mmd.hip, sample_mmd_perm.hip, sample_ksd.hip, sample_svgd.hip, sample_summary.hip, sample_modes.hip, sample_mcmc.hip, sample_chains.hip, sample_knn.hip, sample_density.hip, sample_trajectory.hip, sample_transport.hip): the angle wrap, the wave
 // reductions, the launch epilogue.  A new evaluator over that matrix starts from this header -- one of the FACTORS from
 // factor_model.h, which includes it and holds the factor model the two factor units share, one over PAIRS of points from
 // sample_pairs.h, which includes it and holds what the MMD, KSD and SVGD units share; it does NOT include nsf_host.h

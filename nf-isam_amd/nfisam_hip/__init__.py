@@ -41,6 +41,7 @@ EXPORTS = [
     "nfisam_sample_knn", "nfisam_sample_ball_count",
     "nfisam_sample_density",
     "nfisam_sample_trajectory_error", "nfisam_sample_trajectory_rpe", "nfisam_sample_trajectory_scratch_count",
+    "nfisam_sample_sliced_transport",
 ]
 
 
@@ -92,6 +93,14 @@ class MmdBlock(C.Structure):
 assert C.sizeof(MmdBlock) == 16
 
 
+class TransportBlock(C.Structure):
+    _fields_ = [("col_off", C.c_int32), ("d", C.c_int32), ("n_dirs", C.c_int32), ("reserved", C.c_int32),
+                ("dir_off", C.c_int64), ("out_off", C.c_int64)]
+
+
+assert C.sizeof(TransportBlock) == 32
+
+
 class MomentBlock(C.Structure):
     _fields_ = [("col_off", C.c_int32), ("d", C.c_int32), ("cov_off", C.c_int64)]
 
@@ -134,6 +143,10 @@ def lib():
         _lib.nfisam_sample_accept_scratch_count.restype = C.c_size_t
         _lib.nfisam_chain_state_count.restype = C.c_size_t
         _lib.nfisam_sample_trajectory_scratch_count.restype = C.c_size_t
+        vp, i32, i64 = C.c_void_p, C.c_int, C.c_longlong               # (two 64-bit counts among the ints: spelled out)
+        _lib.nfisam_sample_sliced_transport.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, i64, i32,
+                                                        vp, i64, vp]
+        _lib.nfisam_sample_sliced_transport.restype = C.c_int
         for name in EXPORTS:
             getattr(_lib, name)   # raises AttributeError if the ABI is incomplete
     return _lib
@@ -1103,6 +1116,112 @@ def mmd_sums_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, scale=None, wrap=None, 
                                        _ptr(dev["scale"]), _ptr(dev["wrap"]), _ptr(sums), _ptr(scratch), _stream()),
                "nfisam_sample_mmd")
     return sums
+
+
+# ---- sliced Wasserstein: every (block, direction) slice of two sample sets in one launch (nfisam_sample_sliced_transport) ------
+TRANSPORT_BLOCK_DTYPE = np.dtype([("col_off", np.int32), ("d", np.int32), ("n_dirs", np.int32), ("reserved", np.int32),
+                                  ("dir_off", np.int64), ("out_off", np.int64)])
+assert TRANSPORT_BLOCK_DTYPE.itemsize == C.sizeof(TransportBlock)
+TRANSPORT_MAX_N = 8192                   # NFISAM_TRANSPORT_MAX_N: points per set (two lists of float64 keys in LDS)
+TRANSPORT_KINDS = (0, 1, 2)              # what an entry contributes: the value, its cosine, its sine
+
+
+def pack_transport_blocks(dims, n_dirs) -> np.ndarray:
+    """The block table (numpy TRANSPORT_BLOCK_DTYPE) of consecutive blocks of `dims` entries with `n_dirs` directions each
+    (one count, or one per block): block b's directions are the doubles dir_off .. dir_off + n_dirs * d of the direction
+    array, [n_dirs, d] row-major, and its slices out_off .. out_off + n_dirs of the result, both in table order."""
+    dims = np.asarray(dims, dtype=np.int64).reshape(-1)
+    nd = np.broadcast_to(np.asarray(n_dirs, dtype=np.int64).reshape(-1), dims.shape) if np.size(n_dirs) == 1 else \
+        np.asarray(n_dirs, dtype=np.int64).reshape(-1)
+    if nd.shape != dims.shape:
+        raise ValueError("n_dirs: one count, or one per block (%d), got %d" % (dims.size, nd.size))
+    t = np.zeros(dims.size, dtype=TRANSPORT_BLOCK_DTYPE)
+    t["d"], t["n_dirs"] = dims, nd
+    t["col_off"] = np.cumsum(dims) - dims
+    t["dir_off"] = np.cumsum(dims * nd) - dims * nd
+    t["out_off"] = np.cumsum(nd) - nd
+    return t
+
+
+def check_transport_blocks(blocks: np.ndarray, xcols, ycols, x_rows: int, y_rows: int, dirs, kind=None, scale=None) -> int:
+    """ValueError for tables the kernel must not see: what `_check_table_layout` and `_check_rows` refuse (no block or more
+    than 65535, d < 1, entries outside [0, n_entries), a row outside its matrix, per-entry arrays of another length), a
+    direction count outside 1..65535, a kind outside 0..2, directions that are not a 1-D float array of exactly the doubles
+    the table names, slices that start below 0 or that two blocks share, a non-finite direction or scale.
+    -> the number of slices (the length of the result)."""
+    cols = {"xcols": (xcols, x_rows), "ycols": (ycols, y_rows)}
+    off, d = _check_table_layout(blocks, TRANSPORT_BLOCK_DTYPE, "TRANSPORT_BLOCK_DTYPE", cols, dict(kind=kind, scale=scale))
+    _check_rows(cols)
+    nd, doff, ooff = (blocks[k].astype(np.int64) for k in ("n_dirs", "dir_off", "out_off"))
+    if np.any((nd < 1) | (nd > 65535)):
+        b = int(np.argmax((nd < 1) | (nd > 65535)))
+        raise ValueError("block %d: n_dirs = %d is outside 1..65535" % (b, int(nd[b])))
+    if kind is not None and not np.all(np.isin(np.asarray(kind), TRANSPORT_KINDS)):
+        raise ValueError("kind must be 0 (the value), 1 (its cosine) or 2 (its sine)")
+    if torch.is_tensor(dirs) or np.ndim(dirs) != 1 or np.asarray(dirs).dtype.kind != "f":
+        raise ValueError("dirs must be a 1-D float array (numpy): every block's [n_dirs, d] directions, flattened")
+    dirs = np.asarray(dirs, dtype=np.float64)
+    if np.any(doff < 0) or int((doff + nd * d).max()) != dirs.size:
+        raise ValueError("dirs has %d values, the table names %d (block b: dir_off .. dir_off + n_dirs * d, dir_off >= 0)"
+                         % (dirs.size, int((doff + nd * d).max())))
+    if np.any(ooff < 0):
+        raise ValueError("block %d: out_off must be >= 0" % int(np.argmax(ooff < 0)))
+    _check_disjoint(ooff, nd, "every slice is stored once")
+    if not np.all(np.isfinite(dirs)):
+        raise ValueError("dirs must be finite")
+    if scale is not None and not np.all(np.isfinite(np.asarray(scale, dtype=np.float64))):
+        raise ValueError("scale must be finite")
+    return int((ooff + nd).max())
+
+
+def _check_transport_sizes(m, n, p):
+    if p not in (1, 2):
+        raise ValueError("p must be 1 or 2, got %r" % (p,))
+    if m < 1 or n < 1:
+        raise ValueError("both sample sets need at least one point")
+    if m > TRANSPORT_MAX_N or n > TRANSPORT_MAX_N:
+        raise ValueError("sliced_transport sorts at most %d points per set in LDS, got %d and %d" % (TRANSPORT_MAX_N, m, n))
+
+
+def sliced_transport(X, Y, blocks: np.ndarray, xcols, ycols, dirs, p=2, kind=None, scale=None, device=None):
+    """W_p^p of the sample sets X [m, x_cols] and Y [n, y_cols] (tensor or numpy; float32 points, float64 arithmetic)
+    projected on every direction of every block of `blocks`: nfisam_sample_sliced_transport, one launch on the current
+    stream.  `blocks`: numpy TRANSPORT_BLOCK_DTYPE (`pack_transport_blocks`); entry e of a block pairs column xcols[e] of X
+    with column ycols[e] of Y and contributes dir[e] * scale[e] * f(value) to a point's key, f by kind[e]: 0 the value, 1 its
+    cosine, 2 its sine (a heading enters as two entries, cos and sin); dirs: the blocks' [n_dirs, d] directions, flattened
+    (float64 numpy); p: 1 or 2.  At most TRANSPORT_MAX_N points per set.  -> [slices] float64 device tensor, block b's at
+    out_off .. out_off + n_dirs; `Statistics.wasserstein_from_slices` forms the distances."""
+    device = _row_major_front("sliced_transport", device, X=X, Y=Y)
+    _check_transport_sizes(int(X.shape[0]), int(Y.shape[0]), p)
+    check_transport_blocks(blocks, xcols, ycols, int(X.shape[1]), int(Y.shape[1]), dirs, kind, scale)
+    return sliced_transport_t(_columns(X, device), _columns(Y, device), blocks, xcols, ycols, dirs, p, kind, scale, checked=True)
+
+
+def sliced_transport_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, dirs, p=2, kind=None, scale=None, checked=False):
+    """`sliced_transport` on the COLUMN-major matrices Xt [x_rows, m], Yt [y_rows, n] (contiguous float32 device tensors, used
+    in place): what the tree walk wrote."""
+    (x_rows, m), (y_rows, n) = _column_major_front("Xt", Xt), _column_major_front("Yt", Yt)
+    if Xt.device != Yt.device:
+        raise ValueError("Xt and Yt must be on the same device")
+    device = Xt.device
+    _check_transport_sizes(m, n, p)
+    if not checked:
+        check_transport_blocks(blocks, xcols, ycols, x_rows, y_rows, dirs, kind, scale)
+    nb = int(blocks.shape[0])
+    blocks = np.ascontiguousarray(blocks)
+    xc, yc = np.asarray(xcols, dtype=np.int32), np.asarray(ycols, dtype=np.int32)
+    dirs = np.ascontiguousarray(dirs, dtype=np.float64)
+    n_out = int((blocks["out_off"].astype(np.int64) + blocks["n_dirs"]).max())
+    with torch.cuda.device(device):
+        dev = _upload_named(device, blocks=_table_bytes(blocks), xcols=xc, ycols=yc, kind=_flags(kind), scale=_entry_f64(scale),
+                            dirs=dirs)
+        out = torch.full((n_out,), float("nan"), dtype=torch.float64, device=device)
+        _check(lib().nfisam_sample_sliced_transport(_ptr(Xt), x_rows, m, _ptr(Yt), y_rows, n, blocks.ctypes.data_as(C.c_void_p),
+                                                    _ptr(dev["blocks"]), nb, _ptr(dev["xcols"]), _ptr(dev["ycols"]),
+                                                    _ptr(dev["kind"]), _ptr(dev["scale"]), int(xc.size), _ptr(dev["dirs"]),
+                                                    C.c_longlong(int(dirs.size)), int(p), _ptr(out), C.c_longlong(n_out),
+                                                    _stream()), "nfisam_sample_sliced_transport")
+    return out
 
 
 # ---- the MMD permutation test: the kernel sums under many relabellings of the pooled set (nfisam_sample_mmd_perm) -------------

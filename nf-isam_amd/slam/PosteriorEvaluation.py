@@ -1,6 +1,6 @@
 """slam.PosteriorEvaluation -- what a trained NFiSAM solver says about its posterior, not in the reference: densities
 (`posterior_log_pdf`, `joint_log_pdf`, `joint_score`), the solver grading itself (`posterior_diagnostics`, `map_estimate`,
-`posterior_ksd`, `posterior_mmd`, and against ground truth `posterior_trajectory_error`), what the posterior holds (`posterior_summary`, `posterior_modes`, `posterior_information`, `posterior_marginal_density`), its samples moved
+`posterior_ksd`, `posterior_mmd`, `posterior_transport`, and against ground truth `posterior_trajectory_error`), what the posterior holds (`posterior_summary`, `posterior_modes`, `posterior_information`, `posterior_marginal_density`), its samples moved
 along the joint score (`posterior_refine`, `map_refine`), the joint density's curvature (`joint_hessian_product`,
 `map_newton`, `laplace_approximation`) and Metropolis chains that make the samples asymptotically exact (`posterior_mcmc`).
 
@@ -894,6 +894,100 @@ class PosteriorEvaluation:
                    rejected=[v for i, v in enumerate(variables) if holm[i] <= alpha],
                    permutations=permutations, seed=seed, alpha=float(alpha))
         return out
+
+    def posterior_transport(self, reference, samples=None, n: int = None, variables=None, blocks=None, columns: str = "xy",
+                            p: int = 2, directions: int = 64, seed: int = 0, joint: bool = True, axes: bool = True) -> dict:
+        """How far the posterior must be moved to become a reference sample set, in the variables' own units: the sliced
+        Wasserstein distance W_p of the joint block, of every variable's marginal and of any further blocks, every (block,
+        direction) slice in ONE device launch (nfisam_sample_sliced_transport: float32 points, float64 keys).  Where
+        `posterior_mmd` has no unit, needs a bandwidth and sits at its floor once the sets are out of kernel reach, this
+        number keeps growing with the separation, sees a missing mode as mass times distance and needs no bandwidth.
+
+        reference, samples, n, variables, blocks, columns, joint: as `posterior_mmd`, with the same front and the same
+        handling of the reference; columns="all" adds the headings by the chord embedding (a heading enters as its cosine
+        and its sine: continuous across +-pi, the radian difference for small differences).  p: 1 or 2.  directions: per
+        block, `Statistics.transport_directions(entries of the block, directions, seed)` -- they depend on (seed, entries)
+        alone, so a variable's marginal is the same number in any table.  axes: also the exact 1-D W_p of every entry of every
+        variable (basis-vector directions in the same launch).  At most 8192 points in either set.
+        -> dict: joint (None without `joint`), marginal (variable -> distance), marginal_mean, marginal_max, max_sliced
+        (variable -> max-sliced distance, and "joint"), axes (variable -> per-entry exact 1-D distances; None without
+        `axes`), blocks (list), m (reference points), n (posterior points), p, directions.
+        Raises RuntimeError when there is nothing to grade yet, ValueError for an unknown option, a requested variable that
+        the ordering, `reference` or `samples` lack, a wrong width, ragged rows, an empty set or one of more than 8192
+        points -- before anything is launched."""
+        from utils import Statistics as ST
+        what = "posterior_transport"
+        try:
+            ST.check_transport_options(p, directions, seed)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (what, e)) from None
+        if columns not in ("xy", "all"):
+            raise ValueError("%s: columns must be 'xy' or 'all', got %r" % (what, columns))
+        t = self._transport_tables(what, reference, samples, n, variables, blocks, columns, int(directions), int(seed), joint, axes)
+        pts, tab, variables = t["pts"], t["tab"], t["variables"]
+        _nh.check_transport_blocks(tab["blocks"], tab["xcols"], tab["ycols"], pts.total_dim, t["width"], tab["dirs"], tab["kind"])
+        out = _nh.sliced_transport_t(pts.St, _nh._columns(t["Y"], pts.device), tab["blocks"], tab["xcols"], tab["ycols"], tab["dirs"],
+                                     p, tab["kind"], None, checked=True)
+        res = ST.transport_result(out.cpu().numpy(), tab, p)
+        k0 = 1 if joint else 0
+        marginal = {v: float(res["distance"][k0 + i]) for i, v in enumerate(variables)}
+        max_sliced = {v: float(res["max_sliced"][k0 + i]) for i, v in enumerate(variables)}
+        if joint:
+            max_sliced["joint"] = float(res["max_sliced"][0])
+        return dict(joint=float(res["distance"][0]) if joint else None, marginal=marginal,
+                    marginal_mean=float(np.mean(list(marginal.values()))), marginal_max=float(np.max(list(marginal.values()))),
+                    max_sliced=max_sliced,
+                    axes={v: res["axis"][k0 + i] for i, v in enumerate(variables)} if axes else None,
+                    blocks=[float(x) for x in res["distance"][k0 + len(variables):]], m=t["m"], n=pts.rows, p=int(p),
+                    directions=int(directions))
+
+    def _transport_tables(self, what, reference, samples, n, variables, blocks, columns, directions, seed, joint, axes) -> dict:
+        """The front of `posterior_transport` (that of `posterior_mmd`: the same order of checks, the same handling of the
+        reference; kept apart from `_mmd_tables`, whose tables carry bandwidths and wrap flags) -> dict: pts, Y [m, width]
+        float32, m, width, variables, tab (`Statistics.transport_tables`: the joint block, one block per variable with its
+        axes, the further blocks).  Nothing is launched."""
+        from utils import Statistics as ST
+        pts = self._eval_points(what, samples, n)
+        rows, pcol = pts.rows, pts.pcol
+        known = set(self._elimination_ordering)
+        variables = [v for v in self._elimination_ordering if v in reference] if variables is None else list(variables)
+        extra = [tuple(b) for b in blocks] if blocks is not None else []
+        if not variables:
+            raise ValueError("%s: no variable to compare (the reference holds none of the ordering's)" % what)
+        for v in list(variables) + [v for b in extra for v in b]:
+            if v not in known:
+                raise ValueError("%s: variable %s is not in the elimination ordering" % (what, v.name))
+            if v not in reference:
+                raise ValueError("%s: the reference lacks variable %s" % (what, v.name))
+        for b in extra:
+            if not b or any(v not in variables for v in b):
+                raise ValueError("%s: a block is a non-empty tuple of compared variables" % what)
+        ref, m = self._check_points(reference, what, variables, _REFERENCE_NOUNS, host=True)
+        for name, k in (("reference", m), ("posterior", rows)):
+            if not 1 <= k <= _nh.TRANSPORT_MAX_N:
+                raise ValueError("%s: the %s set has %d points; a set holds 1..%d" % (what, name, k, _nh.TRANSPORT_MAX_N))
+        rcol, width = {}, 0
+        for v in variables:
+            rcol[v] = width
+            width += v.dim
+        Y = np.concatenate([ref[v] for v in variables], axis=1).astype(np.float32)
+        table = ([tuple(variables)] if joint else []) + [(v,) for v in variables] + extra
+        entries = []
+        for blk in table:
+            xr, yr, kd = [], [], []
+            for v in blk:
+                circ = v.circular_dim_list
+                for c in range(v.dim if columns == "all" else min(v.dim, 2)):
+                    kinds = (1, 2) if circ[c] else (0,)             # a heading: its cosine and its sine
+                    xr += [pcol[v] + c] * len(kinds); yr += [rcol[v] + c] * len(kinds); kd += kinds
+            entries.append((np.asarray(xr, dtype=np.int64), np.asarray(yr, dtype=np.int64), np.asarray(kd, dtype=np.uint8)))
+        k0 = 1 if joint else 0
+        flags = [bool(axes) and k0 <= b < k0 + len(variables) for b in range(len(table))]
+        try:
+            tab = ST.transport_tables(entries, directions, seed, flags)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (what, e)) from None
+        return dict(pts=pts, Y=Y, m=m, width=width, variables=variables, tab=tab)
 
     # ---- what posterior_summary and posterior_modes share: arguments, block table, the weights ------------------------------
     def _summary_front(self, what, samples, n, variables, pairs, weights):

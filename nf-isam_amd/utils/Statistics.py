@@ -7,7 +7,8 @@ lengths and quantiles on the device, the modes of a multi-modal sample set (mean
 `translation_distance` and `geodesic_distance` on the host; and the Gaussian kernel Stein discrepancy of a sample set
 against the density's own score (reference: src/utils/Statistics.py:193-245), its pairwise sums on the device; and -- not
 in the reference -- differential entropy, mutual information and a two-sample KL divergence by k nearest neighbours, the
-neighbour search on the device."""
+neighbour search on the device, and the sliced Wasserstein distance between two sample sets, every projection, sort and
+quantile integral on the device."""
 import functools
 import math
 
@@ -266,6 +267,166 @@ def mmd_permutation_test(x, y, blocks, permutations: int = 999, seed=0, estimato
     out = permutation_test_from_sums(obs.cpu().numpy(), null.cpu().numpy(), m, n, estimator, alpha)
     out.update(permutations=int(labels.shape[0]), seed=seed, estimator=estimator, m=m, n=n)
     return out
+
+
+# ---- how far apart two sample sets are, in their own units: sliced Wasserstein (nfisam_sample_sliced_transport) ------------------
+def transport_directions(d: int, count: int, seed: int = 0) -> np.ndarray:
+    """[count, d] float64 unit vectors: Gaussian rows from `np.random.default_rng([seed, d])`, normalised; d = 1 gives the
+    single direction [[1.0]] whatever `count` is.  THE CONTRACT: a block's directions depend on (seed, d) alone -- not on the
+    block's place in a table, nor on what else is compared -- so a block's sliced distance is the same number wherever it is
+    asked for, and the first k rows for `count` = k are the first k rows for any larger count."""
+    d, count, seed = int(d), int(count), int(seed)
+    if d < 1 or count < 1 or seed < 0:
+        raise ValueError("transport_directions: d >= 1, count >= 1 and seed >= 0 are required, got %d, %d, %d" % (d, count, seed))
+    if d == 1:
+        return np.ones((1, 1))
+    g = np.random.default_rng([seed, d]).standard_normal((count, d))
+    return g / np.sqrt((g * g).sum(1))[:, None]
+
+
+def wasserstein_from_slices(slices, p: int):
+    """(sliced distance, max-sliced distance) from a block's slices W_p^p (`nfisam_hip.sliced_transport`): mean^(1/p) and
+    max^(1/p), in the units of the projected keys.  A NaN slice makes both NaN."""
+    if p not in (1, 2):
+        raise ValueError("p must be 1 or 2, got %r" % (p,))
+    s = np.asarray(slices, dtype=np.float64).reshape(-1)
+    if s.size < 1:
+        raise ValueError("no slices")
+    if np.isnan(s).any():
+        return float("nan"), float("nan")
+    return float(s.mean() ** (1.0 / p)), float(s.max() ** (1.0 / p))
+
+
+def check_transport_options(p=2, directions=64, seed=0, m=None, n=None):
+    """ValueError unless p is 1 or 2, 1 <= directions <= 65535, seed is an integer >= 0 and (where given) both sets have
+    1 .. TRANSPORT_MAX_N points."""
+    import nfisam_hip as _nh
+    if p not in (1, 2):
+        raise ValueError("p must be 1 or 2, got %r" % (p,))
+    if not isinstance(directions, (int, np.integer)) or not 1 <= int(directions) <= 65535:
+        raise ValueError("directions must be an integer in 1..65535, got %r" % (directions,))
+    if not isinstance(seed, (int, np.integer)) or int(seed) < 0:
+        raise ValueError("seed must be an integer >= 0, got %r" % (seed,))
+    for name, k in (("m", m), ("n", n)):
+        if k is not None and not 1 <= int(k) <= _nh.TRANSPORT_MAX_N:
+            raise ValueError("%s = %d points: a set holds 1..%d (both key lists are sorted in LDS)" % (name, int(k), _nh.TRANSPORT_MAX_N))
+
+
+def transport_entries(pairs, flags):
+    """[(xcols, ycols)] and the circular flags of x's columns -> [(xrows, yrows, kind)]: a column becomes one entry of kind 0,
+    a circular column two entries that name it, its cosine (kind 1) and its sine (kind 2) -- the chord embedding."""
+    out = []
+    for xc, yc in pairs:
+        xr, yr, kd = [], [], []
+        for a, b in zip(xc.tolist(), yc.tolist()):
+            kinds = (1, 2) if flags[a] else (0,)
+            xr += [a] * len(kinds); yr += [b] * len(kinds); kd += kinds
+        out.append((np.asarray(xr, dtype=np.int64), np.asarray(yr, dtype=np.int64), np.asarray(kd, dtype=np.uint8)))
+    return out
+
+
+def transport_tables(entries, directions: int, seed: int, axes, scale=None) -> dict:
+    """The tables of one launch for the blocks `entries` ([(xrows, yrows, kind)]): block b gets
+    `transport_directions(its entries, directions, seed)`; for a block with `axes` (one flag, or one per block) every entry is
+    also a one-entry block of its own with the direction [1.0] -- a basis vector: the exact 1-D distance of that entry --
+    appended to the table and reading the block's own entries.  scale [rows of x] or None.
+    -> dict: blocks (TRANSPORT_BLOCK_DTYPE), xcols, ycols, kind (None when every entry is a value), scale (per entry or
+    None), dirs, main (number of blocks asked for), axis_at ({block: index of its first one-entry block})."""
+    import nfisam_hip as _nh
+    axes = [bool(axes)] * len(entries) if np.ndim(axes) == 0 else [bool(a) for a in axes]
+    if len(axes) != len(entries):
+        raise ValueError("axes: one flag, or one per block (%d), got %d" % (len(entries), len(axes)))
+    dims = [int(e[0].size) for e in entries]
+    cache, dirs, nd = {}, [], []
+    for d in dims:
+        if d not in cache:
+            cache[d] = transport_directions(d, directions, seed)
+        dirs.append(cache[d].reshape(-1))
+        nd.append(cache[d].shape[0])
+    extra = sum(d for d, a in zip(dims, axes) if a)
+    if len(entries) + extra > 65535:
+        raise ValueError("%d blocks and %d axis entries: a launch holds at most 65535 blocks" % (len(entries), extra))
+    table = _nh.pack_transport_blocks(dims + [1] * extra, nd + [1] * extra)
+    axis_at, k = {}, len(entries)
+    for b, (d, a) in enumerate(zip(dims, axes)):
+        if a:
+            axis_at[b] = k
+            table["col_off"][k:k + d] = int(table["col_off"][b]) + np.arange(d)
+            k += d
+    xcols = np.concatenate([e[0] for e in entries]).astype(np.int32)
+    ycols = np.concatenate([e[1] for e in entries]).astype(np.int32)
+    kind = np.concatenate([e[2] for e in entries]).astype(np.uint8)
+    return dict(blocks=table, xcols=xcols, ycols=ycols, kind=kind if kind.any() else None,
+                scale=None if scale is None else np.asarray(scale, dtype=np.float64)[xcols],
+                dirs=np.concatenate(dirs + [np.ones(extra)]), main=len(entries), axis_at=axis_at)
+
+
+def transport_result(out, tab: dict, p: int) -> dict:
+    """The slices `out` of a launch over `transport_tables` -> dict: distance [main], max_sliced [main], slices (list of
+    arrays of W_p^p), axis (list: None, or the exact 1-D W_p of every entry of the block)."""
+    out = np.asarray(out, dtype=np.float64)
+    t = tab["blocks"]
+    slices = [out[int(t["out_off"][b]):int(t["out_off"][b]) + int(t["n_dirs"][b])].copy() for b in range(tab["main"])]
+    both = [wasserstein_from_slices(s, p) for s in slices]
+    axis = []
+    for b in range(tab["main"]):
+        k = tab["axis_at"].get(b)
+        axis.append(None if k is None else out[t["out_off"][k:k + int(t["d"][b])]] ** (1.0 / p))
+    return dict(distance=np.array([v[0] for v in both]), max_sliced=np.array([v[1] for v in both]), slices=slices, axis=axis)
+
+
+def _transport_front(x_width, y_width, m, n, blocks, p, directions, seed, scale, circular, axes):
+    """The checks of `sliced_wasserstein` and `sliced_wasserstein_t`, none of which needs a device -> the launch's tables."""
+    check_transport_options(p, directions, seed, m, n)
+    pairs = _block_pairs(blocks)
+    for b, (xc, yc) in enumerate(pairs):
+        if xc.min() < 0 or xc.max() >= x_width or yc.min() < 0 or yc.max() >= y_width:
+            raise ValueError("block %d names a column outside its sample set" % b)
+    flags = _column_flags(circular, x_width)
+    if scale is not None:
+        scale = np.asarray(scale, dtype=np.float64).reshape(-1)
+        if scale.size != x_width or not np.all(np.isfinite(scale)):
+            raise ValueError("scale: one finite value per column of x (%d), got %d" % (x_width, scale.size))
+    return transport_tables(transport_entries(pairs, flags), int(directions), int(seed), axes, scale)
+
+
+def sliced_wasserstein_t(Xt, Yt, blocks, p=2, directions=64, seed=0, scale=None, circular=None, axes=False, checked=False) -> dict:
+    """`sliced_wasserstein` on the COLUMN-major device matrices Xt [x_cols, m], Yt [y_cols, n] (contiguous float32, used in
+    place: what the tree walk wrote); a column is a row of them.  `checked`: `blocks` is what `transport_tables` returned."""
+    import nfisam_hip as _nh
+    if checked:
+        tab = blocks
+    else:
+        if not hasattr(Xt, "shape") or not hasattr(Yt, "shape") or len(Xt.shape) != 2 or len(Yt.shape) != 2:
+            raise ValueError("Xt and Yt must be [columns, points]")
+        tab = _transport_front(int(Xt.shape[0]), int(Yt.shape[0]), int(Xt.shape[1]), int(Yt.shape[1]), blocks, p, directions, seed,
+                               scale, circular, axes)
+    out = _nh.sliced_transport_t(Xt, Yt, tab["blocks"], tab["xcols"], tab["ycols"], tab["dirs"], p, tab["kind"], tab["scale"])
+    return transport_result(out.cpu().numpy(), tab, p)
+
+
+def sliced_wasserstein(x, y, blocks, p=2, directions=64, seed=0, scale=None, circular=None, axes=False, device=None) -> dict:
+    """The sliced Wasserstein distance W_p between the sample sets x [m, x_cols] and y [n, y_cols] (numpy or torch) restricted
+    to each of `blocks`, all blocks and directions in ONE device launch (nfisam_hip.sliced_transport: float32 points, float64
+    keys): how far, in the columns' own units, x must be moved to become y.  It needs no bandwidth, keeps growing with the
+    separation where the MMD saturates, and sees a missing mode as mass times distance.
+
+    blocks: as `mmd_blocks` takes them (column lists, or (xcols, ycols) pairs).  p: 1 or 2.  A block of d entries is
+    projected on `transport_directions(d, directions, seed)` -- the directions depend on (seed, d) alone; a one-entry block
+    has the single direction 1 and its value is the exact 1-D distance.  scale [x_cols]: factor on a column's values (and its
+    partner's in y).  circular [x_cols]: columns that are angles; each becomes two entries, its cosine and its sine (the
+    chord embedding: continuous across +-pi, the radian difference for small differences).  axes: also the exact 1-D W_p of
+    every entry of every block (basis-vector directions, in the same launch).  At most 8192 points per set.
+    -> dict: distance [n_blocks] = (mean of the slices)^(1/p), max_sliced [n_blocks] = (max of the slices)^(1/p), slices
+    (list of arrays: W_p^p per direction), axis (list: None, or with `axes` the per-entry distances).  There is no CPU path."""
+    import nfisam_hip as _nh
+    if np.ndim(x) != 2 or np.ndim(y) != 2:
+        raise ValueError("x and y must be [points, columns]")
+    tab = _transport_front(int(x.shape[1]), int(y.shape[1]), int(x.shape[0]), int(y.shape[0]), blocks, p, directions, seed, scale,
+                           circular, axes)
+    out = _nh.sliced_transport(x, y, tab["blocks"], tab["xcols"], tab["ycols"], tab["dirs"], p, tab["kind"], tab["scale"],
+                               device=device)
+    return transport_result(out.cpu().numpy(), tab, p)
 
 
 # ---- what a sample set says: means, covariances, quantiles on the device (nfisam_sample_moments / nfisam_sample_quantiles) ----
