@@ -897,8 +897,9 @@ def factor_graph_log_density_t(terms: np.ndarray, St, device, per_factor=False, 
 # Every binding below comes as NAME(X [n, cols], ..., device), which makes every check on a row-major tensor or array before
 # the device is touched and hands the transposed copy on, and as NAME_t(Xt [rows, n], ..., checked=True), which works on the
 # column-major device matrix in place.  A new evaluator is written from these helpers (csrc/sample_common.h on the device
-# side): the two fronts, the block-table checks, `_f64` for the weights, which go the plain way, and `_upload_named` for
-# everything small -- ONE `upload` per call for whatever is on the host, every result taken by name, whatever form it came in.
+# side): the two fronts (`_two_set_front` / `_two_set_upload` where two sample sets meet), the block-table checks, `_f64` for
+# the weights, which go the plain way, and `_upload_named` for everything small -- ONE `upload` per call for whatever is on the
+# host, every result taken by name, whatever form it came in.
 def _row_major_front(what, device, **mats):
     """The head of the row-major binding `what`: -> the device (default: the first matrix's own, or "cuda").  RuntimeError
     unless that is a ROCm device, ValueError unless every matrix is a 2-D tensor or array.  Nothing is copied yet: `_columns`
@@ -929,6 +930,25 @@ def _column_major_front(name, t):
     if t.ndim != 2 or t.dtype != torch.float32 or not t.is_contiguous():
         raise ValueError("%s must be a contiguous float32 [rows, points] tensor" % name)
     return int(t.shape[0]), int(t.shape[1])
+
+
+def _two_set_front(names, At, Bt, same=False):
+    """The head of a column-major binding over two sets, `names` their arguments' names: both pass `_column_major_front` and
+    lie on one device; with `same`, Bt None is At -> (Bt, a_rows, m, b_rows, n)."""
+    a_rows, m = _column_major_front(names[0], At)
+    if same and Bt is None:
+        Bt = At
+    b_rows, n = _column_major_front(names[1], Bt)
+    if At.device != Bt.device:
+        raise ValueError("%s and %s must be on the same device" % tuple(names))
+    return Bt, a_rows, m, b_rows, n
+
+
+def _two_set_upload(device, blocks, names, acols, bcols, **per_entry):
+    """What such a binding stages, in ONE `upload`: the contiguous table `blocks`, the two column lists as int32 under `names`
+    and the per-entry arrays -> ({name: tensor on `device`}, the number of entries)."""
+    ac, bc = np.asarray(acols, dtype=np.int32), np.asarray(bcols, dtype=np.int32)
+    return _upload_named(device, blocks=_table_bytes(blocks), **{names[0]: ac, names[1]: bc}, **per_entry), int(ac.size)
 
 
 def _f64(a, device):
@@ -1023,6 +1043,20 @@ def _check_bandwidths(blocks):
         raise ValueError("block %d: inv_two_sigma2 must be positive and finite" % int(np.argmin(ok)))
 
 
+def _check_finite(name, a):
+    """ValueError unless the optional host array `a` holds finite values alone."""
+    if a is not None and not np.all(np.isfinite(np.asarray(a, dtype=np.float64))):
+        raise ValueError("%s must be finite" % name)
+
+
+def _consecutive(dims, dtype):
+    """-> (dims as int64 [n_blocks], the zeroed table of `dtype` with d = dims and col_off = the blocks one after another)."""
+    dims = np.asarray(dims, dtype=np.int64).reshape(-1)
+    t = np.zeros(dims.size, dtype=dtype)
+    t["d"], t["col_off"] = dims, np.cumsum(dims) - dims
+    return dims, t
+
+
 def _check_rows(cols):
     """Every row of the column lists `cols` ({name: (list, rows of its matrix)}) inside its matrix."""
     for name, (c, rows) in cols.items():
@@ -1059,10 +1093,7 @@ assert MMD_BLOCK_DTYPE.itemsize == C.sizeof(MmdBlock)
 
 def pack_mmd_blocks(dims, sigmas) -> np.ndarray:
     """The block table (numpy MMD_BLOCK_DTYPE) of consecutive blocks of `dims` entries with kernel bandwidths `sigmas`."""
-    dims = np.asarray(dims, dtype=np.int64).reshape(-1)
-    t = np.zeros(dims.size, dtype=MMD_BLOCK_DTYPE)
-    t["d"] = dims
-    t["col_off"] = np.cumsum(dims) - dims
+    dims, t = _consecutive(dims, MMD_BLOCK_DTYPE)
     t["inv_two_sigma2"] = 1.0 / (2.0 * np.asarray(sigmas, dtype=np.float64).reshape(-1) ** 2)
     return t
 
@@ -1074,8 +1105,7 @@ def check_mmd_blocks(blocks: np.ndarray, xcols, ycols, x_rows: int, y_rows: int,
     _check_table_layout(blocks, MMD_BLOCK_DTYPE, "MMD_BLOCK_DTYPE", cols, dict(scale=scale, wrap=wrap))
     _check_bandwidths(blocks)
     _check_rows(cols)
-    if scale is not None and not np.all(np.isfinite(np.asarray(scale, dtype=np.float64))):
-        raise ValueError("scale must be finite")
+    _check_finite("scale", scale)
 
 
 def mmd_sums(X, Y, blocks: np.ndarray, xcols, ycols, scale=None, wrap=None, device=None):
@@ -1092,9 +1122,7 @@ def mmd_sums(X, Y, blocks: np.ndarray, xcols, ycols, scale=None, wrap=None, devi
 def mmd_sums_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, scale=None, wrap=None, checked=False):
     """`mmd_sums` on the COLUMN-major matrices Xt [x_rows, m], Yt [y_rows, n] (contiguous float32 device tensors, used in
     place): what the tree walk wrote."""
-    (x_rows, m), (y_rows, n) = _column_major_front("Xt", Xt), _column_major_front("Yt", Yt)
-    if Xt.device != Yt.device:
-        raise ValueError("Xt and Yt must be on the same device")
+    Yt, x_rows, m, y_rows, n = _two_set_front(("Xt", "Yt"), Xt, Yt)
     device = Xt.device
     if m < 1 or n < 1:
         raise ValueError("both sample sets need at least one point")
@@ -1102,9 +1130,8 @@ def mmd_sums_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, scale=None, wrap=None, 
         check_mmd_blocks(blocks, xcols, ycols, x_rows, y_rows, scale, wrap)
     nb = int(blocks.shape[0])
     blocks = np.ascontiguousarray(blocks)
-    xc, yc = np.asarray(xcols, dtype=np.int32), np.asarray(ycols, dtype=np.int32)
     with torch.cuda.device(device):
-        dev = _upload_named(device, blocks=_table_bytes(blocks), xcols=xc, ycols=yc, scale=_entry_f64(scale), wrap=_flags(wrap))
+        dev, ne = _two_set_upload(device, blocks, ("xcols", "ycols"), xcols, ycols, scale=_entry_f64(scale), wrap=_flags(wrap))
         count = int(lib().nfisam_sample_mmd_scratch_count(m, n, nb))
         if count < 1:
             raise ValueError("mmd_sums: %d x %d points in %d blocks exceed the grid" % (m, n, nb))
@@ -1112,7 +1139,7 @@ def mmd_sums_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, scale=None, wrap=None, 
         scratch = torch.empty(count, dtype=torch.float64, device=device)
         sums = torch.empty(nb, 3, dtype=torch.float64, device=device)
         _check(lib().nfisam_sample_mmd(_ptr(Xt), x_rows, m, _ptr(Yt), y_rows, n, blocks.ctypes.data_as(C.c_void_p),
-                                       _ptr(dev["blocks"]), nb, _ptr(dev["xcols"]), _ptr(dev["ycols"]), int(xc.size),
+                                       _ptr(dev["blocks"]), nb, _ptr(dev["xcols"]), _ptr(dev["ycols"]), ne,
                                        _ptr(dev["scale"]), _ptr(dev["wrap"]), _ptr(sums), _ptr(scratch), _stream()),
                "nfisam_sample_mmd")
     return sums
@@ -1130,14 +1157,12 @@ def pack_transport_blocks(dims, n_dirs) -> np.ndarray:
     """The block table (numpy TRANSPORT_BLOCK_DTYPE) of consecutive blocks of `dims` entries with `n_dirs` directions each
     (one count, or one per block): block b's directions are the doubles dir_off .. dir_off + n_dirs * d of the direction
     array, [n_dirs, d] row-major, and its slices out_off .. out_off + n_dirs of the result, both in table order."""
-    dims = np.asarray(dims, dtype=np.int64).reshape(-1)
+    dims, t = _consecutive(dims, TRANSPORT_BLOCK_DTYPE)
     nd = np.broadcast_to(np.asarray(n_dirs, dtype=np.int64).reshape(-1), dims.shape) if np.size(n_dirs) == 1 else \
         np.asarray(n_dirs, dtype=np.int64).reshape(-1)
     if nd.shape != dims.shape:
         raise ValueError("n_dirs: one count, or one per block (%d), got %d" % (dims.size, nd.size))
-    t = np.zeros(dims.size, dtype=TRANSPORT_BLOCK_DTYPE)
-    t["d"], t["n_dirs"] = dims, nd
-    t["col_off"] = np.cumsum(dims) - dims
+    t["n_dirs"] = nd
     t["dir_off"] = np.cumsum(dims * nd) - dims * nd
     t["out_off"] = np.cumsum(nd) - nd
     return t
@@ -1167,10 +1192,8 @@ def check_transport_blocks(blocks: np.ndarray, xcols, ycols, x_rows: int, y_rows
     if np.any(ooff < 0):
         raise ValueError("block %d: out_off must be >= 0" % int(np.argmax(ooff < 0)))
     _check_disjoint(ooff, nd, "every slice is stored once")
-    if not np.all(np.isfinite(dirs)):
-        raise ValueError("dirs must be finite")
-    if scale is not None and not np.all(np.isfinite(np.asarray(scale, dtype=np.float64))):
-        raise ValueError("scale must be finite")
+    _check_finite("dirs", dirs)
+    _check_finite("scale", scale)
     return int((ooff + nd).max())
 
 
@@ -1200,25 +1223,22 @@ def sliced_transport(X, Y, blocks: np.ndarray, xcols, ycols, dirs, p=2, kind=Non
 def sliced_transport_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, dirs, p=2, kind=None, scale=None, checked=False):
     """`sliced_transport` on the COLUMN-major matrices Xt [x_rows, m], Yt [y_rows, n] (contiguous float32 device tensors, used
     in place): what the tree walk wrote."""
-    (x_rows, m), (y_rows, n) = _column_major_front("Xt", Xt), _column_major_front("Yt", Yt)
-    if Xt.device != Yt.device:
-        raise ValueError("Xt and Yt must be on the same device")
+    Yt, x_rows, m, y_rows, n = _two_set_front(("Xt", "Yt"), Xt, Yt)
     device = Xt.device
     _check_transport_sizes(m, n, p)
     if not checked:
         check_transport_blocks(blocks, xcols, ycols, x_rows, y_rows, dirs, kind, scale)
     nb = int(blocks.shape[0])
     blocks = np.ascontiguousarray(blocks)
-    xc, yc = np.asarray(xcols, dtype=np.int32), np.asarray(ycols, dtype=np.int32)
     dirs = np.ascontiguousarray(dirs, dtype=np.float64)
     n_out = int((blocks["out_off"].astype(np.int64) + blocks["n_dirs"]).max())
     with torch.cuda.device(device):
-        dev = _upload_named(device, blocks=_table_bytes(blocks), xcols=xc, ycols=yc, kind=_flags(kind), scale=_entry_f64(scale),
-                            dirs=dirs)
+        dev, ne = _two_set_upload(device, blocks, ("xcols", "ycols"), xcols, ycols, kind=_flags(kind), scale=_entry_f64(scale),
+                                  dirs=dirs)
         out = torch.full((n_out,), float("nan"), dtype=torch.float64, device=device)
         _check(lib().nfisam_sample_sliced_transport(_ptr(Xt), x_rows, m, _ptr(Yt), y_rows, n, blocks.ctypes.data_as(C.c_void_p),
                                                     _ptr(dev["blocks"]), nb, _ptr(dev["xcols"]), _ptr(dev["ycols"]),
-                                                    _ptr(dev["kind"]), _ptr(dev["scale"]), int(xc.size), _ptr(dev["dirs"]),
+                                                    _ptr(dev["kind"]), _ptr(dev["scale"]), ne, _ptr(dev["dirs"]),
                                                     C.c_longlong(int(dirs.size)), int(p), _ptr(out), C.c_longlong(n_out),
                                                     _stream()), "nfisam_sample_sliced_transport")
     return out
@@ -1304,9 +1324,7 @@ def mmd_perm_sums_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, labels, scale=None
     """`mmd_perm_sums` on the COLUMN-major matrices Xt [x_rows, m], Yt [y_rows, n] (contiguous float32 device tensors, used in
     place).  More than MMD_PERM_MAX permutations, or more than fit MMD_PERM_SCRATCH_BYTES of strip partials, are launched in
     chunks (multiples of 256) and concatenated: a permutation's numbers do not depend on the split."""
-    (x_rows, m), (y_rows, n) = _column_major_front("Xt", Xt), _column_major_front("Yt", Yt)
-    if Xt.device != Yt.device:
-        raise ValueError("Xt and Yt must be on the same device")
+    Yt, x_rows, m, y_rows, n = _two_set_front(("Xt", "Yt"), Xt, Yt)
     device = Xt.device
     P = _perm_count(labels, n_perms)
     if not checked:
@@ -1314,7 +1332,6 @@ def mmd_perm_sums_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, labels, scale=None
         check_perm_labels(labels, m, n, P)
     nb = int(blocks.shape[0])
     blocks = np.ascontiguousarray(blocks)
-    xc, yc = np.asarray(xcols, dtype=np.int32), np.asarray(ycols, dtype=np.int32)
     packed = pack_perm_labels(labels) if labels.dtype == np.bool_ else np.ascontiguousarray(labels)
     per_perm = int(lib().nfisam_sample_mmd_perm_scratch_count(m, n, nb, MMD_PERM_CHUNK)) // MMD_PERM_CHUNK * 8
     if per_perm < 1:
@@ -1323,7 +1340,7 @@ def mmd_perm_sums_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, labels, scale=None
     step = min(step, MMD_PERM_MAX)
     sums = torch.empty(nb, P, 3, dtype=torch.float64, device=device)
     with torch.cuda.device(device):
-        dev = _upload_named(device, blocks=_table_bytes(blocks), xcols=xc, ycols=yc, scale=_entry_f64(scale), wrap=_flags(wrap))
+        dev, ne = _two_set_upload(device, blocks, ("xcols", "ycols"), xcols, ycols, scale=_entry_f64(scale), wrap=_flags(wrap))
         for p0 in range(0, P, step):
             cnt = min(step, P - p0)
             words = np.ascontiguousarray(packed[:, p0 // 64:(p0 + cnt + 63) // 64]).view(np.int64)
@@ -1334,7 +1351,7 @@ def mmd_perm_sums_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, labels, scale=None
             scratch = torch.empty(count, dtype=torch.float64, device=device)
             out = sums if cnt == P else torch.empty(nb, cnt, 3, dtype=torch.float64, device=device)
             _check(lib().nfisam_sample_mmd_perm(_ptr(Xt), x_rows, m, _ptr(Yt), y_rows, n, blocks.ctypes.data_as(C.c_void_p),
-                                                _ptr(dev["blocks"]), nb, _ptr(dev["xcols"]), _ptr(dev["ycols"]), int(xc.size),
+                                                _ptr(dev["blocks"]), nb, _ptr(dev["xcols"]), _ptr(dev["ycols"]), ne,
                                                 _ptr(dev["scale"]), _ptr(dev["wrap"]), _ptr(lab), cnt, _ptr(out), _ptr(scratch),
                                                 _stream()), "nfisam_sample_mmd_perm")
             if out is not sums:
@@ -1879,10 +1896,7 @@ assert MOMENT_BLOCK_DTYPE.itemsize == C.sizeof(MomentBlock)
 def pack_moment_blocks(dims) -> np.ndarray:
     """The block table (numpy MOMENT_BLOCK_DTYPE) of consecutive blocks of `dims` entries, their d x d matrices one after
     another in `cov`."""
-    dims = np.asarray(dims, dtype=np.int64).reshape(-1)
-    t = np.zeros(dims.size, dtype=MOMENT_BLOCK_DTYPE)
-    t["d"] = dims
-    t["col_off"] = np.cumsum(dims) - dims
+    dims, t = _consecutive(dims, MOMENT_BLOCK_DTYPE)
     t["cov_off"] = np.cumsum(dims * dims) - dims * dims
     return t
 
@@ -2169,10 +2183,7 @@ KNN_KEYS = ("dist", "idx", "log_sum", "n_used")
 def pack_knn_blocks(dims, radius_rows=None) -> np.ndarray:
     """The block table (numpy KNN_BLOCK_DTYPE) of consecutive blocks of `dims` entries; radius_rows: the row of `radius` each
     block's queries take in `sample_ball_count` (default: all 0)."""
-    dims = np.asarray(dims, dtype=np.int64).reshape(-1)
-    t = np.zeros(dims.size, dtype=KNN_BLOCK_DTYPE)
-    t["d"] = dims
-    t["col_off"] = np.cumsum(dims) - dims
+    dims, t = _consecutive(dims, KNN_BLOCK_DTYPE)
     if radius_rows is not None:
         t["radius_row"] = np.asarray(radius_rows, dtype=np.int64).reshape(-1)
     return t
@@ -2185,9 +2196,8 @@ def check_knn_blocks(blocks: np.ndarray, xcols, ycols, x_rows: int, y_rows: int,
     cols = {"xcols": (xcols, x_rows), "ycols": (ycols, y_rows)}
     _check_table_layout(blocks, KNN_BLOCK_DTYPE, "KNN_BLOCK_DTYPE", cols, dict(scale=scale, wrap=wrap), KNN_MAX_D)
     _check_rows(cols)
-    if scale is not None and not (torch.is_tensor(scale) and scale.is_cuda):     # (a device tensor is taken as it is)
-        if not np.all(np.isfinite(np.asarray(scale, dtype=np.float64))):
-            raise ValueError("scale must be finite")
+    if not (torch.is_tensor(scale) and scale.is_cuda):                            # (a device tensor is taken as it is)
+        _check_finite("scale", scale)
     if n_radius is not None:
         rr = blocks["radius_row"].astype(np.int64)
         bad = (rr < 0) | (rr >= int(n_radius))
@@ -2209,22 +2219,6 @@ def check_knn_args(m: int, n: int, k=1, norm="max", exclude_self=False) -> int:
     if exclude_self and m != n:
         raise ValueError("exclude_self needs the two sets to be one (m = %d, n = %d)" % (m, n))
     return KNN_NORMS[norm]
-
-
-def _knn_front(what, Xt, Yt):
-    """The head of the two column-major bindings: Yt None is Xt -> (Yt, x_rows, m, y_rows, n)."""
-    x_rows, m = _column_major_front("Xt", Xt)
-    if Yt is None:
-        Yt = Xt
-    y_rows, n = _column_major_front("Yt", Yt)
-    if Xt.device != Yt.device:
-        raise ValueError("Xt and Yt must be on the same device")
-    return Yt, x_rows, m, y_rows, n
-
-
-def _knn_upload(device, blocks, xcols, ycols, scale, wrap):
-    xc, yc = np.asarray(xcols, dtype=np.int32), np.asarray(ycols, dtype=np.int32)
-    return _upload_named(device, blocks=_table_bytes(blocks), xcols=xc, ycols=yc, scale=_entry_f64(scale), wrap=_flags(wrap)), int(xc.size)
 
 
 def sample_knn(X, Y, blocks: np.ndarray, xcols, ycols, k=4, norm="max", scale=None, wrap=None, exclude_self=False, device=None):
@@ -2251,7 +2245,7 @@ def sample_knn_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, k=4, norm="max", scal
     """`sample_knn` on the COLUMN-major matrices Xt [x_rows, m], Yt [y_rows, n] (contiguous float32 device tensors, used in
     place; Yt None: Xt): what the tree walk wrote.  `checked` skips the table and argument checks (the caller has made them);
     `out`: the dict of an earlier call with the same shapes, written in place."""
-    Yt, x_rows, m, y_rows, n = _knn_front("sample_knn", Xt, Yt)
+    Yt, x_rows, m, y_rows, n = _two_set_front(("Xt", "Yt"), Xt, Yt, same=True)
     if not checked:
         check_knn_blocks(blocks, xcols, ycols, x_rows, y_rows, scale, wrap)
         check_knn_args(m, n, k, norm, exclude_self)
@@ -2265,7 +2259,7 @@ def sample_knn_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, k=4, norm="max", scal
                 raise ValueError("out[%r] must be a contiguous %s tensor of shape %s on %s" % (key, dt, shape, device))
     blocks = np.ascontiguousarray(blocks)
     with torch.cuda.device(device):
-        dev, ne = _knn_upload(device, blocks, xcols, ycols, scale, wrap)
+        dev, ne = _two_set_upload(device, blocks, ("xcols", "ycols"), xcols, ycols, scale=_entry_f64(scale), wrap=_flags(wrap))
         res = out if out is not None else {key: torch.empty(shape, dtype=dt, device=device) for key, (shape, dt) in shapes.items()}
         _check(lib().nfisam_sample_knn(_ptr(Xt), x_rows, m, _ptr(Yt), y_rows, n, C.c_int(1 if exclude_self else 0),
                                        blocks.ctypes.data_as(C.c_void_p), _ptr(dev["blocks"]), nb, _ptr(dev["xcols"]),
@@ -2300,7 +2294,7 @@ def sample_ball_count_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, radius, norm="
     """`sample_ball_count` on the COLUMN-major matrices Xt [x_rows, m], Yt [y_rows, n] (Yt None: Xt); radius: a contiguous
     float64 [n_radius, m] tensor on their device (rows of a `sample_knn_t` result's dist, for instance).  `out`: an int32
     [n_blocks, m] device tensor written in place."""
-    Yt, x_rows, m, y_rows, n = _knn_front("sample_ball_count", Xt, Yt)
+    Yt, x_rows, m, y_rows, n = _two_set_front(("Xt", "Yt"), Xt, Yt, same=True)
     if not torch.is_tensor(radius) or not radius.is_cuda:
         raise RuntimeError("radius must be a tensor on a ROCm device (no CPU path exists)")
     if radius.ndim != 2 or radius.dtype != torch.float64 or not radius.is_contiguous() or int(radius.shape[1]) != m or \
@@ -2316,7 +2310,7 @@ def sample_ball_count_t(Xt, Yt, blocks: np.ndarray, xcols, ycols, radius, norm="
         raise ValueError("out must be a contiguous int32 tensor of shape %s on %s" % ((nb, m), device))
     blocks = np.ascontiguousarray(blocks)
     with torch.cuda.device(device):
-        dev, ne = _knn_upload(device, blocks, xcols, ycols, scale, wrap)
+        dev, ne = _two_set_upload(device, blocks, ("xcols", "ycols"), xcols, ycols, scale=_entry_f64(scale), wrap=_flags(wrap))
         count = out if out is not None else torch.empty(nb, m, dtype=torch.int32, device=device)
         _check(lib().nfisam_sample_ball_count(_ptr(Xt), x_rows, m, _ptr(Yt), y_rows, n, C.c_int(1 if exclude_self else 0),
                                               blocks.ctypes.data_as(C.c_void_p), _ptr(dev["blocks"]), nb, _ptr(dev["xcols"]),
@@ -2343,12 +2337,11 @@ def pack_density_blocks(dims, whiten, col_off=None) -> np.ndarray:
     matrix W with W H W' = I for its bandwidth matrix H (inv(cholesky(H)); the upper triangle is not read); log_norm =
     sum_r log W_rr - d/2 log(2 pi) is formed here.  col_off: each block's first entry (default: consecutive blocks) -- blocks
     may share entries, which is how bandwidth candidates of one column set go into one launch."""
-    dims = np.asarray(dims, dtype=np.int64).reshape(-1)
+    dims, t = _consecutive(dims, DENSITY_BLOCK_DTYPE)
     if len(whiten) != dims.size:
         raise ValueError("one whitening matrix per block (%d), got %d" % (dims.size, len(whiten)))
-    t = np.zeros(dims.size, dtype=DENSITY_BLOCK_DTYPE)
-    t["d"] = dims
-    t["col_off"] = np.cumsum(dims) - dims if col_off is None else np.asarray(col_off, dtype=np.int64).reshape(-1)
+    if col_off is not None:
+        t["col_off"] = np.asarray(col_off, dtype=np.int64).reshape(-1)
     for b, (d, W) in enumerate(zip(dims, whiten)):
         W = np.asarray(W, dtype=np.float64)
         if not 1 <= d <= DENSITY_MAX_D or W.shape != (d, d):
@@ -2431,12 +2424,7 @@ def sample_density_t(Qt, Xt, blocks: np.ndarray, qcols, xcols, wrap=None, log_w=
     in place; Xt None: Qt): what the tree walk wrote.  log_w: None or a float64 [n] tensor on their device (-inf: a zero
     weight) with log_w_sum the log of the weights' sum (None: formed on the device); or `weights`, from which both are formed
     on the device (`density_log_weights`).  `checked` skips the table, argument and weight checks (the caller has made them)."""
-    q_rows, m = _column_major_front("Qt", Qt)
-    if Xt is None:
-        Xt = Qt
-    x_rows, n = _column_major_front("Xt", Xt)
-    if Qt.device != Xt.device:
-        raise ValueError("Qt and Xt must be on the same device")
+    Xt, q_rows, m, x_rows, n = _two_set_front(("Qt", "Xt"), Qt, Xt, same=True)
     device = Qt.device
     if log_w is not None and weights is not None:
         raise ValueError("give log_w or weights, not both")
@@ -2449,9 +2437,8 @@ def sample_density_t(Qt, Xt, blocks: np.ndarray, qcols, xcols, wrap=None, log_w=
         weights = _check_weights(weights, n)
     nb = int(blocks.shape[0])
     blocks = np.ascontiguousarray(blocks)
-    qc, xc = np.asarray(qcols, dtype=np.int32), np.asarray(xcols, dtype=np.int32)
     with torch.cuda.device(device):
-        dev = _upload_named(device, blocks=_table_bytes(blocks), qcols=qc, xcols=xc, wrap=_flags(wrap))
+        dev, ne = _two_set_upload(device, blocks, ("qcols", "xcols"), qcols, xcols, wrap=_flags(wrap))
         if weights is not None:
             log_w, log_w_sum = density_log_weights(weights, n, device, checked=True)
         elif log_w is not None and log_w_sum is None:
@@ -2460,7 +2447,7 @@ def sample_density_t(Qt, Xt, blocks: np.ndarray, qcols, xcols, wrap=None, log_w=
         dens = torch.empty(nb, m, dtype=torch.float64, device=device) if want_density else None
         _check(lib().nfisam_sample_density(_ptr(Qt), q_rows, m, _ptr(Xt), x_rows, n, C.c_int(1 if exclude_self else 0),
                                            blocks.ctypes.data_as(C.c_void_p), _ptr(dev["blocks"]), nb, _ptr(dev["qcols"]),
-                                           _ptr(dev["xcols"]), int(qc.size), _ptr(dev["wrap"]), _ptr(log_w),
+                                           _ptr(dev["xcols"]), ne, _ptr(dev["wrap"]), _ptr(log_w),
                                            C.c_double(0.0 if log_w_sum is None else log_w_sum), _ptr(log_dens), _ptr(dens),
                                            _stream()), "nfisam_sample_density")
     return dict(log_density=log_dens, density=dens)

@@ -8,7 +8,11 @@ A mixin of `slam.NFiSAM.NFiSAM`: the walk (`posterior_launch`, `_post_columns`, 
 are reached through `self`.  Every public method goes through ONE front, `_eval_points`, which makes the checks that need no
 device and hands back an `EvalPoints` record; the kernels then read the record's column-major matrix `St` [total_dim, n]
 through the `_t` bindings of nfisam_hip.  A new evaluation starts with a call of the front, not with a copy of another's
-opening lines."""
+opening lines: `_eval_points` for its points (whose record also says which columns are headings: `flags`, `cols_of`),
+`_reference_front` for a reference sample set and the blocks of variables to compare, `_named` around a check that does
+not know the method's name, `_places` to name a per-block result."""
+import contextlib
+
 import numpy as np
 import torch
 
@@ -21,6 +25,15 @@ def _device():
     return "cuda:%d" % torch.cuda.current_device()
 
 
+@contextlib.contextmanager
+def _named(what):
+    """A ValueError raised inside is raised again with the method's name in front."""
+    try:
+        yield
+    except ValueError as e:
+        raise ValueError("%s: %s" % (what, e)) from None
+
+
 # how `_check_points` words its refusals: (a missing variable, a wrong shape, ragged rows, the letter of the row count)
 _SAMPLE_NOUNS = ("samples lack", "samples", "ragged samples", "n")
 _REFERENCE_NOUNS = ("the reference lacks", "reference samples", "ragged reference", "m")
@@ -31,12 +44,32 @@ class EvalPoints:
     -> first column), total_dim, table (the clique table when log q is evaluated, else None), device (the table's, else
     where a draw lies, else the current ROCm device: asked for on first use, so that every check comes before the device
     matters) and St, the column-major float32 device matrix [total_dim, rows] -- formed on first use and once: given values
-    are laid out on their side of the bus and copied over, a draw is the walk's matrix transposed."""
-    __slots__ = ("values", "rows", "pcol", "total_dim", "table", "_solver", "_device", "_St")
+    are laid out on their side of the bus and copied over, a draw is the walk's matrix transposed.  `cols_of(v)` are a
+    variable's columns, `flags` [total_dim] bool the heading columns (from the ordering's variables, formed on first use) and
+    `cols` the columns the ordering's variables take, ascending: THE answer to which columns are headings, no device."""
+    __slots__ = ("values", "rows", "pcol", "total_dim", "table", "_solver", "_device", "_St", "_flags")
 
     def __init__(self, solver, values, rows, pcol, total_dim, table):
         self.values, self.rows, self.pcol, self.total_dim, self.table = values, rows, pcol, total_dim, table
-        self._solver, self._device, self._St = solver, None, None
+        self._solver, self._device, self._St, self._flags = solver, None, None, None
+
+    def cols_of(self, v):
+        return np.arange(self.pcol[v], self.pcol[v] + v.dim)
+
+    @property
+    def flags(self):
+        if self._flags is None:
+            self._flags = np.zeros(self.total_dim, dtype=bool)
+            for v in self._solver._elimination_ordering:
+                self._flags[self.cols_of(v)] = [bool(c) for c in v.circular_dim_list]
+        return self._flags
+
+    @property
+    def cols(self):
+        used = np.zeros(self.total_dim, dtype=bool)
+        for v in self._solver._elimination_ordering:
+            used[self.cols_of(v)] = True
+        return np.flatnonzero(used)
 
     @property
     def device(self):
@@ -68,8 +101,37 @@ class EvalPoints:
     def over(self, St):
         """The same record over another matrix of the same layout (a copy to refine, a selection of its points)."""
         other = EvalPoints(self._solver, self.values, int(St.shape[1]), self.pcol, self.total_dim, self.table)
-        other._device, other._St = self.device, St
+        other._device, other._St, other._flags = self.device, St, self._flags
         return other
+
+
+class ReferenceSet:
+    """What `_reference_layout` returns: values ({variable: [m, dim] host array}), m, variables (in the order asked for), rcol
+    (variable -> first column of the set's own layout: the variables side by side), width, table (the blocks of variables to
+    compare: one per variable, until `_reference_front` puts its own there) and Y, the float32 matrix [m, width] -- formed
+    on first use and once, as `EvalPoints.St` is."""
+    __slots__ = ("values", "m", "variables", "rcol", "width", "table", "_Y")
+
+    def __init__(self, values, m, variables):
+        self.values, self.m, self.variables, self._Y = values, m, variables, None
+        self.rcol, self.width, self.table = {}, 0, [(v,) for v in variables]
+        for v in variables:
+            self.rcol[v] = self.width
+            self.width += v.dim
+
+    @property
+    def Y(self):
+        if self._Y is None:
+            self._Y = np.concatenate([self.values[v] for v in self.variables], axis=1).astype(np.float32)
+        return self._Y
+
+    def pairs(self, pts: EvalPoints, columns: str = "all"):
+        """`table` as column pairs -> [(xcols, ycols)] int64, one per block: rows of `pts.St` and the columns of `Y` they are
+        compared with; columns: "all", or "xy" for the first two of every variable."""
+        def take(v):
+            return np.arange(v.dim if columns == "all" else min(v.dim, 2))
+        return [(np.concatenate([pts.pcol[v] + take(v) for v in blk]), np.concatenate([self.rcol[v] + take(v) for v in blk]))
+                for blk in self.table]
 
 
 class PosteriorEvaluation:
@@ -131,6 +193,47 @@ class PosteriorEvaluation:
         if factors:
             self._joint_terms(pcol)
         return EvalPoints(self, values, rows, pcol, total_dim, self._posterior_table() if log_q else None)
+
+    @staticmethod
+    def _need_known(what: str, v, known):
+        """ValueError unless `v` is one of `known` (the elimination ordering's variables, or the assigned columns)."""
+        if v not in known:
+            raise ValueError("%s: variable %s is not in the elimination ordering" % (what, getattr(v, "name", v)))
+
+    def _reference_layout(self, what, reference, variables) -> ReferenceSet:
+        """A reference sample set's front: `reference` maps every one of `variables` to [m, dim] values (checked by
+        `_check_points` in the reference's words, brought to numpy) -> the record of its own column layout."""
+        values, m = self._check_points(reference, what, variables, _REFERENCE_NOUNS, host=True)
+        return ReferenceSet(values, m, list(variables))
+
+    def _reference_front(self, what, reference, variables, blocks, joint) -> ReferenceSet:
+        """What every grader against a reference set calls after `_eval_points`, in this order: `variables` default to those of
+        the ordering that `reference` holds and must not be empty, every variable named (in `blocks` too: further blocks, each a
+        tuple of variables) must be in the ordering and in `reference`, a block is non-empty and of compared variables, then
+        `_reference_layout` -> its record with table = the joint block (with `joint`), one block per variable, `blocks`."""
+        known = set(self._elimination_ordering)
+        variables = [v for v in self._elimination_ordering if v in reference] if variables is None else list(variables)
+        extra = [tuple(b) for b in blocks] if blocks is not None else []
+        if not variables:
+            raise ValueError("%s: no variable to compare (the reference holds none of the ordering's)" % what)
+        for v in variables + [v for b in extra for v in b]:
+            self._need_known(what, v, known)
+            if v not in reference:
+                raise ValueError("%s: the reference lacks variable %s" % (what, v.name))
+        for b in extra:
+            if not b or any(v not in variables for v in b):
+                raise ValueError("%s: a block is a non-empty tuple of compared variables" % what)
+        ref = self._reference_layout(what, reference, variables)
+        ref.table = ([tuple(variables)] if joint else []) + ref.table + extra
+        return ref
+
+    @staticmethod
+    def _places(a, variables, joint, item=float) -> dict:
+        """A vector with one value per block of `_reference_front`'s table under the names the graders return it by:
+        joint (None without `joint`), marginal {variable: value}, blocks [...]."""
+        k0 = 1 if joint else 0
+        return dict(joint=item(a[0]) if joint else None, marginal={v: item(a[k0 + i]) for i, v in enumerate(variables)},
+                    blocks=[item(x) for x in a[k0 + len(variables):]])
 
     # ---- the launches behind them: log q, log p, the score ---------------------------------------------------------------------
     def _joint_terms(self, pcol):
@@ -257,16 +360,7 @@ class PosteriorEvaluation:
         estimate (FactorGraphSolver.plot2d_MAP_rbt_only, src/slam/FactorGraphSolver.py:660-671).  -> variable -> [dim]."""
         return self.posterior_diagnostics(samples)["map_sample"]
 
-    # ---- what posterior_ksd, posterior_refine and map_refine share: the columns in use, their flags and spreads ----------------
-    def _column_flags(self, pts: EvalPoints):
-        """-> (flags [total_dim] bool: the heading columns, from the variables; cols: the columns the ordering's variables
-        take, ascending).  No device."""
-        flags, used = np.zeros(pts.total_dim, dtype=bool), np.zeros(pts.total_dim, dtype=bool)
-        for v in self._elimination_ordering:
-            flags[pts.pcol[v]:pts.pcol[v] + v.dim] = [bool(c) for c in v.circular_dim_list]
-            used[pts.pcol[v]:pts.pcol[v] + v.dim] = True
-        return flags, np.flatnonzero(used)
-
+    # ---- what posterior_ksd, posterior_refine and map_refine share: the spreads of the columns in use ----------------------------
     @staticmethod
     def _column_scale(pts: EvalPoints, flags, cols, standardise: bool):
         """-> scale [total_dim]: with `standardise` 1 / spread of every column of `cols` over the points of `pts`
@@ -322,7 +416,7 @@ class PosteriorEvaluation:
         if sigma is not None and not (np.isfinite(sigma) and sigma > 0):
             raise ValueError("%s: sigma must be positive and finite" % what)
         order = list(self._elimination_ordering)
-        flags, cols = self._column_flags(pts)
+        flags, cols = pts.flags, pts.cols
         scale = self._column_scale(pts, flags, cols, standardise)
         sig = float(np.sqrt(cols.size)) if sigma is None else float(sigma)
         precision = scale * scale / (sig * sig)
@@ -347,14 +441,12 @@ class PosteriorEvaluation:
         times its spread with `standardise` (`step_size` itself for a column without spread), else `step_size`."""
         from utils import Statistics as ST
         pts = self._eval_points(what, samples, n, factors=True, nonempty=True)
-        flags, cols = self._column_flags(pts)
+        flags, cols = pts.flags, pts.cols
         blocks = blocks_of(pts, cols)
-        try:
+        with _named(what):
             if np.ndim(step_size) != 0:
                 raise ValueError("step_size is one positive finite step")
             ST.check_refine_options(pts.total_dim, blocks, sigma, None, flags, steps, step_size)
-        except ValueError as e:
-            raise ValueError("%s: %s" % (what, e)) from None
         scale = self._column_scale(pts, flags, cols, bool(standardise))
         step = np.full(pts.total_dim, float(step_size))
         if standardise:
@@ -394,7 +486,7 @@ class PosteriorEvaluation:
             if kernel not in ("variable", "joint", None):
                 raise ValueError("%s: kernel must be 'variable', 'joint' or None, got %r" % (what, kernel))
             if kernel == "variable":
-                return [np.arange(pts.pcol[v], pts.pcol[v] + v.dim) for v in self._elimination_ordering]
+                return [pts.cols_of(v) for v in self._elimination_ordering]
             return [cols]
 
         pts, flags, cols, blocks, scale, step = self._refine_front(what, samples, n, steps, step_size, standardise, blocks_of,
@@ -500,9 +592,9 @@ class PosteriorEvaluation:
         what, every = "posterior_mcmc", independence_every
         count = not isinstance(every, bool) and isinstance(every, (int, np.integer)) and every >= 0
         pts = self._eval_points(what, samples, n, factors=True, log_q=bool(count and every > 0), nonempty=True)
-        flags, cols = self._column_flags(pts)
+        flags, cols = pts.flags, pts.cols
         order, pcol = list(self._elimination_ordering), pts.pcol
-        try:
+        with _named(what):
             if not count:
                 raise ValueError("independence_every must be an integer >= 0, got %r" % (every,))
             if np.ndim(step_size) != 0 or not (np.isfinite(step_size) and step_size > 0):
@@ -515,8 +607,6 @@ class PosteriorEvaluation:
             opt = ST.check_metropolis_options(pts.total_dim, steps, float(step_size), None, kernel, warmup, None, seed)
             if diagnostics:
                 ST.check_chain_options(pts.total_dim, opt["steps"], opt["warmup"], {}, least=4)
-        except ValueError as e:
-            raise ValueError("%s: %s" % (what, e)) from None
         scale = self._column_scale(pts, flags, cols, bool(standardise))
         h = np.zeros(pts.total_dim)
         h[cols] = float(step_size)
@@ -636,8 +726,8 @@ class PosteriorEvaluation:
         from utils import Statistics as ST
         what = "map_newton"
         pts = self._eval_points(what, samples, n, factors=True, nonempty=True)
-        flags, cols = self._column_flags(pts)
-        try:
+        flags, cols = pts.flags, pts.cols
+        with _named(what):
             if isinstance(top, bool) or int(top) != top or int(top) < 1:
                 raise ValueError("top must be an integer >= 1, got %r" % (top,))
             if np.ndim(damping) != 0:
@@ -645,8 +735,6 @@ class PosteriorEvaluation:
             opt = ST.check_newton_options(pts.total_dim, steps, 2 * int(cols.size) if cg_iters is None else cg_iters, rtol, damping,
                                           ST.NEWTON_GTOL if gtol is None else gtol,
                                           ST.NEWTON_BACKTRACKS if backtracks is None else backtracks, circular=flags)
-        except ValueError as e:
-            raise ValueError("%s: %s" % (what, e)) from None
         scale = self._column_scale(pts, flags, cols, bool(standardise))
         top = min(int(top), pts.rows)
         log_p = self._joint_launch(pts)
@@ -698,20 +786,16 @@ class PosteriorEvaluation:
             if len(p) != 2:
                 raise ValueError("%s: a pair is a tuple (a, b) of two variables" % what)
         for v in variables + [v for p in pairs for v in p]:
-            if v not in known:
-                raise ValueError("%s: variable %s is not in the elimination ordering" % (what, getattr(v, "name", v)))
-        flags, used = self._column_flags(pts)
+            self._need_known(what, v, known)
         want = sorted(set(pts.pcol[v] + c for v in variables + [v for p in pairs for v in p] for c in range(v.dim)))
-        try:
+        with _named(what):
             if isinstance(max_columns, bool) or int(max_columns) != max_columns or int(max_columns) < 1:
                 raise ValueError("max_columns must be an integer >= 1, got %r" % (max_columns,))
             if not want:
                 raise ValueError("no variable to summarise")
             if len(want) > int(max_columns):
                 raise ValueError("%d columns are requested, max_columns is %d" % (len(want), int(max_columns)))
-            opt = ST.check_newton_options(pts.total_dim, 0, 2 * int(used.size) if cg_iters is None else cg_iters, rtol)
-        except ValueError as e:
-            raise ValueError("%s: %s" % (what, e)) from None
+            opt = ST.check_newton_options(pts.total_dim, 0, 2 * int(pts.cols.size) if cg_iters is None else cg_iters, rtol)
         at = {c: j for j, c in enumerate(want)}
         work = pts.over(pts.St[:, :1].expand(pts.total_dim, len(want)).contiguous())
         Bt = torch.zeros(pts.total_dim, len(want), dtype=torch.float64, device=pts.device)
@@ -767,77 +851,38 @@ class PosteriorEvaluation:
         return self._mmd_result(t, mmd_from_sums(sums.cpu().numpy(), pts.rows, t["m"], estimator))
 
     def _mmd_tables(self, what, reference, samples, n, variables, blocks, columns, estimator, sigma, joint) -> dict:
-        """What `posterior_mmd` and `posterior_mmd_test` share: the option checks, the front, the reference set laid out side
-        by side and the block table (the joint block, one block per variable, the further blocks) -> dict: pts, Y [m, width]
-        float32, m, width, variables, joint, estimator, blocks (MMD_BLOCK_DTYPE), xcols, ycols, wrap [entries] uint8, flags
-        (wrap, or None when no entry is an angle).  Nothing is launched."""
-        from utils.Statistics import ESTIMATORS
-        if estimator not in ESTIMATORS:
-            raise ValueError("%s: estimator must be one of %s, got %r" % (what, ESTIMATORS, estimator))
+        """What `posterior_mmd` and `posterior_mmd_test` share: the option checks, the two fronts, then what is the MMD's own:
+        the estimator's least number of points, the bandwidths (`Statistics.mmd_bandwidths`) and the wrap flags -> dict: pts,
+        and of `_reference_front`'s record Y [m, width] float32, m, width, variables; joint, estimator, blocks (MMD_BLOCK_DTYPE),
+        xcols, ycols, wrap [entries] uint8, flags (wrap, or None when no entry is an angle).  Nothing is launched."""
+        from utils import Statistics as ST
+        if estimator not in ST.ESTIMATORS:
+            raise ValueError("%s: estimator must be one of %s, got %r" % (what, ST.ESTIMATORS, estimator))
         if columns not in ("xy", "all"):
             raise ValueError("%s: columns must be 'xy' or 'all', got %r" % (what, columns))
         pts = self._eval_points(what, samples, n)
-        rows, pcol = pts.rows, pts.pcol
-        known = set(self._elimination_ordering)
-        variables = [v for v in self._elimination_ordering if v in reference] if variables is None else list(variables)
-        extra = [tuple(b) for b in blocks] if blocks is not None else []
-        if not variables:
-            raise ValueError("%s: no variable to compare (the reference holds none of the ordering's)" % what)
-        for v in list(variables) + [v for b in extra for v in b]:
-            if v not in known:
-                raise ValueError("%s: variable %s is not in the elimination ordering" % (what, v.name))
-            if v not in reference:
-                raise ValueError("%s: the reference lacks variable %s" % (what, v.name))
-        for b in extra:
-            if not b or any(v not in variables for v in b):
-                raise ValueError("%s: a block is a non-empty tuple of compared variables" % what)
-        # the reference set: its own column layout, the requested variables side by side
-        ref, m = self._check_points(reference, what, variables, _REFERENCE_NOUNS, host=True)
-        rcol, width = {}, 0
-        for v in variables:
-            rcol[v] = width
-            width += v.dim
+        ref = self._reference_front(what, reference, variables, blocks, joint)
         need = 1 if estimator == "MMDb" else 2
-        if m < need or rows < need:
+        if ref.m < need or pts.rows < need:
             raise ValueError("%s: %s needs at least %d points in each set (reference %d, posterior %d)"
-                             % (what, estimator, need, m, rows))
-        Y = np.concatenate([ref[v] for v in variables], axis=1).astype(np.float32)
-
-        def cols_of(v):
-            return range(v.dim if columns == "all" else min(v.dim, 2))
-
-        table = ([tuple(variables)] if joint else []) + [(v,) for v in variables] + extra
-        xcols, ycols, wrap, dims = [], [], [], []
-        for blk in table:
-            k = 0
-            for v in blk:
-                circ = v.circular_dim_list
-                for c in cols_of(v):
-                    xcols.append(pcol[v] + c); ycols.append(rcol[v] + c); wrap.append(bool(circ[c]))
-                    k += 1
-            dims.append(k)
-        xcols, ycols, wrap = np.asarray(xcols, dtype=np.int32), np.asarray(ycols, dtype=np.int32), np.asarray(wrap, dtype=np.uint8)
-        dims = np.asarray(dims)
-        if sigma is None:
-            sig = np.ones(len(table)) if estimator == "mmd" else np.sqrt(dims.astype(np.float64))
-        else:
-            sig = np.broadcast_to(np.asarray(sigma, dtype=np.float64).reshape(-1), (len(table),)) if np.size(sigma) == 1 else \
-                np.asarray(sigma, dtype=np.float64).reshape(-1)
-            if sig.size != len(table) or not np.all(np.isfinite(sig) & (sig > 0)):
-                raise ValueError("%s: sigma is one positive bandwidth, or one per block (%d)" % (what, len(table)))
-        return dict(pts=pts, Y=Y, m=m, width=width, variables=variables, joint=joint, estimator=estimator,
+                             % (what, estimator, need, ref.m, pts.rows))
+        pairs = ref.pairs(pts, columns)
+        xcols, ycols = (np.concatenate(c).astype(np.int32) for c in zip(*pairs))
+        wrap = pts.flags[xcols].astype(np.uint8)
+        dims = [p[0].size for p in pairs]
+        if sigma is not None and np.size(sigma) == 1:           # (a list of one bandwidth is one bandwidth here)
+            sigma = np.asarray(sigma, dtype=np.float64).reshape(())
+        sig = ST.mmd_bandwidths(dims, estimator, sigma)
+        if sig.size != len(dims) or not np.all(np.isfinite(sig) & (sig > 0)):
+            raise ValueError("%s: sigma is one positive bandwidth, or one per block (%d)" % (what, len(dims)))
+        return dict(pts=pts, Y=ref.Y, m=ref.m, width=ref.width, variables=ref.variables, joint=joint, estimator=estimator,
                     blocks=_nh.pack_mmd_blocks(dims, sig), xcols=xcols, ycols=ycols, wrap=wrap, flags=wrap if wrap.any() else None)
 
-    @staticmethod
-    def _mmd_result(t: dict, val) -> dict:
+    def _mmd_result(self, t: dict, val) -> dict:
         """The values `val` [blocks of `_mmd_tables`] under the names `posterior_mmd` returns them by."""
-        variables, m, rows = t["variables"], t["m"], t["pts"].rows
-        k0 = 1 if t["joint"] else 0
-        marginal = {v: float(val[k0 + i]) for i, v in enumerate(variables)}
-        return dict(joint=float(val[0]) if t["joint"] else None, marginal=marginal,
-                    marginal_mean=float(np.mean(list(marginal.values()))),
-                    blocks=[float(x) for x in val[k0 + len(variables):]], floor=float(np.sqrt(1.0 / m + 1.0 / rows)),
-                    m=m, n=rows, estimator=t["estimator"])
+        m, rows, at = t["m"], t["pts"].rows, self._places(val, t["variables"], t["joint"])
+        return dict(joint=at["joint"], marginal=at["marginal"], marginal_mean=float(np.mean(list(at["marginal"].values()))),
+                    blocks=at["blocks"], floor=float(np.sqrt(1.0 / m + 1.0 / rows)), m=m, n=rows, estimator=t["estimator"])
 
     def posterior_mmd_test(self, reference, samples=None, n: int = None, variables=None, blocks=None, columns: str = "xy",
                            estimator: str = "mmd", sigma=None, standardise: bool = False, joint: bool = True,
@@ -883,13 +928,8 @@ class PosteriorEvaluation:
         res = ST.permutation_test_from_sums(obs.cpu().numpy(), null.cpu().numpy(), rows, m, estimator, alpha)
         out = self._mmd_result(t, res["statistic"])
         k0 = 1 if joint else 0
-
-        def places(a):
-            return dict(joint=float(a[0]) if joint else None, marginal={v: float(a[k0 + i]) for i, v in enumerate(variables)},
-                        blocks=[float(x) for x in a[k0 + len(variables):]])
-
         holm = ST.holm_adjust(res["p_value"][k0:k0 + len(variables)])
-        out.update(p_value=places(res["p_value"]), threshold=places(res["threshold"]),
+        out.update(p_value=self._places(res["p_value"], variables, joint), threshold=self._places(res["threshold"], variables, joint),
                    marginal_p_holm={v: float(holm[i]) for i, v in enumerate(variables)},
                    rejected=[v for i, v in enumerate(variables) if holm[i] <= alpha],
                    permutations=permutations, seed=seed, alpha=float(alpha))
@@ -917,10 +957,8 @@ class PosteriorEvaluation:
         points -- before anything is launched."""
         from utils import Statistics as ST
         what = "posterior_transport"
-        try:
+        with _named(what):
             ST.check_transport_options(p, directions, seed)
-        except ValueError as e:
-            raise ValueError("%s: %s" % (what, e)) from None
         if columns not in ("xy", "all"):
             raise ValueError("%s: columns must be 'xy' or 'all', got %r" % (what, columns))
         t = self._transport_tables(what, reference, samples, n, variables, blocks, columns, int(directions), int(seed), joint, axes)
@@ -929,65 +967,30 @@ class PosteriorEvaluation:
         out = _nh.sliced_transport_t(pts.St, _nh._columns(t["Y"], pts.device), tab["blocks"], tab["xcols"], tab["ycols"], tab["dirs"],
                                      p, tab["kind"], None, checked=True)
         res = ST.transport_result(out.cpu().numpy(), tab, p)
-        k0 = 1 if joint else 0
-        marginal = {v: float(res["distance"][k0 + i]) for i, v in enumerate(variables)}
-        max_sliced = {v: float(res["max_sliced"][k0 + i]) for i, v in enumerate(variables)}
-        if joint:
-            max_sliced["joint"] = float(res["max_sliced"][0])
-        return dict(joint=float(res["distance"][0]) if joint else None, marginal=marginal,
-                    marginal_mean=float(np.mean(list(marginal.values()))), marginal_max=float(np.max(list(marginal.values()))),
-                    max_sliced=max_sliced,
-                    axes={v: res["axis"][k0 + i] for i, v in enumerate(variables)} if axes else None,
-                    blocks=[float(x) for x in res["distance"][k0 + len(variables):]], m=t["m"], n=pts.rows, p=int(p),
-                    directions=int(directions))
+        dist, top = self._places(res["distance"], variables, joint), self._places(res["max_sliced"], variables, joint)
+        marginal = dist["marginal"]
+        return dict(joint=dist["joint"], marginal=marginal, marginal_mean=float(np.mean(list(marginal.values()))),
+                    marginal_max=float(np.max(list(marginal.values()))),
+                    max_sliced=dict(top["marginal"], joint=top["joint"]) if joint else top["marginal"],
+                    axes=self._places(res["axis"], variables, joint, item=lambda a: a)["marginal"] if axes else None,
+                    blocks=dist["blocks"], m=t["m"], n=pts.rows, p=int(p), directions=int(directions))
 
     def _transport_tables(self, what, reference, samples, n, variables, blocks, columns, directions, seed, joint, axes) -> dict:
-        """The front of `posterior_transport` (that of `posterior_mmd`: the same order of checks, the same handling of the
-        reference; kept apart from `_mmd_tables`, whose tables carry bandwidths and wrap flags) -> dict: pts, Y [m, width]
-        float32, m, width, variables, tab (`Statistics.transport_tables`: the joint block, one block per variable with its
-        axes, the further blocks).  Nothing is launched."""
+        """The two fronts of `posterior_transport` (those of `posterior_mmd`), then what is the transport's own: 1..8192 points
+        in either set, the directions, and the exact per-entry distances (`axes`) of every variable's own block -> dict: pts,
+        of `_reference_front`'s record Y [m, width] float32, m, width, variables; tab (`Statistics.transport_tables` over
+        `Statistics.transport_entries`: a heading enters as two entries).  Nothing is launched."""
         from utils import Statistics as ST
         pts = self._eval_points(what, samples, n)
-        rows, pcol = pts.rows, pts.pcol
-        known = set(self._elimination_ordering)
-        variables = [v for v in self._elimination_ordering if v in reference] if variables is None else list(variables)
-        extra = [tuple(b) for b in blocks] if blocks is not None else []
-        if not variables:
-            raise ValueError("%s: no variable to compare (the reference holds none of the ordering's)" % what)
-        for v in list(variables) + [v for b in extra for v in b]:
-            if v not in known:
-                raise ValueError("%s: variable %s is not in the elimination ordering" % (what, v.name))
-            if v not in reference:
-                raise ValueError("%s: the reference lacks variable %s" % (what, v.name))
-        for b in extra:
-            if not b or any(v not in variables for v in b):
-                raise ValueError("%s: a block is a non-empty tuple of compared variables" % what)
-        ref, m = self._check_points(reference, what, variables, _REFERENCE_NOUNS, host=True)
-        for name, k in (("reference", m), ("posterior", rows)):
+        ref = self._reference_front(what, reference, variables, blocks, joint)
+        for name, k in (("reference", ref.m), ("posterior", pts.rows)):
             if not 1 <= k <= _nh.TRANSPORT_MAX_N:
                 raise ValueError("%s: the %s set has %d points; a set holds 1..%d" % (what, name, k, _nh.TRANSPORT_MAX_N))
-        rcol, width = {}, 0
-        for v in variables:
-            rcol[v] = width
-            width += v.dim
-        Y = np.concatenate([ref[v] for v in variables], axis=1).astype(np.float32)
-        table = ([tuple(variables)] if joint else []) + [(v,) for v in variables] + extra
-        entries = []
-        for blk in table:
-            xr, yr, kd = [], [], []
-            for v in blk:
-                circ = v.circular_dim_list
-                for c in range(v.dim if columns == "all" else min(v.dim, 2)):
-                    kinds = (1, 2) if circ[c] else (0,)             # a heading: its cosine and its sine
-                    xr += [pcol[v] + c] * len(kinds); yr += [rcol[v] + c] * len(kinds); kd += kinds
-            entries.append((np.asarray(xr, dtype=np.int64), np.asarray(yr, dtype=np.int64), np.asarray(kd, dtype=np.uint8)))
         k0 = 1 if joint else 0
-        flags = [bool(axes) and k0 <= b < k0 + len(variables) for b in range(len(table))]
-        try:
-            tab = ST.transport_tables(entries, directions, seed, flags)
-        except ValueError as e:
-            raise ValueError("%s: %s" % (what, e)) from None
-        return dict(pts=pts, Y=Y, m=m, width=width, variables=variables, tab=tab)
+        flags = [bool(axes) and k0 <= b < k0 + len(ref.variables) for b in range(len(ref.table))]
+        with _named(what):
+            tab = ST.transport_tables(ST.transport_entries(ref.pairs(pts, columns), pts.flags), directions, seed, flags)
+        return dict(pts=pts, Y=ref.Y, m=ref.m, width=ref.width, variables=ref.variables, tab=tab)
 
     # ---- what posterior_summary and posterior_modes share: arguments, block table, the weights ------------------------------
     def _summary_front(self, what, samples, n, variables, pairs, weights):
@@ -1005,8 +1008,7 @@ class PosteriorEvaluation:
             if len(p) != 2:
                 raise ValueError("%s: a pair is a tuple (a, b) of two variables" % what)
         for v in variables + [v for p in pairs for v in p]:
-            if v not in known:
-                raise ValueError("%s: variable %s is not in the elimination ordering" % (what, getattr(v, "name", v)))
+            self._need_known(what, v, known)
         for a, b in pairs:
             if a.dim + b.dim > _nh.MOMENTS_MAX_D:
                 raise ValueError("%s: the pair (%s, %s) is %d columns wide; a block holds at most %d"
@@ -1018,21 +1020,15 @@ class PosteriorEvaluation:
         """-> the checked [rows] float64 host weights (a device tensor is brought over); None without weights, for "importance"."""
         if weights is None or importance:
             return None
-        try:
+        with _named(what):
             return _nh._check_weights(weights.detach().cpu().numpy() if torch.is_tensor(weights) else weights, rows)
-        except ValueError as e:
-            raise ValueError("%s: %s" % (what, e)) from None
 
     @staticmethod
-    def _summary_table(variables, pairs, pcol):
+    def _summary_table(pts: EvalPoints, variables, pairs):
         """-> (table, cols, circ): every variable, then every pair; entry = one column of the sample matrix."""
         table = [(v,) for v in variables] + pairs
-        cols, circ = [], []
-        for blk in table:
-            for v in blk:
-                cols.extend(pcol[v] + c for c in range(v.dim))
-                circ.extend(bool(c) for c in v.circular_dim_list)
-        return table, np.asarray(cols, dtype=np.int32), np.asarray(circ, dtype=np.uint8)
+        cols = np.concatenate([pts.cols_of(v) for blk in table for v in blk]).astype(np.int32)
+        return table, cols, pts.flags[cols].astype(np.uint8)
 
     def _weights(self, what, pts: EvalPoints, importance, w_host):
         """-> (weights: None, the host array or, for "importance", exp(log w - max) on the device; ess)."""
@@ -1097,7 +1093,7 @@ class PosteriorEvaluation:
                     raise ValueError("%s: truth of %s must be [%d], got shape %s" % (what, v.name, v.dim, np.shape(truth[v])))
 
         # the table: every variable, then every pair; entry = one column of the sample matrix
-        table, cols, circ = self._summary_table(variables, pairs, pts.pcol)
+        table, cols, circ = self._summary_table(pts, variables, pairs)
         blocks = _nh.pack_moment_blocks([sum(v.dim for v in blk) for blk in table])
         _nh.check_moment_blocks(blocks, cols, pts.total_dim, circ)
         flags = circ if circ.any() else None
@@ -1157,21 +1153,17 @@ class PosteriorEvaluation:
         from utils import Statistics as ST
         what = "posterior_modes"
         pts, importance, variables, pairs = self._summary_front(what, samples, n, variables, pairs, weights)
-        try:
+        with _named(what):
             sigma, _ = ST.check_mode_options(len(variables) + len(pairs), 1, sigma, None, tol, merge, max_iters, max_modes)
-        except ValueError as e:
-            raise ValueError("%s: %s" % (what, e)) from None
         w_host = self._summary_weights(what, weights, importance, pts.rows)
-        table, cols, circ = self._summary_table(variables, pairs, pts.pcol)
+        table, cols, _ = self._summary_table(pts, variables, pairs)
         w_dev, ess = self._weights(what, pts, importance, w_host)
-        flags = np.zeros(pts.total_dim, dtype=bool)
-        flags[cols] = circ != 0
         blocks, at = [], 0
         for blk in table:
             d = sum(v.dim for v in blk)
             blocks.append(cols[at:at + d])
             at += d
-        res = ST.sample_modes_t(pts.St, blocks, circular=flags, weights=w_dev, sigma=sigma, tol=tol, merge=merge,
+        res = ST.sample_modes_t(pts.St, blocks, circular=pts.flags, weights=w_dev, sigma=sigma, tol=tol, merge=merge,
                                 max_iters=max_iters, max_modes=max_modes, checked=True)
         out = dict(modes={}, pair_modes={}, labels={}, n=pts.rows, ess=ess, sigma={}, not_converged={}, unlabelled={})
         for b, blk in enumerate(table):
@@ -1217,33 +1209,21 @@ class PosteriorEvaluation:
         what = "posterior_information"
         pts, _, variables, pairs = self._summary_front(what, samples, n, variables, pairs, None)
         rows = pts.rows
-        try:
+        with _named(what):
             ST.check_knn_options(pts.total_dim, k, "max", None, m=rows)
-        except ValueError as e:
-            raise ValueError("%s: %s" % (what, e)) from None
-        graded, ref, rcol, width = [], None, {}, 0
         if reference is not None:
             graded = [v for v in variables if v in reference]
             if not graded:
                 raise ValueError("%s: the reference holds none of the variables" % what)
-            ref, m_ref = self._check_points(reference, what, graded, _REFERENCE_NOUNS, host=True)
-            if m_ref < int(k):
-                raise ValueError("%s: the reference's %d points hold no %d-th neighbour" % (what, m_ref, int(k)))
-            for v in graded:
-                rcol[v] = width
-                width += v.dim
-
-        def cols_of(v):
-            return np.arange(pts.pcol[v], pts.pcol[v] + v.dim)
-
-        flags = np.zeros(pts.total_dim, dtype=bool)
-        for v in self._elimination_ordering:
-            flags[cols_of(v)] = [bool(c) for c in v.circular_dim_list]
+            ref = self._reference_layout(what, reference, graded)
+            if ref.m < int(k):
+                raise ValueError("%s: the reference's %d points hold no %d-th neighbour" % (what, ref.m, int(k)))
+        flags, cols_of = pts.flags, pts.cols_of
         scale = None if standardise else np.ones(pts.total_dim)
         St = pts.St
 
         ent = ST.knn_entropy_t(St, [cols_of(v) for v in variables], k, flags, scale, "max", checked=True)
-        table, cols, circ = self._summary_table(variables, [], pts.pcol)
+        table, cols, circ = self._summary_table(pts, variables, [])
         blocks = _nh.pack_moment_blocks([v.dim for v in variables])
         _, _, cov_d = _nh.sample_moments_t(St, blocks, cols, circ if circ.any() else None, None, checked=True)
         cov = cov_d.cpu().numpy()
@@ -1261,9 +1241,7 @@ class PosteriorEvaluation:
             for p, pair in enumerate(pairs):
                 out["mutual_information"][pair], out["zeros"][pair] = float(mi["mi"][p]), int(mi["zeros"][p])
         if reference is not None:
-            Y = np.concatenate([ref[v] for v in graded], axis=1).astype(np.float32)
-            div = ST.knn_divergence_t(St, _nh._columns(Y, pts.device), [(cols_of(v), np.arange(rcol[v], rcol[v] + v.dim)) for v in graded],
-                                      k, flags, scale, "max", checked=True)
+            div = ST.knn_divergence_t(St, _nh._columns(ref.Y, pts.device), ref.pairs(pts), k, flags, scale, "max", checked=True)
             out["divergence"] = {v: float(div["divergence"][b]) for b, v in enumerate(graded)}
         return out
 
@@ -1307,10 +1285,8 @@ class PosteriorEvaluation:
                 raise ValueError("%s: %s is %d columns wide; a density block holds at most %d" % (what, v.name, v.dim, _nh.DENSITY_MAX_D))
         if curves is None and maps is None and at is None and truth is None:
             raise ValueError("%s: ask for at least one of curves, maps, at or truth" % what)
-        try:
+        with _named(what):
             ST.check_density_options(bandwidth, rows)
-        except ValueError as e:
-            raise ValueError("%s: %s" % (what, e)) from None
         if curves is not None and (isinstance(curves, bool) or int(curves) != curves or int(curves) < 2):
             raise ValueError("%s: curves is the number of grid points, an integer >= 2, got %r" % (what, curves))
         map_vars = []
@@ -1343,10 +1319,9 @@ class PosteriorEvaluation:
                 if np.ndim(truth[v]) != 1 or len(truth[v]) != v.dim or not np.all(np.isfinite(np.asarray(truth[v], dtype=np.float64))):
                     raise ValueError("%s: truth of %s must be [%d] finite values, got shape %s" % (what, v.name, v.dim, np.shape(truth[v])))
         w_host = self._summary_weights(what, weights, importance, rows)
-        table, cols, circ = self._summary_table(variables, pairs, pts.pcol)
+        table, cols, _ = self._summary_table(pts, variables, pairs)
         w_dev, ess = self._weights(what, pts, importance, w_host)
-        flags = np.zeros(pts.total_dim, dtype=bool)
-        flags[cols] = circ != 0
+        flags = pts.flags
 
         # every block whose bandwidth is needed: variables and pairs, then the curves' coordinates, then the maps' xy blocks
         blocks, at_col = [], 0
@@ -1492,8 +1467,7 @@ class PosteriorEvaluation:
         if not poses or (given and not any(v in truth for v in poses)):
             raise ValueError("%s: truth holds none of the poses" % what)
         for v in poses + landmarks:
-            if v not in known:
-                raise ValueError("%s: variable %s is not in the elimination ordering" % (what, getattr(v, "name", v)))
+            self._need_known(what, v, known)
             if v not in truth:
                 raise ValueError("%s: truth lacks variable %s" % (what, v.name))
             if v.dim < 2 or np.ndim(truth[v]) != 1 or len(truth[v]) != v.dim or not np.all(np.isfinite(np.asarray(truth[v], dtype=np.float64))):
@@ -1502,10 +1476,8 @@ class PosteriorEvaluation:
         if len(set(poses)) != len(poses):
             raise ValueError("%s: a pose is listed twice" % what)
         headed = [v.dim >= 3 and bool(v.circular_dim_list[2]) for v in poses]
-        try:
+        with _named(what):
             strides = ST.check_strides(strides, len(poses)) if len(tuple(strides)) else ()
-        except ValueError as e:
-            raise ValueError("%s: %s" % (what, e)) from None
         if strides and not all(headed):
             raise ValueError("%s: the relative pose error needs a heading on every pose; pass strides=()" % what)
         probs = np.asarray(quantiles, dtype=np.float64).reshape(-1)

@@ -83,6 +83,17 @@ def mmd_from_sums(sums: np.ndarray, m: int, n: int, estimator: str = "MMDb") -> 
         return np.sqrt(u2)
 
 
+def mmd_bandwidths(dims, estimator: str, sigma=None) -> np.ndarray:
+    """THE rule for the kernel bandwidths of blocks of `dims` entries -> float64, one per block: sigma None gives 1 for "mmd"
+    (the reference's k_sigma2 = 1) and sqrt(d) for "MMDb" / "MMDu2"; one value (0-d) is every block's; a list is taken as it
+    is, flattened -- whether it has one value per block, and positive ones, the caller checks in its own words."""
+    dims = np.asarray(dims)
+    if sigma is None:
+        return np.ones(dims.size) if estimator == "mmd" else np.sqrt(dims.astype(np.float64))
+    sig = np.asarray(sigma, dtype=np.float64)
+    return np.broadcast_to(sig, (dims.size,)) if sig.ndim == 0 else sig.reshape(-1)
+
+
 def _block_pairs(blocks):
     """blocks -> [(xcols, ycols)]: a block is a list of column indices (both sets) or an (xcols, ycols) pair of lists."""
     out = []
@@ -128,13 +139,9 @@ def _mmd_block_tables(x, y, blocks, estimator, sigma, scale, circular):
                          % (estimator, 1 if estimator == "MMDb" else 2, m, n))
     pairs = _block_pairs(blocks)
     dims = np.array([p[0].size for p in pairs])
-    if sigma is None:
-        sig = np.ones(len(pairs)) if estimator == "mmd" else np.sqrt(dims.astype(np.float64))
-    else:
-        sig = np.broadcast_to(np.asarray(sigma, dtype=np.float64), (len(pairs),)) if np.ndim(sigma) == 0 else \
-            np.asarray(sigma, dtype=np.float64).reshape(-1)
-        if sig.size != len(pairs):
-            raise ValueError("sigma: one value, or one per block (%d), got %d" % (len(pairs), sig.size))
+    sig = mmd_bandwidths(dims, estimator, sigma)
+    if sig.size != len(pairs):
+        raise ValueError("sigma: one value, or one per block (%d), got %d" % (len(pairs), sig.size))
     xcols = np.concatenate([p[0] for p in pairs])
     ycols = np.concatenate([p[1] for p in pairs])
     if xcols.min() < 0 or xcols.max() >= x.shape[1] or ycols.min() < 0 or ycols.max() >= y.shape[1]:
