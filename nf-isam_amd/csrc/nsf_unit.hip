@@ -2984,21 +2984,20 @@ __global__ void __launch_bounds__(512) nsf_forward_kernel(const float* __restric
     const int DT = D * TILE;
     float* xa = smem;            // [D][TILE]
     float* xb = xa + DT;         // [D][TILE]
-    float* ldacc = xb + DT;      // [TILE]
+    float* ldpart = xb + DT;     // [W][TILE]: each wave's log-det over all layers
     for (int e = threadIdx.x; e < DT; e += blockDim.x) {
         const int p = e / D, k = e - p * D;
         const int q = p0 + p;
         xa[k * TILE + p] = (q < n) ? x[(size_t)q * D + k] : 0.0f;
     }
-    if (threadIdx.x < TILE) ldacc[threadIdx.x] = 0.0f;
     __syncthreads();
     cfloat* kp = (cfloat*)kparams;
     const int Pk = layer_stride > 0 ? layer_stride : LY::count(D);
     float* xin = xa;
     float* xout = xb;
+    float ld = 0.0f;             // the wave's own dims, layer after layer: a fixed order, no atomics
     for (int l = 0; l < L; ++l) {
         cfloat* lp = kp + (size_t)l * Pk;
-        float ld = 0.0f;
         for (int i = w; i < D; i += W) {
             float h1[H], h2[H], th[PoP];
             load_theta<K, H, cfloat*>(lp, i, xin, TILE, lane, h1, h2, th);
@@ -3008,11 +3007,11 @@ __global__ void __launch_bounds__(512) nsf_forward_kernel(const float* __restric
             xout[i * TILE + lane] = zz;
             ld += lad;
         }
-        atomicAdd(&ldacc[lane], ld);
+        if (l == L - 1) ldpart[w * TILE + lane] = ld;
         __syncthreads();
         float* tmp = xin; xin = xout; xout = tmp;
     }
-    // xin holds z
+    // xin holds z, ldpart the W partial log-dets (added in wave order below)
     if (z != nullptr) {
         for (int e = threadIdx.x; e < DT; e += blockDim.x) {
             const int p = e / D, k = e - p * D;
@@ -3022,12 +3021,13 @@ __global__ void __launch_bounds__(512) nsf_forward_kernel(const float* __restric
     }
     if (threadIdx.x < TILE && p0 + (int)threadIdx.x < n) {
         const int q = p0 + threadIdx.x;
-        const float ld = ldacc[threadIdx.x];
-        if (logdet != nullptr) logdet[q] = ld;
+        float ldsum = ldpart[threadIdx.x];
+        for (int v = 1; v < W; ++v) ldsum += ldpart[v * TILE + threadIdx.x];
+        if (logdet != nullptr) logdet[q] = ldsum;
         if (logprob != nullptr) {
             float zz = 0.0f;
             for (int k = 0; k < D; ++k) { const float t = xin[k * TILE + threadIdx.x]; zz += t * t; }
-            logprob[q] = -0.5f * zz - 0.5f * (float)D * 1.8378770664093453f + ld;
+            logprob[q] = -0.5f * zz - 0.5f * (float)D * 1.8378770664093453f + ldsum;
         }
     }
 }
@@ -3503,7 +3503,7 @@ template <int KK, int HH>
 static int unit_forward(const float* x, const float* kparams, int n, int D, float B, int L, int layer_stride, float* z,
                         float* logdet, float* logprob, hipStream_t s) {
     const int W = pick_waves(D);
-    const size_t lds = ((size_t)2 * D * TILE + TILE) * sizeof(float);
+    const size_t lds = ((size_t)2 * D * TILE + (size_t)W * TILE) * sizeof(float);      // two row buffers + W partial log-dets
     int rc = set_lds(nsf_forward_kernel<KK, HH>, lds);
     if (rc) return rc;
     hipLaunchKernelGGL((nsf_forward_kernel<KK, HH>), dim3((n + TILE - 1) / TILE), dim3(64 * W), lds, s, x, kparams, n, D, B, L,
